@@ -14,14 +14,24 @@ into pinned host memory (the trainers are host-side).  Actions ("serpenoid gait"
 precomputed into ONE pinned host buffer and uploaded step by step INSIDE the timed region, on
 the launch stream, as SURVEY §8(d) defines the metric ("including action upload and
 obs/reward/done availability at the trainer rank"; ppo/train.py:122 pays that copy every
-step).  The rate with the actions already resident in HBM is measured in a second timed
-region of the same length and reported beside it (`actions_resident`).
+step).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.
+`--full` adds what the headline does not need, each after and outside its timed region:
+  actions_resident  the rate with the actions already resident in HBM, a second timed region
+                    of the same length
+  contacts_per_substep  an untimed pass that counts contact points per substep (N=1 only)
+  cpu_baseline      the CPU oracle (oracle/, kind "port") timed on this box's host cores on a
+                    bounded sample of the same workload (N=1 only)
+  variants          BASELINE configs[3] and [4] and the round-1 contact model (N=1 only)
+
+Rank 0 prints ONE JSON line (contract in the task statement) with an extra object:
   roofline      dominant kernel (env_step_sched_kernel) against the HBM roofline, algorithmic
-                bytes / HIP-event launch time
-  cpu_baseline  the CPU oracle (oracle/, kind "port") timed on this box's host cores on a
-                bounded sample of the same workload (N=1 only)
+                bytes / HIP-event launch time of the headline's own timed steps
+
+`--dump-outputs DIR` writes what the last timed step returned to the trainer rank, as
+DIR/obs.npy, reward.npy, done.npy (and substeps.npy at N=1), float32: the same arguments give
+the same inputs in every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -286,6 +296,23 @@ def measure_variant(pkg, torch, dev, device_index, E, NL, K, W, friction_seed=No
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays: {name: float32 array, one row per env} -> path/<name>.npy.  Above DUMP_MAX_BYTES in all, a fixed sample of
+    the envs (seed 0, sorted) is written instead, and its env indices as path/env_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    keep = DUMP_MAX_BYTES // (row_bytes + 8)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, env_index=rows.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` from a plain shell, N > 1: the reference's SubprocVecEnv fans out by itself when it is
     constructed (ppo/multiprocessing_env.py:97-117); so does this.  One rank per GPU is started through
@@ -375,8 +402,15 @@ def main():
     ap.add_argument("--policy", action="store_true",
                     help="not the BASELINE metric: actions sampled from an on-device 2x256 actor-critic "
                          "(bullet-envs_amd/rollout.py, SURVEY 8(f)-1) instead of the precomputed gait; 1 GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the actions-resident timed region, the contact "
+                         "histogram pass, the CPU baseline and the variants (--no-cpu-baseline / --no-variants still "
+                         "drop those two); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to the trainer rank as DIR/<name>.npy "
+                         "(float32)")
     args = ap.parse_args()
-    if args.profile:
+    if args.profile or not args.full:
         args.no_cpu_baseline = args.no_variants = True
 
     rank = int(os.environ.get("RANK", "0"))
@@ -456,7 +490,8 @@ def main():
 
     # actions for every step of both timed regions: ONE pinned host buffer on the trainer rank; step j's block is
     # uploaded inside the timed region, on the launch stream, in front of the step
-    second = 0 if (args.profile or args.policy) else K        # the actions-resident region (same length, gait carried on)
+    # the actions-resident region (same length, gait carried on): --full only
+    second = K if (args.full and not args.profile and not args.policy) else 0
     total = W + K + second
     if rank == 0:
         gids = np.arange(world * E)
@@ -555,10 +590,26 @@ def main():
             dist.all_reduce(subs, op=dist.ReduceOp.SUM)
         return t_own, float(t_el.item()), float(subs.item()), loc, k_ms, k_n
 
+    def last_step_outputs():
+        """What the last timed step handed the trainer rank (rank 0, after timed_region's synchronize): obs, reward, done
+        and, at N = 1, the substep counts, as float32 host arrays with one row per env."""
+        if net is not None:
+            obs, rew, done = pol_state["h_obs"], pol_state["h_rew"], pol_state["h_done"]
+            sub = local.substeps
+        else:
+            obs, rew, done = h_obs, h_rew, h_done
+            sub = sub_rows[K - 1] if world == 1 and K > 0 else None
+        arrays = {"obs": obs.numpy(), "reward": rew.numpy(), "done": done.numpy()}
+        if sub is not None:
+            arrays["substeps"] = sub.cpu().numpy()
+        return {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+
     for j in range(W):
         one_step(j)
     torch.cuda.synchronize()
     own_s, elapsed, substeps, local_sub, kernel_ms, kcount = timed_region(W, False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs())
     resident = None
     if second:
         r_own, r_el, r_sub, _r_loc, r_kms, _ = timed_region(W + K, True)
@@ -580,14 +631,14 @@ def main():
     # [0] substeps that went through the streamed-row solve because their contacts outgrew the register-resident one's
     # slots (16 links), [1] [2] contacts left without rows: must be zeros
     overflow = local.stepper.contact_overflow()
-    # Not the headline: further single-GPU measurements, after and outside its timed region (default run only).
+    # Not the headline: further single-GPU measurements, after and outside its timed region (--full, default configuration).
     #   configs3_c32 / configs4_c16_fric: BASELINE configs[3] and [4], so that the driver's record carries a timed line
     #     for every single-GPU configuration (own K, ms_per_step, mean substeps, roofline block, one-thread CPU leg);
     #   round1_contact_model: the stateless two-point manifold on implicit cylinders that rounds 1 and 2 measured
     #     (self_collision 0: those rounds built no link-link rows for 16 links), keeps the record comparable.
     variants = None
     headline_hist = None
-    if rank == 0 and world == 1 and not args.policy and not args.profile:
+    if args.full and rank == 0 and world == 1 and not args.policy and not args.profile:
         # (an untimed pass of its own, the gait stream carried on)
         more = [torch.from_numpy(gait_actions(np.arange(E), total + j, A).astype(np.float32)).to(dev) for j in range(HIST_STEPS)]
         headline_hist = histogram_pass(local, torch, more)
@@ -661,6 +712,7 @@ def main():
                                     world * E * A * 4, "RCCL scatter, " if world > 1 else "",
                                     "RCCL gather to rank 0, " if world > 1 else ""),
                 "self_launched": bool(os.environ.get("SNK_BENCH_SELF_LAUNCHED")),
+                "full": bool(args.full),
                 "parallelism": "envs sharded over %d GPU(s), no data-path collective; "
                                "RCCL actions scatter + obs/reward/done gather to rank 0" % world
                                if world > 1 else "1 GPU, one wavefront per env",

@@ -209,6 +209,31 @@ def test_bench_plain_multi_gpu_invocation_refuses_cleanly_without_the_gpus():
     assert "--gpus 2 but this node shows" in out.stderr
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_above_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one .npy per output; above the byte cap a fixed sample of the envs (the same one every
+    time) together with the env indices it took."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("snk_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    arrays = {"obs": rng.normal(size=(1000, 56)).astype(np.float32), "reward": rng.normal(size=1000).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, a in arrays.items():
+        got = np.load(str(tmp_path / "all" / (k + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    assert not os.path.exists(str(tmp_path / "all" / "env_index.npy"))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * (57 * 4 + 8))
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    idx = np.load(str(tmp_path / "s1" / "env_index.npy"))
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(str(tmp_path / "s2" / "env_index.npy")))
+    rows = idx.astype(np.int64)
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(str(tmp_path / "s1" / (k + ".npy"))), a[rows])
+
+
 def test_subproc_vec_env_refuses_thunks_that_differ(pkg):
     """The reference forks one process per thunk and honours each one's own settings (ppo/multiprocessing_env.py:106-111);
     one GPU handle runs ONE parameter set, so thunks that differ are refused -- naming the thunk and the first differing

@@ -752,7 +752,7 @@ def test_bench_multi_rank_rehearsal():
     # two ranks: with the launcher, the parent bench.py (which never opens the GPU) and pytest that is at most four
     # processes with the GPU open, inside the box's limit of six (more ranks: tests/test_dist_gloo.py runs 2 / 4 / 8)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--envs-per-gpu", "512"]
+           "--envs-per-gpu", "512", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -782,7 +782,8 @@ def test_bench_line_contract_and_profile_form():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "SNK_BENCH_BACKEND")}
     base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--envs-per-gpu", "512"]
-    out = subprocess.run(base + ["--no-cpu-baseline", "--no-variants"], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    out = subprocess.run(base + ["--full", "--no-cpu-baseline", "--no-variants"], cwd=root, env=env, capture_output=True,
+                         text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert r["n_gpus"] == 1 and r["unit"] == "env-steps/s" and r["dtype"] == "f32" and r["vs_baseline"] is None
@@ -795,6 +796,38 @@ def test_bench_line_contract_and_profile_form():
     p = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert p["actions_resident"] is None and p["config"]["contacts_per_substep"] is None
     assert p["cpu_baseline"] is None and p["variants"] is None and p["roofline"]["launches"] == 3
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times K steps and measures nothing else; --dump-outputs writes what the last timed step
+    returned (obs / reward / done block and substep counts, float32), the same in two runs of the same arguments."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "SNK_BENCH_BACKEND")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+            "--envs-per-gpu", "512"]
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = subprocess.run(base + ["--dump-outputs", d], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == 4 and r["roofline"]["launches"] == 4 and r["ms_per_step"] > 0 and r["value"] > 0
+        assert r["higher_is_better"] is True and r["dtype"] == "f32" and r["unit"] == "env-steps/s"
+        assert r["actions_resident"] is None and r["cpu_baseline"] is None and r["variants"] is None
+        assert r["config"]["contacts_per_substep"] is None and r["config"]["full"] is False
+        dumps.append({k: np.load(os.path.join(d, k + ".npy")) for k in ("obs", "reward", "done", "substeps")})
+    a, b = dumps
+    assert a["obs"].shape == (512, 56) and a["reward"].shape == a["done"].shape == a["substeps"].shape == (512,)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert set(np.unique(a["done"])) <= {0.0, 1.0} and a["substeps"].max() > 0 and np.isfinite(a["obs"]).all()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 @pytest.mark.gpu

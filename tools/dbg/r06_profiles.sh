@@ -1,5 +1,5 @@
 #!/bin/bash
-# The three configurations' rocprofv3 passes on a round-6 build, each with the W / K the default bench.py run times it
+# The three configurations' rocprofv3 passes on a round-6 build, each with the W / K `bench.py --full` times it
 # with (headline 10 + 100; variants.configs4_c16_fric 10 + 50; variants.configs3_c32 6 + 20), so that the trace's timed
 # launches carry the same substep counts as the bench line's:
 #   bash tools/dbg/r06_profiles.sh  -> gpurun_out/prof6/{c16,c16_fric,c32}
