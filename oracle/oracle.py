@@ -95,6 +95,7 @@ def _load(f32=False):
         "orc_momentum": (None, [vp, D, D, D]),
         "orc_contacts": (C.c_int32, [vp, D, C.c_int32]),
         "orc_last_normal_impulses": (C.c_int32, [vp, D, C.c_int32]),
+        "orc_last_friction_impulses": (C.c_int32, [vp, D, C.c_int32]),
         "orc_cylinder_frames": (C.c_int32, [vp, D]),
         "orc_debug_gjk": (C.c_double, [vp, D, D, D]),
         "orc_contacts_full": (C.c_int32, [vp, D, C.c_int32]),
@@ -351,4 +352,10 @@ class OracleEnv:
     def last_normal_impulses(self, maxc=256):
         out = np.zeros(maxc)
         nc = self.lib.orc_last_normal_impulses(self.h, _dp(out), maxc)
+        return out[:nc]
+
+    def last_friction_impulses(self, maxc=256):
+        """[nc, 2]: the accumulated impulses of the two friction rows of every contact the last substep solved."""
+        out = np.zeros((maxc, 2))
+        nc = self.lib.orc_last_friction_impulses(self.h, _dp(out), maxc)
         return out[:nc]

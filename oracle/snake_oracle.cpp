@@ -241,6 +241,7 @@ struct orc_env {
     int last_iters;
     std::vector<Contact> contacts;
     std::vector<Real> last_normal_impulse;
+    std::vector<Real> last_friction_impulse;   /* 2 per contact: the two tangent rows' accumulated impulses */
     std::vector<Manifold> manifolds;   /* contact_model 1: one per link (used by the links that carry a cylinder) */
     /* obstacle 2: the free box (a btMultiBody without links [U]) */
     Real bpos[3], bquat[4], bomega[3], bvel[3];
@@ -1814,6 +1815,8 @@ void substep(orc_env* e, const Real* targets) {
         tau2[r.joint] += r.J[6 + r.joint] * r.applied / dt;
     }
     e->last_normal_impulse.assign(nc, 0);
+    e->last_friction_impulse.assign(2 * nc, 0);
+    for (int k2 = 0; k2 < 2 * nc; k2++) e->last_friction_impulse[k2] = frictions[k2].applied;
     for (int ci = 0; ci < nc; ci++) {
         const Contact& c = e->contacts[ci];
         e->last_normal_impulse[ci] = normals[ci].applied;
@@ -2052,6 +2055,7 @@ void orc_hard_reset(orc_env* e) {
     e->last_iters = 0;
     e->contacts.clear();
     e->last_normal_impulse.clear();
+    e->last_friction_impulse.clear();
     e->manifolds.clear();    /* resetSimulation + loadURDF: a new world (a soft reset keeps the contact cache [U]) */
     e->pairs.clear();
     box_reset(e);
@@ -2338,6 +2342,11 @@ int32_t orc_contacts_full(orc_env* e, double* out, int32_t maxc) {
 }
 /* the contacts the LAST substep solved, same record; aligned with orc_last_normal_impulses */
 int32_t orc_last_contacts_full(const orc_env* e, double* out, int32_t maxc) { return dump_contacts(e->contacts, out, maxc); }
+int32_t orc_last_friction_impulses(const orc_env* e, double* out, int32_t maxc) {
+    int nc = (int)e->last_friction_impulse.size() / 2;
+    for (int i = 0; i < 2 * nc && i < 2 * maxc; i++) out[i] = e->last_friction_impulse[i];
+    return nc;
+}
 int32_t orc_last_normal_impulses(const orc_env* e, double* out, int32_t maxc) {
     int nc = (int)e->last_normal_impulse.size();
     for (int i = 0; i < nc && i < maxc; i++) out[i] = e->last_normal_impulse[i];

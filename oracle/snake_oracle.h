@@ -217,6 +217,9 @@ int32_t  orc_contacts_full(orc_env* e, double* out, int32_t max_contacts);
 int32_t  orc_last_contacts_full(const orc_env* e, double* out, int32_t max_contacts);
 /* impulses of the last substep: normal impulses per contact */
 int32_t  orc_last_normal_impulses(const orc_env* e, double* out, int32_t max_contacts);
+/* ... and the two friction rows' impulses per contact (out [max_contacts x 2]; friction_directions 1: the second 0);
+ * returns the contact count */
+int32_t  orc_last_friction_impulses(const orc_env* e, double* out, int32_t max_contacts);
 
 /* CPU-baseline driver for bench.py: n_envs envs x (warmup + steps) batched env-steps of the
  * serpenoid-gait stream on n_threads threads, timed inside (no Python in the loop).  Returns seconds for the
