@@ -42,6 +42,7 @@ class SnkParams(C.Structure):
         ("collision_force", C.c_double), ("collision_penalty", C.c_double),
         ("done_penalty", C.c_double),
         ("contact_order", C.c_int32), ("reserved0", C.c_int32),
+        ("noncontact_order", C.c_int32), ("contact_erp_rule", C.c_int32),
     ]
 
 
@@ -85,6 +86,7 @@ SYMBOLS = {
     "snk_get_ground_friction": (C.c_int, [_vp, _F]),
     "snk_debug_set_tickets": (C.c_int, [_vp, C.c_uint32]),
     "snk_debug_raise_alarm": (C.c_int, [_vp]),
+    "snk_debug_noncontact_order": (C.c_int, [C.c_int32, _I32]),
     "snk_selftest": (C.c_int, [C.c_int32]),
     "snk_timing_enable": (C.c_int, [_vp, C.c_int32]),
     "snk_timing_read": (C.c_int, [_vp, _D, _I32]),
@@ -146,6 +148,14 @@ def default_params(**over):
                 raise AttributeError("snk_params has no field %r" % k)
             setattr(p, k, v)
     return p
+
+
+def noncontact_order(n_modules):
+    """The sweep order the kernels are compiled with for snk_params::noncontact_order 1 (snk_debug_noncontact_order):
+    2n entries, 0..n-1 = limit j, n..2n-1 = motor j - n, in the order of the forward sweep."""
+    out = np.zeros(2 * int(n_modules), np.int32)
+    check(load().snk_debug_noncontact_order(int(n_modules), out.ctypes.data_as(_I32)), "snk_debug_noncontact_order")
+    return out
 
 
 def fptr(a):

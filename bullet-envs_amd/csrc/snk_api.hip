@@ -71,9 +71,10 @@ struct snk_handle {
 
 namespace {
 
-// packed_stride > 0 (snk_step_packed): obs rows of that stride, reward and done flag behind each row's observation
-template <int N, bool V2>
-int launch_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode,
+// packed_stride > 0 (snk_step_packed): obs rows of that stride, reward and done flag behind each row's observation.
+// RULES: the solver-rules variant the solving kernels are instantiated for (snk_device.hpp: LdsFor, rules_variant)
+template <int N, bool V2, int RULES>
+int launch_step_o(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode,
                 hipStream_t st, int packed_stride = 0) {
     const int stride = packed_stride > 0 ? packed_stride : h->D.obs_dim;
     const int packed = packed_stride > 0 ? 1 : 0;
@@ -85,22 +86,39 @@ int launch_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done
         a.rows_all = h->d_rows; a.mf_all = h->d_mf; a.ovf = h->d_ovf; a.box_all = h->d_box; a.sc = h->sched;
         a.model_slot = h->model_slot; a.vec_mode = vec_mode; a.n_envs = h->n_envs;
         a.obs_stride = stride; a.packed = packed; a.pad_ = 0;
-        hipLaunchKernelGGL((snk::env_step_sched_kernel<N, V2>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, a);
+        hipLaunchKernelGGL((snk::env_step_sched_kernel<N, V2, RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, a);
         return 0;
     }
     if (h->plan)
         hipLaunchKernelGGL((snk::plan_kernel<N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->d_order,
                            h->n_envs);
-    hipLaunchKernelGGL((snk::env_step_kernel<N, V2>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, h->d_model, h->d_recs,
+    hipLaunchKernelGGL((snk::env_step_kernel<N, V2, RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, h->d_model, h->d_recs,
                        h->d_mu, act, obs, rew, done, sub, vec_mode, h->n_envs, h->plan ? h->d_order : nullptr, h->d_rows, h->d_mf, h->d_ovf, h->d_box,
                        stride, packed);
     return 0;
 }
 template <int N, bool V2>
-int launch_substep(snk_handle* h, const float* tgt, int k, int32_t* info, hipStream_t st) {
-    hipLaunchKernelGGL((snk::substep_kernel<N, V2>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, h->d_model, h->d_recs,
+int launch_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode,
+                hipStream_t st, int packed_stride = 0) {
+    switch (snk::rules_variant(h->D)) {
+    case 2: return launch_step_o<N, V2, 2>(h, act, obs, rew, done, sub, vec_mode, st, packed_stride);
+    case 1: return launch_step_o<N, V2, 1>(h, act, obs, rew, done, sub, vec_mode, st, packed_stride);
+    default: return launch_step_o<N, V2, 0>(h, act, obs, rew, done, sub, vec_mode, st, packed_stride);
+    }
+}
+template <int N, bool V2, int RULES>
+int launch_substep_o(snk_handle* h, const float* tgt, int k, int32_t* info, hipStream_t st) {
+    hipLaunchKernelGGL((snk::substep_kernel<N, V2, RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, h->d_model, h->d_recs,
                        h->d_mu, tgt, k, info, h->n_envs, h->d_rows, h->d_mf, h->d_ovf, h->d_box);
     return 0;
+}
+template <int N, bool V2>
+int launch_substep(snk_handle* h, const float* tgt, int k, int32_t* info, hipStream_t st) {
+    switch (snk::rules_variant(h->D)) {
+    case 2: return launch_substep_o<N, V2, 2>(h, tgt, k, info, st);
+    case 1: return launch_substep_o<N, V2, 1>(h, tgt, k, info, st);
+    default: return launch_substep_o<N, V2, 0>(h, tgt, k, info, st);
+    }
 }
 template <int N, bool V2>
 int launch_reset(snk_handle* h, const uint8_t* mask, float* obs, int hard, hipStream_t st) {
@@ -132,14 +150,22 @@ int resident_waves(size_t bytes, int device, int* out) {
     *out = per_cu * prop.multiProcessorCount;
     return 0;
 }
+template <int N, bool V2, int RULES>
+int set_lds_attr_rules(size_t bytes) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::env_step_kernel<N, V2, RULES>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::env_step_sched_kernel<N, V2, RULES>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::substep_kernel<N, V2, RULES>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return 0;
+}
 template <int N, bool V2>
-int set_lds_attr(size_t bytes) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::env_step_kernel<N, V2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::env_step_sched_kernel<N, V2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::substep_kernel<N, V2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+int set_lds_attr(size_t bytes, int rules) {
+    // (every solver-rules variant has the same LDS image: the rules are compile-time constants only)
+    const int rc = rules == 2 ? set_lds_attr_rules<N, V2, 2>(bytes)
+                              : (rules == 1 ? set_lds_attr_rules<N, V2, 1>(bytes) : set_lds_attr_rules<N, V2, 0>(bytes));
+    if (rc) return rc;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::reset_kernel<N, V2>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::obs_kernel<N, V2>),
@@ -253,6 +279,8 @@ void snk_default_params(snk_params* p) {
     p->done_penalty = -5.0;
     p->contact_order = 0;
     p->reserved0 = 0;
+    p->noncontact_order = 0;
+    p->contact_erp_rule = 0;
 }
 
 int snk_destroy(snk_handle* h);
@@ -276,7 +304,7 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     h->v2 = h->n == 16 && getenv("SNK_FORCE_STREAMED") == nullptr && p->obstacle != 2;      // (a free box: six more
                                                                                             //  components, streamed rows)
     h->lds_bytes = h->n == 16 ? (h->v2 ? sizeof(snk::Lds<16, true>) : sizeof(snk::Lds<16, false>)) : sizeof(snk::Lds<32, false>);
-    int rc = SNK_DISPATCH(h, set_lds_attr, h->lds_bytes);
+    int rc = SNK_DISPATCH(h, set_lds_attr, h->lds_bytes, snk::rules_variant(h->D));
     if (rc) return rc;
     const size_t ne = (size_t)n_envs;
     HIP_TRY(hipMalloc(&h->d_model, sizeof(snk::DevModel)));
@@ -420,6 +448,10 @@ int snk_create(const snk_params* p, int32_t n_envs, int32_t device, snk_handle**
     if (p->contact_order < 0) return fail("snk_create: contact_order must be 0 (link order), 1 (reversed), 2 (Bullet's quickSort on equal keys) or k >= 3 (a fixed permutation)");
     if (p->contact_order != 0 && p->contact_model != 1)
         return fail("snk_create: contact_order needs contact_model 1 (it orders the persistent ground manifolds)");
+    if (p->noncontact_order != 0 && p->noncontact_order != 1)
+        return fail("snk_create: noncontact_order must be 0 (limits, then motors, by joint index) or 1 (Bullet's quickSort on equal keys)");
+    if (p->contact_erp_rule != 0 && p->contact_erp_rule != 1)
+        return fail("snk_create: contact_erp_rule must be 0 (contact_erp at any depth) or 1 (limit_erp above the split-impulse threshold)");
     if (p->warm_start && p->contact_model != 1)
         return fail("snk_create: warm_start needs contact_model 1 (the impulses live in the persistent contact cache)");
     if (!(p->breaking_threshold > 0.0)) return fail("snk_create: breaking_threshold must be positive");
@@ -821,6 +853,21 @@ int snk_debug_raise_alarm(snk_handle* h) {
     // a step still running sees it at its next bounded wait and drains
     __atomic_store_n(h->h_alarm, 1, __ATOMIC_SEQ_CST);
     return 0;
+}
+
+int snk_debug_noncontact_order(int32_t n_modules, int32_t* out) {
+    if (!out) return fail("snk_debug_noncontact_order: null output");
+    auto write = [out](auto tab) {
+        constexpr int n = (int)(sizeof(tab.motor_at) / sizeof(tab.motor_at[0]));
+        for (int k = 0; k < n; k++) {
+            out[k] = n + tab.motor_at[k];            // the motors first ...
+            out[n + k] = tab.motor_at[k];            // ... then the limits, in the same joint order
+        }
+        return 0;
+    };
+    if (n_modules == 16) return write(snk::NoncontactOrder<16>::tab);
+    if (n_modules == 32) return write(snk::NoncontactOrder<32>::tab);
+    return fail("snk_debug_noncontact_order: n_modules must be 16 or 32");
 }
 
 int snk_selftest(int32_t device) {

@@ -164,6 +164,8 @@ __device__ __forceinline__ float lane_bcast(float x, int src_lane_uniform) {
 template <int N, int NL>
 struct LdsCommon {
     static constexpr int kN = N;
+    static constexpr int kNCO = 0;       // snk_params::noncontact_order this image's kernels are compiled for (LdsFor)
+    static constexpr bool kERP = false;  // contact_erp_rule's depth test compiled in (LdsFor)
     static constexpr int NB = N + 1;     // composite bodies
     static constexpr int ND = N + 6;     // generalized velocity [omega_w, v_w, qd]
     static constexpr int NC = 4 * N;     // contact slots: 2n cylinders x 2 end caps
@@ -357,6 +359,21 @@ struct Lds<N, true> : LdsCommon<N, N> {
         fill(app, 2 * (N / 2 + NC / 2 + NC)); fill(&mfl[0][0], 24 * 2 * N);
     }
 };
+
+// The image the solving kernels of one solver-rules variant use (RULES, a kernel template parameter): the same layout, with
+// the rules as compile-time constants.  RULES 0 = both rules at their defaults: Lds itself, so that the default kernels
+// compile from exactly the code they did before the rules existed.  RULES 1 = noncontact_order 0 with contact_erp_rule's
+// depth test (LT::kERP); RULES 2 = noncontact_order 1 (LT::kNCO: the solves unroll their motor sweeps over that order)
+// with the depth test -- under contact_erp_rule 0 both of its ERPs are contact_erp, the same bits as without it.
+template <class Base, int NCO>
+struct LdsRules : Base {
+    static constexpr int kNCO = NCO;
+    static constexpr bool kERP = true;
+};
+template <int N, bool V2, int RULES>
+using LdsFor = typename std::conditional<RULES == 0, Lds<N, V2>, LdsRules<Lds<N, V2>, RULES == 2 ? 1 : 0>>::type;
+// the variant a parameter set runs on
+inline int rules_variant(const DevModel& D) { return D.noncontact_order ? 2 : (D.contact_erp_rule ? 1 : 0); }
 
 __device__ __forceinline__ void lds_sync() { __syncthreads(); }
 
@@ -1000,7 +1017,9 @@ __device__ void build_rows_v1(LT& L, const DevModel& M, int lane, int nc, int& n
             float target = -rv_;
             if (kind == 0) {
                 const float pen = dist + M.slop;
-                target += pen > 0.f ? -pen * M.inv_dt : -pen * M.contact_erp * M.inv_dt;
+                float erp = M.contact_erp;
+                if constexpr (LT::kERP) erp = pen > M.erp_split ? M.erp_shallow : M.erp_deep;     // contact_erp_rule
+                target += pen > 0.f ? -pen * M.inv_dt : -pen * erp * M.inv_dt;
             }
             // the record's columns (Lds<N, false>): J / den with -rhs and 0 in the pad columns; M^-1 J^T with 0 and den
             // (J and M^-1 J^T are zero in the pad columns as they come)
@@ -1085,7 +1104,10 @@ __device__ void build_rows_v1(LT& L, const DevModel& M, int lane, int nc, int& n
         unsigned long long bal = __ballot(viol);
         nlim = __popcll(bal);
         if (viol) {
-            int idx = __popcll(bal & ((1ull << lane) - 1ull));
+            // noncontact_order 1: the violated limits in the quickSort's joint order, not by joint index
+            unsigned long long before = (1ull << lane) - 1ull;
+            if constexpr (LT::kNCO != 0) before = NoncontactOrder<N>::tab.below[lane];
+            int idx = __popcll(bal & before);
             float den = mden_j;
             float dinv = den > 1.1920929e-7f ? 1.0f / den : 0.f;
             float rel = sgn * L.qd()[lane];
@@ -1400,7 +1422,8 @@ __device__ float pgs_v1(LT& L, const DevModel& M, int lane, int nc, int nn, floa
             float Uv = 0.f;                                              // lane 6+j: the dI motor j got in this sweep
 #pragma unroll
             for (int jj = 0; jj < N; jj++) {
-                const int j = fwd ? jj : N - 1 - jj;
+                // (noncontact_order 1: the quickSort's joint order, a compile-time table -- RMm[] stays in registers)
+                const int j = LT::kNCO ? NoncontactOrder<N>::motor(fwd, jj) : (fwd ? jj : N - 1 - jj);
                 float u = (TARGV - dv) * DINVV;                          // every motor's candidate dI, lane-local (DINVV = 0 beyond the joints)
                 if (mi < 1e30f) u = fminf(fmaxf(ACCV + u, -mi), mi) - ACCV;   // (a lane's ACCV only matters at its own step)
                 const float sdI = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), 6 + j));
@@ -1410,8 +1433,13 @@ __device__ float pgs_v1(LT& L, const DevModel& M, int lane, int nc, int nn, floa
             ACCV += Uv;
             lsq_nc = fmaxf(lsq_nc, cols_max<LT::kMO - 1>(fabsf(Uv * DENV)));
         };
-        if (it & 1) { limit_rows(true); motor_rows(std::true_type{}); }
-        else { motor_rows(std::false_type{}); limit_rows(false); }
+        if constexpr (LT::kNCO == 0) {      // list = [limits..., motors...], odd iterations forwards
+            if (it & 1) { limit_rows(true); motor_rows(std::true_type{}); }
+            else { motor_rows(std::false_type{}); limit_rows(false); }
+        } else {                            // noncontact_order 1: list = [motors..., limits...]
+            if (it & 1) { motor_rows(std::true_type{}); limit_rows(true); }
+            else { limit_rows(false); motor_rows(std::false_type{}); }
+        }
         if (nc > 0) {
             // normals: slot k of the ring holds contact (trip base + k).  A slot is refilled with
             // the contact kRingN further on as soon as it has been consumed -- if there is one: round 1 refilled
@@ -1705,7 +1733,13 @@ __device__ __forceinline__ void substep_v1(LT& L, const DevModel& M, int lane, f
         if (lane < N) L.tauj[lane] = -M.joint_damp * L.qd_old[lane];
         lds_sync();
         if (lane == 0) {
-            for (int i = 0; i < nn; i++) L.tauj[L.nc_joint[i]] += L.nc_sign[i] * L.nc_app[i] * M.inv_dt;
+            // in the list's order, as the oracle sums (the storage keeps the limits in front of the motors either way;
+            // noncontact_order 1 sweeps -- and sums -- the motors first)
+            const int nlim_ = nn - N;
+            for (int i = 0; i < nn; i++) {
+                const int r = LT::kNCO ? (i < N ? nlim_ + i : i - N) : i;
+                L.tauj[L.nc_joint[r]] += L.nc_sign[r] * L.nc_app[r] * M.inv_dt;
+            }
         }
         lds_sync();
         // velocities changed in (3): refresh w, v, zeta of every body (pose unchanged)
@@ -1758,7 +1792,7 @@ __device__ __forceinline__ void substep_v1(LT& L, const DevModel& M, int lane, f
         L.box[7 + lane - ND] = fminf(fmaxf(x, -M.max_vel), M.max_vel);
     }
     if (lane < N) {
-        // motor rows sit after the limit rows in the non-contact list
+        // motor rows sit after the limit rows in the non-contact list's storage (whatever order the sweep takes them in)
         L.taum()[lane] = L.nc_app[nn - N + lane] * M.inv_dt;
     }
     lds_sync();
@@ -1874,7 +1908,7 @@ __device__ __forceinline__ void substep(LT& L, const DevModel& M0, int lane_in, 
             // contact cache travels through its block of global memory, where the streamed-row kernels keep it.  The
             // rule is per substep and a function of the state alone, so results do not depend on the schedule, and the
             // single-substep API takes the same path.  Counted (snk_contact_overflow[0]), never silent.
-            using L1 = Lds<LT::kN, false>;
+            using L1 = LdsFor<LT::kN, false, LT::kNCO ? 2 : (LT::kERP ? 1 : 0)>;
             static_assert(sizeof(L1) <= sizeof(LT), "the streamed-row image must fit the register-resident one's allocation");
             L1& Lx = *reinterpret_cast<L1*>(&L);
             // The cache goes out with plain stores and this CU's vector L1 is invalidated behind them (what an agent-scope
@@ -2071,7 +2105,7 @@ __device__ __forceinline__ void soft_reset(LT& L, int lane) {
 // ----------------------------------------------------------------------------------
 // kernels
 // ----------------------------------------------------------------------------------
-template <int N, bool V2>
+template <int N, bool V2, int RULES = 0>
 __global__ __launch_bounds__(64, 2) void env_step_kernel(const DevModel* __restrict__ Mp, float* __restrict__ recs,
                                                       const float* __restrict__ mu_plane,
                                                       float* __restrict__ actions, float* __restrict__ obs,
@@ -2081,7 +2115,7 @@ __global__ __launch_bounds__(64, 2) void env_step_kernel(const DevModel* __restr
                                                       float* __restrict__ mf_all, unsigned long long* __restrict__ ovf,
                                                       float* __restrict__ box_all, int obs_stride, int packed) {
     extern __shared__ float4 smem_raw[];
-    using LT = Lds<N, V2>;
+    using LT = LdsFor<N, V2, RULES>;
     LT& L = *reinterpret_cast<LT*>(smem_raw);
     const DevModel& M = *Mp;
     // longest-first schedule: workgroup b takes the envs with the b-th, (b + G)-th, ... largest predicted work (G
@@ -2173,7 +2207,7 @@ __global__ __launch_bounds__(64, 2) void env_step_kernel(const DevModel* __restr
     }
 }
 
-template <int N, bool V2>
+template <int N, bool V2, int RULES = 0>
 __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restrict__ Mp, float* __restrict__ recs,
                                                      const float* __restrict__ mu_plane,
                                                      const float* __restrict__ targets, int k,
@@ -2181,7 +2215,7 @@ __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restri
                                                      float* __restrict__ mf_all, unsigned long long* __restrict__ ovf,
                                                      float* __restrict__ box_all) {
     extern __shared__ float4 smem_raw[];
-    using LT = Lds<N, V2>;
+    using LT = LdsFor<N, V2, RULES>;
     LT& L = *reinterpret_cast<LT*>(smem_raw);
     const DevModel& M = *Mp;
     const int lane = threadIdx.x;
@@ -2559,11 +2593,11 @@ __device__ __forceinline__ Sched load_sched(StepArgPtr p) {
     return sc;
 }
 
-template <int N, bool V2>
+template <int N, bool V2, int RULES = 0>
 __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs args_by_value) {
     (void)args_by_value;            // read through step_args() only
     extern __shared__ float4 smem_raw[];
-    using LT = Lds<N, V2>;
+    using LT = LdsFor<N, V2, RULES>;
     LT& L = *reinterpret_cast<LT*>(smem_raw);
     int lane = threadIdx.x;
 #ifdef SNK_SCHED_DEBUG

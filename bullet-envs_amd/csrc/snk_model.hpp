@@ -75,7 +75,87 @@ struct DevModel {
     float m_root;
     float zbase[3];   // z axis of the `base` link in body-0 frame (joint-0 force component)
     float hbase[3];   // COM of the `base` link in body-0 frame (height sample)
+    // snk_params::contact_erp_rule: a contact row whose penetration pen = dist + slop is <= 0 takes the ERP
+    // pen > erp_split ? erp_shallow : erp_deep (rule 0: both are contact_erp; rule 1: limit_erp (m_erp) above the
+    // split-impulse threshold, contact_erp (m_erp2) at or below it)
+    float erp_shallow, erp_deep, erp_split;
+    int noncontact_order, contact_erp_rule;   // the switches themselves (snk_device.hpp: rules_variant picks the kernels)
 };
+
+// btAlignedObjectArray::quickSort (Hoare partition, pivot = the middle element, `i <= j` swap) on LEN equal keys, restated:
+// every partition reverses its range and recurses into the two halves.  perm[position] = the element that ends there.
+// One definition for the host (contact_order 2, snk_debug_noncontact_order) and the kernels (noncontact_order 1).
+template <int LEN>
+struct QsEqualKeys {
+    int perm[LEN > 0 ? LEN : 1];
+};
+template <int LEN>
+constexpr QsEqualKeys<LEN> qs_equal_keys() {
+    QsEqualKeys<LEN> q{};
+    for (int c = 0; c < LEN; c++) q.perm[c] = c;
+    int stack[2 * (LEN > 0 ? LEN : 1)][2] = {};
+    int sp = 0;
+    if (LEN > 1) { stack[sp][0] = 0; stack[sp][1] = LEN - 1; sp++; }
+    while (sp > 0) {
+        sp--;
+        const int lo = stack[sp][0], hi = stack[sp][1];
+        int i = lo, j = hi;
+        do {
+            if (i <= j) { const int t = q.perm[i]; q.perm[i] = q.perm[j]; q.perm[j] = t; i++; j--; }
+        } while (i <= j);
+        // (the two recursive calls work on disjoint ranges: their order does not matter)
+        if (i < hi) { stack[sp][0] = i; stack[sp][1] = hi; sp++; }
+        if (lo < j) { stack[sp][0] = lo; stack[sp][1] = j; sp++; }
+    }
+    return q;
+}
+
+// snk_params::noncontact_order 1: the world's constraint list [limit 0..n-1, motor 0..n-1] after that quickSort.  Its first
+// partition reverses the whole list and splits it into halves, so the motors come first, then the limits, each half in
+// the same pattern: motor_at[k] = the joint of the k-th motor row, and the limit rows follow in the same joint order.
+// below[j] = the joints whose rows come before joint j's in that order (a violated limit's place among the violated
+// ones is popcount(violated & below[j])).
+template <int N>
+struct NoncontactTables {
+    int motor_at[N], rank[N];
+    unsigned long long below[N];
+};
+template <int N>
+constexpr NoncontactTables<N> noncontact_tables() {
+    constexpr QsEqualKeys<2 * N> qs = qs_equal_keys<2 * N>();
+    NoncontactTables<N> t{};
+    for (int k = 0; k < N; k++) t.motor_at[k] = qs.perm[k] - N;
+    for (int k = 0; k < N; k++) t.rank[t.motor_at[k]] = k;
+    for (int j = 0; j < N; j++) {
+        t.below[j] = 0;
+        for (int o = 0; o < N; o++)
+            if (t.rank[o] < t.rank[j]) t.below[j] |= 1ull << o;
+    }
+    return t;
+}
+template <int N>
+struct NoncontactOrder {
+    static constexpr QsEqualKeys<2 * N> qs = qs_equal_keys<2 * N>();
+    static constexpr NoncontactTables<N> tab = noncontact_tables<N>();
+    // the motor swept at step k of a sweep (forwards: the k-th of the list; backwards: the k-th from its end)
+    static constexpr int motor(bool fwd, int k) { return tab.motor_at[fwd ? k : N - 1 - k]; }
+    static constexpr bool halves_split() {
+        for (int k = 0; k < N; k++)
+            if (qs.perm[k] < N || qs.perm[N + k] != qs.perm[k] - N) return false;
+        return true;
+    }
+};
+static_assert(NoncontactOrder<16>::halves_split() && NoncontactOrder<32>::halves_split(),
+              "noncontact_order 1: the quickSort puts every motor before every limit, both halves in one pattern");
+static_assert(NoncontactOrder<16>::tab.motor_at[0] == 5 && NoncontactOrder<16>::tab.motor_at[1] == 4 &&
+                  NoncontactOrder<16>::tab.motor_at[2] == 7 && NoncontactOrder<16>::tab.motor_at[3] == 6 &&
+                  NoncontactOrder<16>::tab.motor_at[4] == 1 && NoncontactOrder<16>::tab.motor_at[5] == 0 &&
+                  NoncontactOrder<16>::tab.motor_at[6] == 3 && NoncontactOrder<16>::tab.motor_at[7] == 2 &&
+                  NoncontactOrder<16>::tab.motor_at[8] == 13 && NoncontactOrder<16>::tab.motor_at[9] == 12 &&
+                  NoncontactOrder<16>::tab.motor_at[10] == 15 && NoncontactOrder<16>::tab.motor_at[11] == 14 &&
+                  NoncontactOrder<16>::tab.motor_at[12] == 9 && NoncontactOrder<16>::tab.motor_at[13] == 8 &&
+                  NoncontactOrder<16>::tab.motor_at[14] == 11 && NoncontactOrder<16>::tab.motor_at[15] == 10,
+              "DESIGN.md 3: the motors of the 16-link chain in the order 5 4 7 6 1 0 3 2 13 12 15 14 9 8 11 10");
 
 namespace detail {
 inline void rpy(double r, double p, double y, double* R) {
@@ -277,6 +357,13 @@ inline void build_dev_model(const snk_params& P, const HostModel& H, DevModel& D
     D.cone = (P.cone_friction && P.friction_directions == 2) ? 1 : 0;
     D.fricB = P.friction_directions == 1 ? 0.0f : 1.0f;
     D.contact_order = P.contact_order;
+    D.noncontact_order = P.noncontact_order;
+    D.contact_erp_rule = P.contact_erp_rule;
+    // contact_erp_rule 1 [U] (setupMultiBodyContactConstraint as read): m_erp unless split impulse is on and the contact is
+    // deeper than m_splitImpulsePenetrationThreshold (-0.04 m), then m_erp2.  Rule 0: contact_erp at any depth
+    D.erp_deep = (float)P.contact_erp;
+    D.erp_shallow = P.contact_erp_rule ? (float)P.limit_erp : (float)P.contact_erp;
+    D.erp_split = -0.04f;
     {
         // The oracle's rule (oracle/snake_oracle.cpp: find_contacts): 1 = reversed; 2 = link order after Bullet's unstable
         // quickSort on equal keys; k >= 3 = the cylinder links sorted by a splitmix-style hash of (k, link).  `link` is the index of the cylinder's link in the unmerged URDF tree with the
@@ -286,24 +373,12 @@ inline void build_dev_model(const snk_params& P, const HostModel& H, DevModel& D
         // contact_order 2: where btAlignedObjectArray::quickSort (Hoare partition, pivot = the middle element, `i <= j` swap:
         // on all-equal keys every partition reverses its range and recurses into the halves) leaves element c of a list
         // of nc2 equal keys -- the island manager's sort of the plane-link manifolds, restated (oracle: qs_equal_keys)
-        int qs_perm[kMaxCyl], qs_pos[kMaxCyl];
-        for (int c = 0; c < nc2; c++) qs_perm[c] = c;
-        {
-            int stack[2 * kMaxCyl][2], sp = 0;
-            if (nc2 > 1) { stack[sp][0] = 0; stack[sp][1] = nc2 - 1; sp++; }
-            while (sp > 0) {
-                sp--;
-                const int lo = stack[sp][0], hi = stack[sp][1];
-                int i = lo, j = hi;
-                do {
-                    if (i <= j) { const int t = qs_perm[i]; qs_perm[i] = qs_perm[j]; qs_perm[j] = t; i++; j--; }
-                } while (i <= j);
-                // (the two recursive calls work on disjoint ranges: their order does not matter)
-                if (i < hi) { stack[sp][0] = i; stack[sp][1] = hi; sp++; }
-                if (lo < j) { stack[sp][0] = lo; stack[sp][1] = j; sp++; }
-            }
-        }
-        for (int c = 0; c < nc2; c++) qs_pos[qs_perm[c]] = c;
+        // (qs_equal_keys above: one constexpr definition for the host and the kernels; the chain lengths are 16 and 32)
+        int qs_pos[kMaxCyl];
+        const int* qs_perm = n == 16 ? NoncontactOrder<16>::qs.perm : (n == 32 ? NoncontactOrder<32>::qs.perm : nullptr);
+        for (int c = 0; c < nc2; c++) qs_pos[c] = c;                   // (other chain lengths are refused by snk_create)
+        if (qs_perm)
+            for (int c = 0; c < nc2; c++) qs_pos[qs_perm[c]] = c;
         for (int c = 0; c < nc2; c++) {
             const int link = (c & 1) ? 3 * (c + 1) / 2 + 1 : 3 * c / 2 + 2;
             if (P.contact_order == 0) key[c] = (unsigned long long)c;

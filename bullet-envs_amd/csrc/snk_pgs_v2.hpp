@@ -757,7 +757,9 @@ __device__ void build_batch_v2(LT& L, const DevModel& M, int lane, int nc, int b
             target = want - cur;
         } else if (KIND == 1) {
             float pen = L.ccdist[lane] + M.slop;
-            target = -rv + (pen > 0.f ? -pen * M.inv_dt : -pen * M.contact_erp * M.inv_dt);
+            float erp = M.contact_erp;
+            if constexpr (LT::kERP) erp = pen > M.erp_split ? M.erp_shallow : M.erp_deep;     // contact_erp_rule
+            target = -rv + (pen > 0.f ? -pen * M.inv_dt : -pen * erp * M.inv_dt);
         } else {
             target = -rv;
         }
@@ -1272,9 +1274,26 @@ __device__ __forceinline__ void cones8(float (&RJ)[kSlots], float (&RM)[kSlots],
 // the 16 motor rows, forwards or backwards; returns max |dI * den| = max |y| of the sweep
 // (ALIVE: every motor row has a usable denominator -- always, unless a joint has no inertia;
 // otherwise dead rows are masked out of the residual through LDS)
+// NCO = snk_params::noncontact_order: 1 takes the motors in the order of NoncontactOrder<16> (snk_model.hpp), every step
+// with its motor's lane as an immediate and RMm[] indexed by constants only
+template <bool FWD, bool CLAMP, bool ALIVE, int NCO, class LT, int... K>
+__device__ __forceinline__ float motors16_ordered(LT& L, const float (&RMm)[16], float& dv, const float TARGV, float& ACCV,
+                                                  float PMIV, std::integer_sequence<int, K...>) {
+    float res = 0.f;
+    auto step = [&](auto j_c) {
+        constexpr int J = decltype(j_c)::value;
+        float s_ = motor_step<J, CLAMP>(RMm[J], dv, TARGV, ACCV, PMIV);
+        res = fmaxf(res, fabsf(ALIVE ? s_ : s_ * (L.MmS[J][1] * L.MmS[J][2])));
+    };
+    (step(std::integral_constant<int, NoncontactOrder<16>::motor(FWD, K)>{}), ...);
+    return res;
+}
 template <bool FWD, bool CLAMP, bool ALIVE, class LT>
 __device__ __forceinline__ float motors16(LT& L, const float (&RMm)[16], float& dv, const float TARGV, float& ACCV,
                                           float PMIV) {
+    if constexpr (LT::kNCO != 0)
+        return motors16_ordered<FWD, CLAMP, ALIVE, LT::kNCO>(L, RMm, dv, TARGV, ACCV, PMIV,
+                                                             std::make_integer_sequence<int, 16>{});
     float res = 0.f;
 #define SNK_MOTOR(J)                                                                              \
     {                                                                                              \
@@ -1606,7 +1625,10 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
         unsigned long long bal = __ballot(viol);
         nlim = __builtin_amdgcn_readfirstlane(__popcll(bal));
         if (viol) {
-            int idx = __popcll(bal & ((1ull << lane) - 1ull));
+            // noncontact_order 1: the violated limits in the quickSort's joint order, not by joint index
+            unsigned long long before = (1ull << lane) - 1ull;
+            if constexpr (LT::kNCO != 0) before = NoncontactOrder<N>::tab.below[lane];
+            int idx = __popcll(bal & before);
             float den = L.Mm[lane][6 + lane];
             float dinv = den > 1.1920929e-7f ? 1.0f / den : 0.f;
             float rel = sgn * L.qd()[lane];
@@ -1686,7 +1708,7 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
                     if (__builtin_amdgcn_readfirstlane(fabsf(dI * L.nc_den[idx]) > thr ? 1 : 0)) exceeded = 1;
                 }
             };
-            // non-contact rows: list = [limits..., motors 0..15], walked forwards on odd
+            // non-contact rows: list = [limits..., motors 0..15] (noncontact_order 1: [motors, limits] in NoncontactOrder<16>), walked forwards on odd
             // iterations and backwards on even ones.  The motors' residual is always tracked
             // (one v_max per row); it decides which body runs for the ~190 contact rows.
             float mres;
@@ -1702,12 +1724,22 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
                             : motors16<FWD, false, true>(L, RMm, dv, TARGV, ACCV, 0.f))              \
                   : (mclamp ? motors16<FWD, true, false>(L, RMm, dv, TARGV, ACCV, pmiv())            \
                             : motors16<FWD, false, false>(L, RMm, dv, TARGV, ACCV, 0.f));
-            if (it & 1) {
-                limit_rows(true);
-                SNK_MOTORS(true)
-            } else {
-                SNK_MOTORS(false)
-                limit_rows(false);
+            if constexpr (LT::kNCO == 0) {        // list = [limits..., motors...]
+                if (it & 1) {
+                    limit_rows(true);
+                    SNK_MOTORS(true)
+                } else {
+                    SNK_MOTORS(false)
+                    limit_rows(false);
+                }
+            } else {                              // noncontact_order 1: list = [motors..., limits...]
+                if (it & 1) {
+                    SNK_MOTORS(true)
+                    limit_rows(true);
+                } else {
+                    limit_rows(false);
+                    SNK_MOTORS(false)
+                }
             }
 #undef SNK_MOTORS
             if (__builtin_amdgcn_readfirstlane(mres > thr ? 1 : 0)) exceeded = 1;

@@ -22,7 +22,7 @@ extern "C" {
 
 /* Every knob the reference path depends on.  [U] = PyBullet/Bullet default taken from
  * knowledge of bullet3 (not verifiable here). */
-#define SNK_ABI_VERSION 6       /* bumped whenever snk_params' layout or an entry point's meaning changes */
+#define SNK_ABI_VERSION 7       /* bumped whenever snk_params' layout or an entry point's meaning changes */
 
 typedef struct snk_params {
     /* layout guard (round 6): snk_default_params fills both, snk_create refuses a struct whose size or
@@ -127,6 +127,19 @@ typedef struct snk_params {
                                    order).  A
                                    cylinder's <= 4 points stay together and in their own order.  Needs contact_model 1 */
     int32_t reserved0;          /* 0 */
+    /* (appended with ABI 7: two solver rules that the oracle alone had before) */
+    int32_t noncontact_order;   /* 0 (default): the violated joint limits by joint index, then the n motors by joint index.
+                                   1: the order btMultiBodyDynamicsWorld::solveConstraints is read to hand its solver [U] --
+                                   the world's list [limit_1..limit_n, motor_1..motor_n] after btAlignedObjectArray::quickSort
+                                   on equal island ids, which is not stable: its first partition reverses the list, so the n
+                                   motors come first, then the violated limits, both in one fixed non-identity pattern
+                                   (snk_debug_noncontact_order).  The oracle prices it at +0.3 % of forward motion under the
+                                   bench gait, -23.4 % together with contact_order 2 (profiles/r06_u_rows.json)        */
+    int32_t contact_erp_rule;   /* 0 (default): a penetrating contact row takes contact_erp (m_erp2, 0.08) at any depth.
+                                   1: the choice setupMultiBodyContactConstraint is read to make [U]: limit_erp (m_erp, 0.2)
+                                   unless split impulse is on and the contact is deeper than
+                                   m_splitImpulsePenetrationThreshold (-0.04 m), only then contact_erp.  Ground, link-link
+                                   and box contacts alike.  The oracle prices it at -0.5 % of forward motion             */
 } snk_params;
 
 typedef struct snk_handle snk_handle;
@@ -271,6 +284,12 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */
 int snk_debug_raise_alarm(snk_handle* h);
+
+/* Test hook (host only, no handle): the 2 n-entry sweep order the kernels are compiled with for noncontact_order 1 and
+ * n_modules n (16 or 32), in the oracle's convention (orc_quicksort_equal_keys over 2 n): out[k] = the row at place k of
+ * the forward sweep, entries 0..n-1 naming limit j, entries n..2n-1 motor j - n.  Read from the same constexpr table
+ * the kernels unroll their sweeps over. */
+int snk_debug_noncontact_order(int32_t n_modules, int32_t* out);
 
 /* Device-side self test of the wave primitives (DPP reductions); 0 = pass. */
 int snk_selftest(int32_t device);

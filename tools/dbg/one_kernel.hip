@@ -1,4 +1,5 @@
 // One instantiation of the step kernel by itself (tools/dbg/loop_spills.sh): -DKN=16 -DKV=true | -DKN=16 -DKV=false | -DKN=32 -DKV=false
+// (-DKR=1 | 2: a solver-rules variant, snk_device.hpp: LdsFor)
 #include <hip/hip_runtime.h>
 #include "../../include/snk.h"
 #include "../../bullet-envs_amd/csrc/snk_device.hpp"
@@ -6,4 +7,7 @@
 #define KN 16
 #define KV true
 #endif
-template __global__ void snk::env_step_sched_kernel<KN, KV>(snk::StepArgs);
+#ifndef KR
+#define KR 0
+#endif
+template __global__ void snk::env_step_sched_kernel<KN, KV, KR>(snk::StepArgs);
