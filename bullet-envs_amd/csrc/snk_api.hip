@@ -71,65 +71,62 @@ struct snk_handle {
 
 namespace {
 
+// The kernel variant of a handle: chain length, solve (V2: register-resident) and solver-rules variant (snk_device.hpp:
+// LdsFor, rules_variant), as compile-time constants.  Instantiated for 16 links with the register-resident solve, 16 and
+// 32 links with the streamed-row solve (32: always; 16: when the world holds an obstacle, whose contacts need it).
+template <int N_, bool V2_, int RULES_>
+struct Variant {
+    static constexpr int N = N_;
+    static constexpr bool V2 = V2_;
+    static constexpr int RULES = RULES_;
+};
+template <int N, bool V2, class F>
+int with_rules(int rules, F& fn) {
+    return rules == 2 ? fn(Variant<N, V2, 2>{}) : (rules == 1 ? fn(Variant<N, V2, 1>{}) : fn(Variant<N, V2, 0>{}));
+}
+// fn(Variant<...>{}) for h's variant.  (Only the solving kernels take RULES: the reset and obs kernels of the three
+// variants of one (N, V2) are one instantiation.)
+template <class F>
+int dispatch(const snk_handle* h, F&& fn) {
+    const int rules = snk::rules_variant(h->D);
+    if (h->n == 16) return h->v2 ? with_rules<16, true>(rules, fn) : with_rules<16, false>(rules, fn);
+    if (h->n == 32) return with_rules<32, false>(rules, fn);
+    return fail("unsupported n_modules (16 or 32)");
+}
+
 // packed_stride > 0 (snk_step_packed): obs rows of that stride, reward and done flag behind each row's observation.
-// RULES: the solver-rules variant the solving kernels are instantiated for (snk_device.hpp: LdsFor, rules_variant)
-template <int N, bool V2, int RULES>
-int launch_step_o(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode,
-                hipStream_t st, int packed_stride = 0) {
-    const int stride = packed_stride > 0 ? packed_stride : h->D.obs_dim;
-    const int packed = packed_stride > 0 ? 1 : 0;
+template <class K>
+int launch_step(K, snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode,
+                hipStream_t st, int packed_stride) {
+    snk::StepArgs a;
+    a.recs = h->d_recs; a.mu_plane = h->d_mu; a.actions = act; a.obs = obs; a.rew = rew; a.done = done; a.substeps = sub;
+    a.rows_all = h->d_rows; a.mf_all = h->d_mf; a.ovf = h->d_ovf; a.box_all = h->d_box; a.sc = h->sched;
+    a.model_slot = h->model_slot; a.vec_mode = vec_mode; a.n_envs = h->n_envs;
+    a.obs_stride = packed_stride > 0 ? packed_stride : h->D.obs_dim; a.packed = packed_stride > 0 ? 1 : 0; a.pad_ = 0;
+    a.model = h->d_model; a.order = h->plan ? h->d_order : nullptr;
     if (h->use_sched) {
-        hipLaunchKernelGGL((snk::plan_sched_kernel<N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->sched,
+        hipLaunchKernelGGL((snk::plan_sched_kernel<K::N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->sched,
                            h->n_envs);
-        snk::StepArgs a;
-        a.recs = h->d_recs; a.mu_plane = h->d_mu; a.actions = act; a.obs = obs; a.rew = rew; a.done = done; a.substeps = sub;
-        a.rows_all = h->d_rows; a.mf_all = h->d_mf; a.ovf = h->d_ovf; a.box_all = h->d_box; a.sc = h->sched;
-        a.model_slot = h->model_slot; a.vec_mode = vec_mode; a.n_envs = h->n_envs;
-        a.obs_stride = stride; a.packed = packed; a.pad_ = 0;
-        hipLaunchKernelGGL((snk::env_step_sched_kernel<N, V2, RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, a);
+        hipLaunchKernelGGL((snk::env_step_sched_kernel<K::N, K::V2, K::RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes,
+                           st, a);
         return 0;
     }
     if (h->plan)
-        hipLaunchKernelGGL((snk::plan_kernel<N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->d_order,
+        hipLaunchKernelGGL((snk::plan_kernel<K::N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->d_order,
                            h->n_envs);
-    hipLaunchKernelGGL((snk::env_step_kernel<N, V2, RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, h->d_model, h->d_recs,
-                       h->d_mu, act, obs, rew, done, sub, vec_mode, h->n_envs, h->plan ? h->d_order : nullptr, h->d_rows, h->d_mf, h->d_ovf, h->d_box,
-                       stride, packed);
+    hipLaunchKernelGGL((snk::env_step_kernel<K::N, K::V2, K::RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, a);
     return 0;
 }
-template <int N, bool V2>
-int launch_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode,
-                hipStream_t st, int packed_stride = 0) {
-    switch (snk::rules_variant(h->D)) {
-    case 2: return launch_step_o<N, V2, 2>(h, act, obs, rew, done, sub, vec_mode, st, packed_stride);
-    case 1: return launch_step_o<N, V2, 1>(h, act, obs, rew, done, sub, vec_mode, st, packed_stride);
-    default: return launch_step_o<N, V2, 0>(h, act, obs, rew, done, sub, vec_mode, st, packed_stride);
-    }
-}
-template <int N, bool V2, int RULES>
-int launch_substep_o(snk_handle* h, const float* tgt, int k, int32_t* info, hipStream_t st) {
-    hipLaunchKernelGGL((snk::substep_kernel<N, V2, RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, h->d_model, h->d_recs,
-                       h->d_mu, tgt, k, info, h->n_envs, h->d_rows, h->d_mf, h->d_ovf, h->d_box);
+template <class K>
+int launch_substep(K, snk_handle* h, const float* tgt, int k, int32_t* info, hipStream_t st) {
+    hipLaunchKernelGGL((snk::substep_kernel<K::N, K::V2, K::RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st,
+                       h->d_model, h->d_recs, h->d_mu, tgt, k, info, h->n_envs, h->d_rows, h->d_mf, h->d_ovf, h->d_box);
     return 0;
 }
-template <int N, bool V2>
-int launch_substep(snk_handle* h, const float* tgt, int k, int32_t* info, hipStream_t st) {
-    switch (snk::rules_variant(h->D)) {
-    case 2: return launch_substep_o<N, V2, 2>(h, tgt, k, info, st);
-    case 1: return launch_substep_o<N, V2, 1>(h, tgt, k, info, st);
-    default: return launch_substep_o<N, V2, 0>(h, tgt, k, info, st);
-    }
-}
-template <int N, bool V2>
-int launch_reset(snk_handle* h, const uint8_t* mask, float* obs, int hard, hipStream_t st) {
-    hipLaunchKernelGGL((snk::reset_kernel<N, V2>), dim3(h->n_envs), dim3(64), h->lds_bytes, st, h->d_recs, mask, obs, hard,
-                       h->n_envs);
-    return 0;
-}
-template <int N, bool V2>
-int launch_obs(snk_handle* h, float* obs, float* height, hipStream_t st, float* linkpos) {
-    hipLaunchKernelGGL((snk::obs_kernel<N, V2>), dim3(h->n_envs), dim3(64), h->lds_bytes, st, h->d_model, h->d_recs, obs,
-                       height, linkpos, h->n_envs);
+template <class K>
+int launch_reset(K, snk_handle* h, const uint8_t* mask, float* obs, int hard, hipStream_t st) {
+    hipLaunchKernelGGL((snk::reset_kernel<K::N, K::V2>), dim3(h->n_envs), dim3(64), h->lds_bytes, st, h->d_recs, mask, obs,
+                       hard, h->n_envs);
     return 0;
 }
 // Waves of the step kernel a CU holds: __launch_bounds__(64, 2) = 2 per SIMD, 4 SIMDs, and the CU's LDS (160 KB on
@@ -150,35 +147,17 @@ int resident_waves(size_t bytes, int device, int* out) {
     *out = per_cu * prop.multiProcessorCount;
     return 0;
 }
-template <int N, bool V2, int RULES>
-int set_lds_attr_rules(size_t bytes) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::env_step_kernel<N, V2, RULES>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::env_step_sched_kernel<N, V2, RULES>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::substep_kernel<N, V2, RULES>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+// (every solver-rules variant has the same LDS image: the rules are compile-time constants only)
+template <class K>
+int set_lds_attr(K, size_t bytes) {
+    const void* kernels[] = {reinterpret_cast<const void*>(&snk::env_step_kernel<K::N, K::V2, K::RULES>),
+                             reinterpret_cast<const void*>(&snk::env_step_sched_kernel<K::N, K::V2, K::RULES>),
+                             reinterpret_cast<const void*>(&snk::substep_kernel<K::N, K::V2, K::RULES>),
+                             reinterpret_cast<const void*>(&snk::reset_kernel<K::N, K::V2>),
+                             reinterpret_cast<const void*>(&snk::obs_kernel<K::N, K::V2>)};
+    for (const void* f : kernels) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return 0;
 }
-template <int N, bool V2>
-int set_lds_attr(size_t bytes, int rules) {
-    // (every solver-rules variant has the same LDS image: the rules are compile-time constants only)
-    const int rc = rules == 2 ? set_lds_attr_rules<N, V2, 2>(bytes)
-                              : (rules == 1 ? set_lds_attr_rules<N, V2, 1>(bytes) : set_lds_attr_rules<N, V2, 0>(bytes));
-    if (rc) return rc;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::reset_kernel<N, V2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&snk::obs_kernel<N, V2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
-
-// Kernels are instantiated for the chain lengths the BASELINE configs use.
-// (chain length, solve) pairs the kernels are instantiated for: 16 links with the register-resident solve, 16 and 32
-// links with the streamed-row solve (32: always; 16: when the world holds an obstacle, whose contacts need it)
-#define SNK_DISPATCH(h, FN, ...)                                                                            \
-    ((h)->n == 16 ? ((h)->v2 ? FN<16, true>(__VA_ARGS__) : FN<16, false>(__VA_ARGS__))                      \
-                  : ((h)->n == 32 ? FN<32, false>(__VA_ARGS__) : fail("unsupported n_modules (16 or 32)")))
 
 // slots of snk::g_models, shared by the handles of this process
 std::mutex g_slot_mutex;
@@ -216,6 +195,60 @@ int check_launch() {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
     return 0;
+}
+
+// the launch of snk_step / snk_step_packed, between a pair of snk_timing_enable's events while the pool has one left
+int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode, hipStream_t st,
+               int packed_stride) {
+    HIP_TRY(hipSetDevice(h->device));
+    const bool timed = 2 * h->ev_used + 1 < (int)h->ev.size();
+    if (timed) HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used], st));
+    const int rc = dispatch(h, [&](auto k) { return launch_step(k, h, act, obs, rew, done, sub, vec_mode, st, packed_stride); });
+    if (rc) return rc;
+    if (timed) {
+        HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used + 1], st));
+        h->ev_used++;
+    }
+    return check_launch();
+}
+
+// one obs_kernel pass over h's records (the device idle, the handle alive), and its one output copied to out
+int obs_pass(snk_handle* h, float* obs, float* height, float* linkpos, void* out, size_t bytes) {
+    const int rc = dispatch(h, [&](auto k) {
+        hipLaunchKernelGGL((snk::obs_kernel<decltype(k)::N, decltype(k)::V2>), dim3(h->n_envs), dim3(64), h->lds_bytes,
+                           nullptr, h->d_model, h->d_recs, obs, height, linkpos, h->n_envs);
+        return 0;
+    });
+    if (rc || check_launch()) return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, obs ? obs : (height ? height : linkpos), bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// A contact manifold on the host (the oracle's layout): [count, 4 x (point on the link in link coordinates 3, point on
+// the ground 3, applied normal impulse)] = 29 floats.  On the device: a count, and 4 x (a3, b.x, b.y, lambda) at `pts`
+// (the ground point's z is the plane's, 0).  Slots past the count hold stale points: reported as zeros.
+void manifold_to_host(float count, const float* pts, float* o) {
+    const int n = count < 0.f ? 0 : (count > 4.f ? 4 : (int)count);
+    o[0] = (float)n;
+    for (int j = 0; j < 4; j++) {
+        const bool on = j < n;
+        for (int r = 0; r < 3; r++) o[1 + 7 * j + r] = on ? pts[6 * j + r] : 0.f;
+        o[4 + 7 * j] = on ? pts[3 + 6 * j] : 0.f;
+        o[5 + 7 * j] = on ? pts[4 + 6 * j] : 0.f;
+        o[6 + 7 * j] = 0.f;
+        o[7 + 7 * j] = on ? pts[5 + 6 * j] : 0.f;
+    }
+}
+// the reverse: fills pts, returns the count (a manifold holds 0 .. 4 points, whatever the caller says)
+float manifold_from_host(const float* o, float* pts) {
+    for (int j = 0; j < 4; j++) {
+        for (int r = 0; r < 3; r++) pts[6 * j + r] = o[1 + 7 * j + r];
+        pts[3 + 6 * j] = o[4 + 7 * j];
+        pts[4 + 6 * j] = o[5 + 7 * j];
+        pts[5 + 6 * j] = o[7 + 7 * j];
+    }
+    return o[0] >= 0.f ? (o[0] <= 4.f ? floorf(o[0]) : 4.f) : 0.f;
 }
 
 }  // namespace
@@ -303,8 +336,13 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     // SNK_FORCE_STREAMED=1 (diagnostics, tests): the streamed-row kernels for a 16-link handle too
     h->v2 = h->n == 16 && getenv("SNK_FORCE_STREAMED") == nullptr && p->obstacle != 2;      // (a free box: six more
                                                                                             //  components, streamed rows)
-    h->lds_bytes = h->n == 16 ? (h->v2 ? sizeof(snk::Lds<16, true>) : sizeof(snk::Lds<16, false>)) : sizeof(snk::Lds<32, false>);
-    int rc = SNK_DISPATCH(h, set_lds_attr, h->lds_bytes, snk::rules_variant(h->D));
+    size_t rf = 0, z0 = 0, zn = 0, m0 = 0, m1 = 0;      // the layout of a block of streamed constraint rows (below)
+    int rc = dispatch(h, [&](auto k) {
+        using LR = snk::Lds<decltype(k)::N, false>;
+        h->lds_bytes = sizeof(snk::Lds<decltype(k)::N, decltype(k)::V2>);
+        rf = LR::kRowFloats; z0 = (size_t)(LR::kRows - 3) * LR::kRS; zn = 3 * (size_t)LR::kRS; m0 = LR::kMmOff; m1 = LR::kYOff;
+        return set_lds_attr(k, h->lds_bytes);
+    });
     if (rc) return rc;
     const size_t ne = (size_t)n_envs;
     HIP_TRY(hipMalloc(&h->d_model, sizeof(snk::DevModel)));
@@ -341,18 +379,12 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
         //  goes through the streamed-row solve in place, snk_device.hpp: substep())
         // one block of streamed constraint rows per RESIDENT WAVE (every step / substep kernel is launched with that many
         // workgroups and strides over the environments): 2048 x 112 KB = 230 MB for 32 links, whatever n_envs is
-        const size_t rf = h->n == 32 ? snk::Lds<32, false>::kRowFloats : snk::Lds<16, false>::kRowFloats;
         const size_t nb = (size_t)h->grid_waves;
         const size_t bytes = nb * rf * sizeof(float);
         HIP_TRY(hipMalloc(&h->d_rows, bytes));
         HIP_TRY(hipMemset(h->d_rows, poison ? 0xFF : 0, bytes));
         // what the kernels rely on being zero for good: the last three rows of every block (the refill of a skipped
         // friction pair) and the pad columns of the M^-1 block behind the rows
-        const size_t z0 = h->n == 32 ? (size_t)(snk::Lds<32, false>::kRows - 3) * snk::Lds<32, false>::kRS
-                                     : (size_t)(snk::Lds<16, false>::kRows - 3) * snk::Lds<16, false>::kRS;
-        const size_t zn = 3 * (size_t)(h->n == 32 ? snk::Lds<32, false>::kRS : snk::Lds<16, false>::kRS);
-        const size_t m0 = h->n == 32 ? snk::Lds<32, false>::kMmOff : snk::Lds<16, false>::kMmOff;
-        const size_t m1 = h->n == 32 ? snk::Lds<32, false>::kYOff : snk::Lds<16, false>::kYOff;
         if (poison)
             for (size_t e = 0; e < nb; e++) {
                 HIP_TRY(hipMemsetAsync(h->d_rows + e * rf + z0, 0, zn * sizeof(float), nullptr));
@@ -416,8 +448,8 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
 #endif
     }
     // hard reset (snake.py:88-95)
-    SNK_DISPATCH(h, launch_reset, h, nullptr, nullptr, 1, nullptr);
-    if (check_launch()) return 1;
+    rc = dispatch(h, [&](auto k) { return launch_reset(k, h, nullptr, nullptr, 1, nullptr); });
+    if (rc || check_launch()) return 1;
     HIP_TRY(hipDeviceSynchronize());
     return 0;
 }
@@ -507,7 +539,7 @@ int snk_reset(snk_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stre
     if (check_alarm(h)) return 1;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    SNK_DISPATCH(h, launch_reset, h, mask_dev, obs_dev, 0, st);
+    if (dispatch(h, [&](auto k) { return launch_reset(k, h, mask_dev, obs_dev, 0, st); })) return 1;
     return check_launch();
 }
 
@@ -516,16 +548,7 @@ int snk_step(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev, 
     if (!h) return fail("snk_step: null handle");
     if (!actions_dev || !obs_dev || !rew_dev || !done_dev) return fail("snk_step: null buffer");
     if (check_alarm(h)) return 1;
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool timed = 2 * h->ev_used + 1 < (int)h->ev.size();
-    if (timed) HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used], st));
-    SNK_DISPATCH(h, launch_step, h, actions_dev, obs_dev, rew_dev, done_dev, substeps_dev, vec_mode, st);
-    if (timed) {
-        HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used + 1], st));
-        h->ev_used++;
-    }
-    return check_launch();
+    return timed_step(h, actions_dev, obs_dev, rew_dev, done_dev, substeps_dev, vec_mode, (hipStream_t)stream, 0);
 }
 
 int snk_step_packed(snk_handle* h, float* actions_dev, float* packed_dev, int32_t row_stride, int32_t* substeps_dev,
@@ -534,16 +557,7 @@ int snk_step_packed(snk_handle* h, float* actions_dev, float* packed_dev, int32_
     if (!actions_dev || !packed_dev) return fail("snk_step_packed: null buffer");
     if (row_stride < h->D.obs_dim + 2) return fail("snk_step_packed: row_stride must be at least obs_dim + 2");
     if (check_alarm(h)) return 1;
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool timed = 2 * h->ev_used + 1 < (int)h->ev.size();
-    if (timed) HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used], st));
-    SNK_DISPATCH(h, launch_step, h, actions_dev, packed_dev, nullptr, nullptr, substeps_dev, vec_mode, st, row_stride);
-    if (timed) {
-        HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used + 1], st));
-        h->ev_used++;
-    }
-    return check_launch();
+    return timed_step(h, actions_dev, packed_dev, nullptr, nullptr, substeps_dev, vec_mode, (hipStream_t)stream, row_stride);
 }
 
 int snk_timing_enable(snk_handle* h, int32_t capacity) {
@@ -614,8 +628,7 @@ int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* in
     HIP_TRY(hipSetDevice(h->device));
     const size_t ne = (size_t)h->n_envs;
     HIP_TRY(hipMemcpy(h->d_tgt, targets, ne * h->n * sizeof(float), hipMemcpyHostToDevice));
-    SNK_DISPATCH(h, launch_substep, h, h->d_tgt, k, h->d_info, nullptr);
-    if (check_launch()) return 1;
+    if (dispatch(h, [&](auto v) { return launch_substep(v, h, h->d_tgt, k, h->d_info, nullptr); }) || check_launch()) return 1;
     HIP_TRY(hipDeviceSynchronize());
     if (info) HIP_TRY(hipMemcpy(info, h->d_info, ne * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return 0;
@@ -652,9 +665,7 @@ int snk_set_state(snk_handle* h, const float* state, const float* aux) {
 
 int32_t snk_manifold_floats(const snk_handle* h) { return (h && h->d_mf) ? 2 * h->n * 29 : 0; }
 
-// host layout per cylinder (same as the oracle's): [count, 4 x (point on the link in link coordinates 3, point on the
-// ground 3, applied normal impulse)] = 29 floats; device layout: [count, 3 pad, 4 x (a3, b.x, b.y, lambda)] = kMfFloats
-// (the ground point's z is the plane's, 0)
+// per cylinder: host layout manifold_to_host's; device layout [count, 3 pad, 4 x (a3, b.x, b.y, lambda)] = kMfFloats
 int snk_get_manifold(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_get_manifold: null argument");
     if (!h->d_mf) return fail("snk_get_manifold: this handle has contact_model 0 (no contact cache)");
@@ -662,20 +673,7 @@ int snk_get_manifold(snk_handle* h, float* out) {
     const size_t ncyl = (size_t)h->n_envs * 2 * h->n;
     std::vector<float> dev(ncyl * snk::kMfFloats);
     HIP_TRY(hipMemcpy(dev.data(), h->d_mf, dev.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < ncyl; c++) {
-        const float* d = &dev[snk::kMfFloats * c];
-        float* o = out + 29 * c;
-        const int n = d[0] < 0.f ? 0 : (d[0] > 4.f ? 4 : (int)d[0]);
-        o[0] = (float)n;
-        for (int j = 0; j < 4; j++) {
-            const bool on = j < n;       // slots past the count hold stale points: reported as zeros
-            for (int r = 0; r < 3; r++) o[1 + 7 * j + r] = on ? d[4 + 6 * j + r] : 0.f;
-            o[4 + 7 * j] = on ? d[7 + 6 * j] : 0.f;
-            o[5 + 7 * j] = on ? d[8 + 6 * j] : 0.f;
-            o[6 + 7 * j] = 0.f;
-            o[7 + 7 * j] = on ? d[9 + 6 * j] : 0.f;
-        }
-    }
+    for (size_t c = 0; c < ncyl; c++) manifold_to_host(dev[snk::kMfFloats * c], &dev[snk::kMfFloats * c + 4], out + 29 * c);
     return 0;
 }
 int snk_set_manifold(snk_handle* h, const float* in) {
@@ -684,17 +682,7 @@ int snk_set_manifold(snk_handle* h, const float* in) {
     SNK_SYNC_ALIVE(h);
     const size_t ncyl = (size_t)h->n_envs * 2 * h->n;
     std::vector<float> dev(ncyl * snk::kMfFloats, 0.f);
-    for (size_t c = 0; c < ncyl; c++) {
-        float* d = &dev[snk::kMfFloats * c];
-        const float* o = in + 29 * c;
-        d[0] = o[0] >= 0.f ? (o[0] <= 4.f ? floorf(o[0]) : 4.f) : 0.f;      // a manifold holds 0 .. 4 points, whatever the caller says
-        for (int j = 0; j < 4; j++) {
-            for (int r = 0; r < 3; r++) d[4 + 6 * j + r] = o[1 + 7 * j + r];
-            d[7 + 6 * j] = o[4 + 7 * j];
-            d[8 + 6 * j] = o[5 + 7 * j];
-            d[9 + 6 * j] = o[7 + 7 * j];
-        }
-    }
+    for (size_t c = 0; c < ncyl; c++) dev[snk::kMfFloats * c] = manifold_from_host(in + 29 * c, &dev[snk::kMfFloats * c + 4]);
     HIP_TRY(hipMemcpy(h->d_mf, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
@@ -708,19 +696,7 @@ int snk_get_box(snk_handle* h, float* state, float* manifold) {
     for (size_t e = 0; e < (size_t)h->n_envs; e++) {
         const float* x = &b[e * snk::kBoxFloats];
         if (state) memcpy(state + 13 * e, x, 13 * sizeof(float));
-        if (manifold) {
-            float* o = manifold + 29 * e;
-            const int n = x[13] < 0.f ? 0 : (x[13] > 4.f ? 4 : (int)x[13]);
-            o[0] = (float)n;
-            for (int j = 0; j < 4; j++) {
-                const bool on = j < n;
-                for (int r = 0; r < 3; r++) o[1 + 7 * j + r] = on ? x[14 + 6 * j + r] : 0.f;
-                o[4 + 7 * j] = on ? x[17 + 6 * j] : 0.f;
-                o[5 + 7 * j] = on ? x[18 + 6 * j] : 0.f;
-                o[6 + 7 * j] = 0.f;
-                o[7 + 7 * j] = on ? x[19 + 6 * j] : 0.f;
-            }
-        }
+        if (manifold) manifold_to_host(x[13], x + 14, manifold + 29 * e);      // (state 13, count, points)
     }
     return 0;
 }
@@ -733,16 +709,7 @@ int snk_set_box(snk_handle* h, const float* state, const float* manifold) {
     for (size_t e = 0; e < (size_t)h->n_envs; e++) {
         float* x = &b[e * snk::kBoxFloats];
         if (state) memcpy(x, state + 13 * e, 13 * sizeof(float));
-        if (manifold) {
-            const float* o = manifold + 29 * e;
-            x[13] = o[0] >= 0.f ? (o[0] <= 4.f ? floorf(o[0]) : 4.f) : 0.f;      // 0 .. 4 cached points
-            for (int j = 0; j < 4; j++) {
-                for (int r = 0; r < 3; r++) x[14 + 6 * j + r] = o[1 + 7 * j + r];
-                x[17 + 6 * j] = o[4 + 7 * j];
-                x[18 + 6 * j] = o[5 + 7 * j];
-                x[19 + 6 * j] = o[7 + 7 * j];
-            }
-        }
+        if (manifold) x[13] = manifold_from_host(manifold + 29 * e, x + 14);
     }
     HIP_TRY(hipMemcpy(h->d_box, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
     return 0;
@@ -784,21 +751,13 @@ int snk_contact_histogram(snk_handle* h, uint64_t* out, int32_t reset) {
 int snk_get_obs(snk_handle* h, float* obs) {
     if (!h || !obs) return fail("snk_get_obs: null argument");
     SNK_SYNC_ALIVE(h);
-    SNK_DISPATCH(h, launch_obs, h, h->d_obs, nullptr, nullptr, nullptr);
-    if (check_launch()) return 1;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(obs, h->d_obs, (size_t)h->n_envs * h->D.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return obs_pass(h, h->d_obs, nullptr, nullptr, obs, (size_t)h->n_envs * h->D.obs_dim * sizeof(float));
 }
 
 int snk_mean_height(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_mean_height: null argument");
     SNK_SYNC_ALIVE(h);
-    SNK_DISPATCH(h, launch_obs, h, nullptr, h->d_h, nullptr, nullptr);
-    if (check_launch()) return 1;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, h->d_h, (size_t)h->n_envs * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return obs_pass(h, nullptr, h->d_h, nullptr, out, (size_t)h->n_envs * sizeof(float));
 }
 
 int snk_link_positions(snk_handle* h, float* out) {
@@ -806,11 +765,7 @@ int snk_link_positions(snk_handle* h, float* out) {
     SNK_SYNC_ALIVE(h);
     const size_t bytes = (size_t)h->n_envs * 3 * (h->n + 1) * sizeof(float);
     if (!h->d_linkpos) HIP_TRY(hipMalloc(&h->d_linkpos, bytes));
-    SNK_DISPATCH(h, launch_obs, h, nullptr, nullptr, nullptr, h->d_linkpos);
-    if (check_launch()) return 1;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, h->d_linkpos, bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return obs_pass(h, nullptr, nullptr, h->d_linkpos, out, bytes);
 }
 
 int snk_set_ground_friction(snk_handle* h, const float* mu) {

@@ -1953,30 +1953,26 @@ __device__ __forceinline__ void substep(LT& L, const DevModel& M0, int lane_in, 
 // ----------------------------------------------------------------------------------
 template <class LT>
 __device__ __forceinline__ void load_rec(LT& L, const float* __restrict__ rec, int lane) {
-    constexpr int N = LT::kN;
     lane = launder_lane(lane);
     for (int i = lane; i < LT::REC; i += 64) L.rec[i] = rec[i];
     lds_sync();
 }
-template <class LT>
-__device__ __forceinline__ void store_rec(LT& L, float* __restrict__ rec, int lane) {
-    constexpr int N = LT::kN;
-    lane = launder_lane(lane);
-    lds_sync();
-    for (int i = lane; i < LT::REC; i += 64) rec[i] = L.rec[i];
-}
-// The same store, write-through (sc1): the record leaves this XCD's L2 for memory at once, so a wave on another
+// THROUGH: the same store, write-through (sc1): the record leaves this XCD's L2 for memory at once, so a wave on another
 // XCD can take the env-step over after an agent-scope acquire without this wave writing its whole L2 back
 // (MI355X_MICROARCH.md, inter-workgroup visibility: every handed-off byte stored sc1 and drained with
 // s_waitcnt vmcnt(0) before the flag needs no agent release).  One 16-byte store per lane.
-template <class LT>
-__device__ __forceinline__ void store_rec_through(LT& L, float* __restrict__ rec, int lane) {
+template <class LT, bool THROUGH = false>
+__device__ __forceinline__ void store_rec(LT& L, float* __restrict__ rec, int lane) {
     typedef float v4f __attribute__((ext_vector_type(4)));
     lane = launder_lane(lane);
     lds_sync();
-    if (lane < LT::REC / 4) {
-        const v4f v = reinterpret_cast<const v4f*>(L.rec)[lane];
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(rec + 4 * lane), "v"(v) : "memory");
+    if constexpr (THROUGH) {
+        if (lane < LT::REC / 4) {
+            const v4f v = reinterpret_cast<const v4f*>(L.rec)[lane];
+            asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(rec + 4 * lane), "v"(v) : "memory");
+        }
+    } else {
+        for (int i = lane; i < LT::REC; i += 64) rec[i] = L.rec[i];
     }
 }
 // The register-resident kernels keep an environment's contact manifolds (contact_model 1) in LDS while a wave holds
@@ -2081,6 +2077,36 @@ __device__ __forceinline__ void store_box(LT& L, float* __restrict__ bx, int lan
         }
     }
 }
+// the workgroup's block of streamed constraint rows (one per resident wave): the streamed-row solve's, and behind the
+// register-resident one, for the substeps whose contacts outgrow its slots (substep())
+template <int N>
+__device__ __forceinline__ float* rows_of(float* __restrict__ rows_all) {
+    return rows_all + (size_t)blockIdx.x * Lds<N, false>::kRowFloats;
+}
+// env's block of the contact caches (null under contact_model 0) and of the free boxes (null without obstacle 2)
+template <int N>
+__device__ __forceinline__ float* cache_of(float* __restrict__ mf_all, int env) {
+    return mf_all ? mf_all + (size_t)env * (2 * N * kMfFloats) : nullptr;
+}
+__device__ __forceinline__ float* box_of(float* __restrict__ box_all, int env) {
+    return box_all ? box_all + (size_t)env * kBoxFloats : nullptr;
+}
+// everything of env that a wave holds in LDS while it runs the env: record, contact cache, free box.  THROUGH: stored
+// write-through, for a hand-off to a wave on another XCD (store_rec)
+template <class LT>
+__device__ __forceinline__ void load_env(LT& L, const float* __restrict__ recs, float* __restrict__ mf_all,
+                                         float* __restrict__ box_all, int env, int lane) {
+    load_rec(L, recs + (size_t)env * LT::REC, lane);
+    load_mf(L, cache_of<LT::kN>(mf_all, env), lane);
+    load_box(L, box_of(box_all, env), lane);
+}
+template <class LT, bool THROUGH>
+__device__ __forceinline__ void store_env(LT& L, float* __restrict__ recs, float* __restrict__ mf_all,
+                                          float* __restrict__ box_all, int env, int lane) {
+    store_rec<LT, THROUGH>(L, recs + (size_t)env * LT::REC, lane);
+    store_mf<LT, THROUGH>(L, cache_of<LT::kN>(mf_all, env), lane);
+    store_box<LT, THROUGH>(L, box_of(box_all, env), lane);
+}
 template <class LT>
 __device__ __forceinline__ void write_obs(LT& L, float* __restrict__ obs, int lane) {
     constexpr int N = LT::kN;
@@ -2106,108 +2132,6 @@ __device__ __forceinline__ void soft_reset(LT& L, int lane) {
 // kernels
 // ----------------------------------------------------------------------------------
 template <int N, bool V2, int RULES = 0>
-__global__ __launch_bounds__(64, 2) void env_step_kernel(const DevModel* __restrict__ Mp, float* __restrict__ recs,
-                                                      const float* __restrict__ mu_plane,
-                                                      float* __restrict__ actions, float* __restrict__ obs,
-                                                      float* __restrict__ rew, uint8_t* __restrict__ done,
-                                                      int32_t* __restrict__ substeps, int vec_mode, int n_envs,
-                                                      const int32_t* __restrict__ order, float* __restrict__ rows_all,
-                                                      float* __restrict__ mf_all, unsigned long long* __restrict__ ovf,
-                                                      float* __restrict__ box_all, int obs_stride, int packed) {
-    extern __shared__ float4 smem_raw[];
-    using LT = LdsFor<N, V2, RULES>;
-    LT& L = *reinterpret_cast<LT*>(smem_raw);
-    const DevModel& M = *Mp;
-    // longest-first schedule: workgroup b takes the envs with the b-th, (b + G)-th, ... largest predicted work (G
-    // workgroups: as many as the chip holds at once; the block of streamed constraint rows belongs to the WORKGROUP)
-    for (int slot_ = blockIdx.x; slot_ < n_envs; slot_ += gridDim.x) {
-    const int env = order ? __builtin_amdgcn_readfirstlane(order[slot_]) : slot_;
-    const int lane = threadIdx.x;
-    if (M.poison) { L.poison(lane); lds_sync(); }
-    load_rec(L, recs + (size_t)env * LT::REC, lane);
-    const int A = M.act_dim;
-    // checkBound (SnakeGymEnv.py:82-88) clips the caller's array in place
-    float act = 0.f;
-    if (lane < A) {
-        act = actions[(size_t)env * A + lane];
-        float cl = fminf(fmaxf(act, -1.0f), 1.0f);
-        if (cl != act) actions[(size_t)env * A + lane] = cl;
-        act = cl;
-    }
-    // createAction (snake.py:247-269) + convertActionToJointCommand (snake.py:223-225)
-    if (lane < N) L.targets[lane] = 0.f;
-    lds_sync();
-    if (lane < A) {
-        int slot = (M.gait == 0) ? 2 * lane : ((M.gait == 1) ? 2 * lane + 1 : lane);
-        L.targets[slot] = act * M.scaling;
-    }
-    lds_sync();
-    float mu = fminf(M.mu_link * mu_plane[env], 10.0f);
-    // constraint rows of the streamed-row solve (also behind the register-resident one, for the substeps whose contacts
-    // outgrow its slots: substep())
-    float* env_rows = rows_all + (size_t)blockIdx.x * Lds<N, false>::kRowFloats;
-    float* env_mf = mf_all ? mf_all + (size_t)env * (2 * N * kMfFloats) : nullptr;   // contact cache (contact_model 1)
-    load_mf(L, env_mf, lane);
-    float* env_box = box_all ? box_all + (size_t)env * kBoxFloats : nullptr;
-    load_box(L, env_box, lane);
-    fk_vel(L, M, lane);
-    // Snake.step servo loop (snake.py:283-304)
-    int counter = 0;
-    bool end_height = false;
-    int it_dummy = 0, nc_dummy = 0;
-    SensorHint hint;
-    hint.always = false;
-    hint.h_prev = mean_height(L, M, lane);
-    while (true) {
-        float e = (lane < N) ? (L.targets[lane] - L.q()[lane]) : 0.f;
-        float nrm = sqrtf(wave_sum<64>(e * e));
-        if (!(nrm > M.servo_tol)) break;
-        hint.counter_next = counter + 1;
-        substep(L, M, lane, mu, it_dummy, nc_dummy, hint, env_rows, env_mf, ovf);
-        counter++;
-        hint.h_prev = mean_height(L, M, lane);
-        if (hint.h_prev > M.height_thr) { end_height = true; break; }
-        if (counter > M.max_counter) break;
-    }
-    // SnakeGymEnv.step (SnakeGymEnv.py:36-42)
-    float en = (lane < N) ? L.qd()[lane] * L.taum()[lane] * M.energy_dt : 0.f;   // snake.py:336-341
-    float energy = wave_sum<64>(en);
-    float x = L.rec[0], y = L.rec[1], fzv = L.fz();
-    float r = M.alpha * (x - L.prev_x()) + (fabsf(fzv) > M.coll_force ? M.coll_pen : 0.f) - M.beta * fabsf(y) -
-              M.gamma * energy;
-    bool dn = fabsf(L.rec[13 + M.term_index]) > M.term_angle;
-    if (!dn) dn = mean_height(L, M, lane) > M.height_thr;
-    if (!dn) dn = end_height;
-    if (dn) r += M.done_pen;
-    float* ob = obs + (size_t)env * obs_stride;
-    if (!(dn && vec_mode)) write_obs(L, ob, lane);
-    lds_sync();
-    if (dn) {
-        soft_reset(L, lane);
-        lds_sync();
-        if (vec_mode) write_obs(L, ob, lane);   // worker returns env.reset()'s obs
-    }
-    lds_sync();
-    if (lane == 0) {
-        // _observation = terminal obs (SnakeGymEnv.py:42); the worker's reset() refreshes it
-        L.prev_x() = (dn && vec_mode) ? 0.0f : x;
-        if (packed) {       // snk_step_packed: [obs | reward | done] rows (StepArgs::packed)
-            ob[3 * N + 8] = r;
-            reinterpret_cast<uint32_t*>(ob)[3 * N + 9] = dn ? 1u : 0u;
-        } else {
-            rew[env] = r;
-            done[env] = dn ? 1 : 0;
-        }
-        if (substeps) substeps[env] = counter;
-    }
-    store_rec(L, recs + (size_t)env * LT::REC, lane);
-    store_mf<LT, false>(L, env_mf, lane);
-    store_box<LT, false>(L, env_box, lane);
-    lds_sync();
-    }
-}
-
-template <int N, bool V2, int RULES = 0>
 __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restrict__ Mp, float* __restrict__ recs,
                                                      const float* __restrict__ mu_plane,
                                                      const float* __restrict__ targets, int k,
@@ -2221,7 +2145,7 @@ __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restri
     const int lane = threadIdx.x;
     for (int env = blockIdx.x; env < n_envs; env += gridDim.x) {      // (the block of streamed rows belongs to the workgroup)
     if (M.poison) { L.poison(lane); lds_sync(); }
-    load_rec(L, recs + (size_t)env * LT::REC, lane);
+    load_env(L, recs, mf_all, box_all, env, lane);
     if (lane < N) L.targets[lane] = targets[(size_t)env * N + lane];
     lds_sync();
     float mu = fminf(M.mu_link * mu_plane[env], 10.0f);
@@ -2229,16 +2153,11 @@ __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restri
     int iters = 0, nc = 0;
     SensorHint hint;
     hint.always = true; hint.counter_next = 0; hint.h_prev = 0.f;
-    float* env_rows = rows_all + (size_t)blockIdx.x * Lds<N, false>::kRowFloats;
-    float* env_mf = mf_all ? mf_all + (size_t)env * (2 * N * kMfFloats) : nullptr;
-    load_mf(L, env_mf, lane);
-    float* env_box = box_all ? box_all + (size_t)env * kBoxFloats : nullptr;
-    load_box(L, env_box, lane);
+    float* env_rows = rows_of<N>(rows_all);
+    float* env_mf = cache_of<N>(mf_all, env);
     for (int s = 0; s < k; s++) substep(L, M, lane, mu, iters, nc, hint, env_rows, env_mf, ovf);
     if (info && lane == 0) { info[2 * env] = iters; info[2 * env + 1] = nc; }
-    store_rec(L, recs + (size_t)env * LT::REC, lane);
-    store_mf<LT, false>(L, env_mf, lane);
-    store_box<LT, false>(L, env_box, lane);
+    store_env<LT, false>(L, recs, mf_all, box_all, env, lane);
     lds_sync();
     }
 }
@@ -2304,11 +2223,28 @@ __global__ __launch_bounds__(64) void obs_kernel(const DevModel* __restrict__ Mp
 // key); env_step_kernel's workgroup b then runs order[b].  Pure scheduling: results do not
 // depend on the order.
 // ----------------------------------------------------------------------------------
+// squared servo error of env e before its env-step: the targets the env-step will set from the caller's actions (clipped,
+// mapped to joints by the gait: set_targets) against the joint angles of the env's record
+template <int N>
+__device__ __forceinline__ float servo_err2(const DevModel& M, int A, const float* __restrict__ recs,
+                                            const float* __restrict__ actions, int e) {
+    constexpr int REC = (N <= 16) ? 64 : 128;
+    const float* q = recs + (size_t)e * REC + 13;
+    float err2 = 0.f;
+    for (int j = 0; j < N; j++) {
+        int k = (M.gait == 0) ? ((j & 1) ? -1 : j / 2) : ((M.gait == 1) ? ((j & 1) ? j / 2 : -1) : j);
+        float t = 0.f;
+        if (k >= 0 && k < A) t = fminf(fmaxf(actions[(size_t)e * A + k], -1.f), 1.f) * M.scaling;
+        float d = t - q[j];
+        err2 += d * d;
+    }
+    return err2;
+}
+
 template <int N>
 __global__ __launch_bounds__(1024) void plan_kernel(const DevModel* __restrict__ Mp, const float* __restrict__ recs,
                                                     const float* __restrict__ actions, int32_t* __restrict__ order,
                                                     int n_envs) {
-    constexpr int REC = (N <= 16) ? 64 : 128;
     constexpr int NBIN = 256;
     __shared__ int hist[NBIN];
     __shared__ int base[NBIN];
@@ -2318,15 +2254,7 @@ __global__ __launch_bounds__(1024) void plan_kernel(const DevModel* __restrict__
     __syncthreads();
     const int A = M.act_dim;
     auto key_of = [&](int e) {
-        const float* q = recs + (size_t)e * REC + 13;
-        float err2 = 0.f;
-        for (int j = 0; j < N; j++) {
-            int k = (M.gait == 0) ? ((j & 1) ? -1 : j / 2) : ((M.gait == 1) ? ((j & 1) ? j / 2 : -1) : j);
-            float t = 0.f;
-            if (k >= 0 && k < A) t = fminf(fmaxf(actions[(size_t)e * A + k], -1.f), 1.f) * M.scaling;
-            float d = t - q[j];
-            err2 += d * d;
-        }
+        const float err2 = servo_err2<N>(M, A, recs, actions, e);
         // larger error -> smaller bin index -> earlier workgroup.  log scale, 256 bins.
         float l = __log2f(fmaxf(err2, 1e-12f));          // about [-40, 8]
         int b = (int)((8.0f - l) * 5.0f);
@@ -2503,25 +2431,13 @@ __device__ __forceinline__ void sched_push(const Sched& sc, int lane, int env, i
 template <int N>
 __global__ __launch_bounds__(1024) void plan_sched_kernel(const DevModel* __restrict__ Mp, const float* __restrict__ recs,
                                                           const float* __restrict__ actions, Sched sc, int n_envs) {
-    constexpr int REC = (N <= 16) ? 64 : 128;
     __shared__ uint32_t hist[kBuckets], base[kBuckets];
     const DevModel& M = *Mp;
     const int tid = threadIdx.x;
     if (tid < kBuckets) hist[tid] = 0;
     __syncthreads();
     const int A = M.act_dim;
-    auto key_of = [&](int e) {
-        const float* q = recs + (size_t)e * REC + 13;
-        float err2 = 0.f;
-        for (int j = 0; j < N; j++) {
-            int k = (M.gait == 0) ? ((j & 1) ? -1 : j / 2) : ((M.gait == 1) ? ((j & 1) ? j / 2 : -1) : j);
-            float t = 0.f;
-            if (k >= 0 && k < A) t = fminf(fmaxf(actions[(size_t)e * A + k], -1.f), 1.f) * M.scaling;
-            float d = t - q[j];
-            err2 += d * d;
-        }
-        return predict_remaining(M, sqrtf(err2), 0);
-    };
+    auto key_of = [&](int e) { return predict_remaining(M, sqrtf(servo_err2<N>(M, A, recs, actions, e)), 0); };
     constexpr int kKeep = 8;                 // keys of the first 8 envs of a thread stay in registers for the second pass
     int keys[kKeep];
 #pragma unroll
@@ -2578,6 +2494,10 @@ struct StepArgs {
     // and done flag of env e go into its obs row, at float index obs_dim (f32) and obs_dim + 1 (u32 0 / 1), instead of
     // rew[] / done[]: one [n_envs x stride] buffer that a sharded vector env gathers as it is (device_env.py)
     int32_t obs_stride, packed, pad_;
+    // the unscheduled kernel (env_step_kernel) only: its model, and plan_kernel's order (null: launch order).  Appended,
+    // so that the scheduled kernel's offsets stay as they were
+    const DevModel* model;
+    const int32_t* order;
 };
 typedef const StepArgs __attribute__((address_space(4))) * StepArgPtr;
 __device__ __forceinline__ StepArgPtr step_args() {
@@ -2591,6 +2511,116 @@ __device__ __forceinline__ Sched load_sched(StepArgPtr p) {
     sc.counter = p->sc.counter; sc.finished = p->sc.finished; sc.alarm = p->sc.alarm;
     sc.cap = p->sc.cap; sc.quantum = p->sc.quantum; sc.hyst = p->sc.hyst; sc.wstat = p->sc.wstat;
     return sc;
+}
+
+// Start of an env-step: checkBound (SnakeGymEnv.py:82-88) clips the caller's array in place, createAction
+// (snake.py:247-269) + convertActionToJointCommand (snake.py:223-225) set the joint targets.
+template <class LT>
+__device__ __forceinline__ void set_targets(LT& L, const DevModel& M, float* __restrict__ actions, int env, int lane) {
+    constexpr int N = LT::kN;
+    const int A = M.act_dim;
+    float act = 0.f;
+    if (lane < A) {
+        act = actions[(size_t)env * A + lane];
+        float cl = fminf(fmaxf(act, -1.0f), 1.0f);
+        if (cl != act) actions[(size_t)env * A + lane] = cl;
+        act = cl;
+    }
+    if (lane < N) L.targets[lane] = 0.f;
+    lds_sync();
+    if (lane < A) {
+        int slot = (M.gait == 0) ? 2 * lane : ((M.gait == 1) ? 2 * lane + 1 : lane);
+        L.targets[slot] = act * M.scaling;
+    }
+    lds_sync();
+}
+
+// End of an env-step whose servo loop ran `counter` substeps: SnakeGymEnv.step (SnakeGymEnv.py:36-42).  The outputs
+// are read through `af` here, at the place of use (StepArgs).
+template <class LT>
+__device__ __forceinline__ void finish_env_step(LT& L, const DevModel& M, StepArgPtr af, int env, int lane, int counter,
+                                                bool end_height) {
+    constexpr int N = LT::kN;
+    float en = (lane < N) ? L.qd()[lane] * L.taum()[lane] * M.energy_dt : 0.f;   // snake.py:336-341
+    float energy = wave_sum<64>(en);
+    float x = L.rec[0], y = L.rec[1], fzv = L.fz();
+    float r = M.alpha * (x - L.prev_x()) + (fabsf(fzv) > M.coll_force ? M.coll_pen : 0.f) - M.beta * fabsf(y) -
+              M.gamma * energy;
+    bool dn = uni(fabsf(L.rec[13 + M.term_index]) > M.term_angle);
+    if (!dn) dn = uni(mean_height(L, M, lane) > M.height_thr);
+    if (!dn) dn = end_height;
+    if (dn) r += M.done_pen;
+    const int vec_mode = af->vec_mode;
+    float* ob = af->obs + (size_t)env * af->obs_stride;
+    if (!(dn && vec_mode)) write_obs(L, ob, lane);
+    lds_sync();
+    if (dn) {
+        soft_reset(L, lane);
+        lds_sync();
+        if (vec_mode) write_obs(L, ob, lane);   // worker returns env.reset()'s obs
+    }
+    lds_sync();
+    if (lane == 0) {
+        // _observation = terminal obs (SnakeGymEnv.py:42); the worker's reset() refreshes it
+        L.prev_x() = (dn && vec_mode) ? 0.0f : x;
+        if (af->packed) {       // snk_step_packed: [obs | reward | done] rows (StepArgs::packed)
+            ob[3 * N + 8] = r;
+            reinterpret_cast<uint32_t*>(ob)[3 * N + 9] = dn ? 1u : 0u;
+        } else {
+            af->rew[env] = r;
+            af->done[env] = dn ? 1 : 0;
+        }
+        int32_t* substeps = af->substeps;
+        if (substeps) substeps[env] = counter;
+    }
+}
+
+// Whole env-steps in launch order, without the scheduler: SNK_QUANTUM=0, and the handles that find no model slot.
+template <int N, bool V2, int RULES = 0>
+__global__ __launch_bounds__(64, 2) void env_step_kernel(StepArgs args_by_value) {
+    (void)args_by_value;            // read through step_args() only
+    extern __shared__ float4 smem_raw[];
+    using LT = LdsFor<N, V2, RULES>;
+    LT& L = *reinterpret_cast<LT*>(smem_raw);
+    const DevModel& M = *step_args()->model;
+    // longest-first schedule: workgroup b takes the envs with the b-th, (b + G)-th, ... largest predicted work (G
+    // workgroups: as many as the chip holds at once; the block of streamed constraint rows belongs to the WORKGROUP)
+    for (int slot_ = blockIdx.x; slot_ < step_args()->n_envs; slot_ += gridDim.x) {
+    const StepArgPtr ap = step_args();
+    const int32_t* order = ap->order;
+    const int env = order ? __builtin_amdgcn_readfirstlane(order[slot_]) : slot_;
+    const int lane = threadIdx.x;
+    if (M.poison) { L.poison(lane); lds_sync(); }
+    load_env(L, ap->recs, ap->mf_all, ap->box_all, env, lane);
+    set_targets(L, M, ap->actions, env, lane);
+    float mu = fminf(M.mu_link * ap->mu_plane[env], 10.0f);
+    float* env_rows = rows_of<N>(ap->rows_all);
+    float* env_mf = cache_of<N>(ap->mf_all, env);
+    unsigned long long* ovf = ap->ovf;
+    fk_vel(L, M, lane);
+    // Snake.step servo loop (snake.py:283-304)
+    int counter = 0;
+    bool end_height = false;
+    int it_dummy = 0, nc_dummy = 0;
+    SensorHint hint;
+    hint.always = false;
+    hint.h_prev = mean_height(L, M, lane);
+    while (true) {
+        float e = (lane < N) ? (L.targets[lane] - L.q()[lane]) : 0.f;
+        float nrm = sqrtf(wave_sum<64>(e * e));
+        if (!(nrm > M.servo_tol)) break;
+        hint.counter_next = counter + 1;
+        substep(L, M, lane, mu, it_dummy, nc_dummy, hint, env_rows, env_mf, ovf);
+        counter++;
+        hint.h_prev = mean_height(L, M, lane);
+        if (hint.h_prev > M.height_thr) { end_height = true; break; }
+        if (counter > M.max_counter) break;
+    }
+    const StepArgPtr af = step_args();
+    finish_env_step(L, M, af, env, lane, counter, end_height);
+    store_env<LT, false>(L, af->recs, af->mf_all, af->box_all, env, lane);
+    lds_sync();
+    }
 }
 
 template <int N, bool V2, int RULES = 0>
@@ -2610,7 +2640,6 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
 #endif
         const StepArgPtr ap = step_args();
         const DevModel& M = g_models[ap->model_slot];
-        const int A = M.act_dim;
         const int n_envs = ap->n_envs;
         int env;
         {
@@ -2633,41 +2662,18 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (M.poison) { L.poison(lane); lds_sync(); }
+        // what load_env loads, split around the counter check and the targets: loaded in one go they change this kernel's
+        // spill code
         load_rec(L, ap->recs + (size_t)env * LT::REC, lane);
         int counter = __builtin_amdgcn_readfirstlane(ap->sc.counter[env]);
         if (counter < 0 || counter > M.max_counter + 1 || env >= n_envs) {     // never, unless a hand-off went wrong
             sched_alarm(load_sched(ap), lane);
             break;
         }
-        // checkBound (SnakeGymEnv.py:82-88) clips the caller's array in place
-        float act = 0.f;
-        if (lane < A) {
-            float* actions = ap->actions;
-            act = actions[(size_t)env * A + lane];
-            float cl = fminf(fmaxf(act, -1.0f), 1.0f);
-            if (cl != act) actions[(size_t)env * A + lane] = cl;
-            act = cl;
-        }
-        // createAction (snake.py:247-269) + convertActionToJointCommand (snake.py:223-225)
-        if (lane < N) L.targets[lane] = 0.f;
-        lds_sync();
-        if (lane < A) {
-            int slot = (M.gait == 0) ? 2 * lane : ((M.gait == 1) ? 2 * lane + 1 : lane);
-            L.targets[slot] = act * M.scaling;
-        }
-        lds_sync();
+        set_targets(L, M, ap->actions, env, lane);
         const float mu = fminf(M.mu_link * ap->mu_plane[env], 10.0f);
-        // contact cache of the environment (contact_model 1): recomputed from the argument segment wherever it is used
-        auto env_mf = [&](StepArgPtr q) -> float* {
-            float* mf_all = q->mf_all;
-            return mf_all ? mf_all + (size_t)env * (2 * N * kMfFloats) : nullptr;
-        };
-        load_mf(L, env_mf(ap), lane);
-        auto env_box = [&](StepArgPtr q) -> float* {           // the free box of obstacle 2 (null otherwise)
-            float* box_all = q->box_all;
-            return box_all ? box_all + (size_t)env * kBoxFloats : nullptr;
-        };
-        load_box(L, env_box(ap), lane);
+        load_mf(L, cache_of<N>(ap->mf_all, env), lane);
+        load_box(L, box_of(ap->box_all, env), lane);
         fk_vel(L, M, lane);
         // Snake.step servo loop (snake.py:283-304), `quantum` substeps at a time
         bool end_height = false, complete = false;
@@ -2689,9 +2695,8 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
                 n_chk++; s_top += top; s_rem += remaining; if (top > remaining) n_req++;
 #endif
                 if (top >= remaining + sc.hyst) {
-                    store_rec_through(L, aq->recs + (size_t)env * LT::REC, lane);
-                    store_mf<LT, true>(L, env_mf(aq), lane);        // the contact cache travels with the record
-                    store_box<LT, true>(L, env_box(aq), lane);
+                    // the contact cache and the box travel with the record
+                    store_env<LT, true>(L, aq->recs, aq->mf_all, aq->box_all, env, lane);
                     __hip_atomic_store(&sc.counter[env], counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     sched_push(sc, lane, env, remaining);
                     break;
@@ -2699,13 +2704,8 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
                 in_slice = 0;
             }
             hint.counter_next = counter + 1;
-            {
-                // constraint rows of the streamed-row solve, one block per resident wave (also behind the register-resident
-                // solve, for the substeps whose contacts outgrow its slots: substep())
-                float* env_rows = aq->rows_all + (size_t)blockIdx.x * Lds<N, false>::kRowFloats;
-                substep(L, M, lane, mu, it_dummy, nc_dummy, hint, env_rows, env_mf(aq), aq->ovf);
-                lane = lane_id();       // (not kept in a register across the solve)
-            }
+            substep(L, M, lane, mu, it_dummy, nc_dummy, hint, rows_of<N>(aq->rows_all), cache_of<N>(aq->mf_all, env), aq->ovf);
+            lane = lane_id();       // (not kept in a register across the solve)
 #ifdef SNK_SCHED_DEBUG
             n_sub++;
 #endif
@@ -2717,42 +2717,8 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
         }
         if (!complete) continue;
         const StepArgPtr af = step_args();
-        // SnakeGymEnv.step (SnakeGymEnv.py:36-42)
-        float en = (lane < N) ? L.qd()[lane] * L.taum()[lane] * M.energy_dt : 0.f;   // snake.py:336-341
-        float energy = wave_sum<64>(en);
-        float x = L.rec[0], y = L.rec[1], fzv = L.fz();
-        float r = M.alpha * (x - L.prev_x()) + (fabsf(fzv) > M.coll_force ? M.coll_pen : 0.f) - M.beta * fabsf(y) -
-                  M.gamma * energy;
-        bool dn = uni(fabsf(L.rec[13 + M.term_index]) > M.term_angle);
-        if (!dn) dn = uni(mean_height(L, M, lane) > M.height_thr);
-        if (!dn) dn = end_height;
-        if (dn) r += M.done_pen;
-        const int vec_mode = af->vec_mode;
-        float* ob = af->obs + (size_t)env * af->obs_stride;
-        if (!(dn && vec_mode)) write_obs(L, ob, lane);
-        lds_sync();
-        if (dn) {
-            soft_reset(L, lane);
-            lds_sync();
-            if (vec_mode) write_obs(L, ob, lane);   // worker returns env.reset()'s obs
-        }
-        lds_sync();
-        if (lane == 0) {
-            // _observation = terminal obs (SnakeGymEnv.py:42); the worker's reset() refreshes it
-            L.prev_x() = (dn && vec_mode) ? 0.0f : x;
-            if (af->packed) {
-                ob[3 * N + 8] = r;
-                reinterpret_cast<uint32_t*>(ob)[3 * N + 9] = dn ? 1u : 0u;
-            } else {
-                af->rew[env] = r;
-                af->done[env] = dn ? 1 : 0;
-            }
-            int32_t* substeps = af->substeps;
-            if (substeps) substeps[env] = counter;
-        }
-        store_rec(L, af->recs + (size_t)env * LT::REC, lane);
-        store_mf<LT, false>(L, env_mf(af), lane);
-        store_box<LT, false>(L, env_box(af), lane);
+        finish_env_step(L, M, af, env, lane, counter, end_height);
+        store_env<LT, false>(L, af->recs, af->mf_all, af->box_all, env, lane);
         atomicAdd(af->sc.finished, lane == 0 ? 1 : 0);
     }
 }

@@ -1,6 +1,6 @@
 """Compiler-generated instructions between the hand-written asm row steps of the solve loop.
 usage: python tools/isa_junk.py   (compiles csrc/snk_api.hip with -save-temps into /tmp/snk_isa)"""
-import os, subprocess, sys
+import os, re, subprocess, sys
 from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = "/tmp/snk_isa"
@@ -9,7 +9,10 @@ subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++
                 "-c", os.path.join(ROOT, "bullet-envs_amd/csrc/snk_api.hip"), "-o", os.path.join(out, "snk.o")],
                cwd=out, check=True, stderr=subprocess.DEVNULL)
 s = open(os.path.join(out, "snk_api-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-a = s.index("_ZN3snk15env_step_kernelILi16EEEvPKNS_8DevModelEPfPKfS4_S4_S4_PhPiiiPKi:")
+# the headline kernel, env_step_sched_kernel<16, true, 0>, found by its demangled name
+labels = re.findall(r"^(_ZN3snk\w*env_step_sched_kernel\w*):", s, re.M)
+names = subprocess.run(["c++filt"], input="\n".join(labels), capture_output=True, text=True).stdout.split("\n")
+a = s.index(next(l for l, d in zip(labels, names) if d.startswith("void snk::env_step_sched_kernel<16, true, 0>(")) + ":")
 f = s[a:s.index(".Lfunc_end", a)].split("\n")
 blocks, cur = [], None
 for i, l in enumerate(f):
