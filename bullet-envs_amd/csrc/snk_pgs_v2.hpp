@@ -681,6 +681,18 @@ __device__ int find_contacts_manifold_v1(LT& L, const DevModel& M, int lane, flo
 // (A in staging rows 0..31, B in rows 32..63, so one pass over the slots fills both halves).
 // Staging row layout: [0..21] M^-1 J^T, [22] rhs impulse, [23] denominator, [24] 1/denominator.
 // ------------------------------------------------------------------------------------
+// the wave-uniform constants one body contributes to a delta sweep
+struct BodyK {
+    f3 ax, Ua, Ub, r;
+    float Dinv;
+};
+template <class LT>
+__device__ __forceinline__ BodyK load_body_k(LT& L, int b) {
+    BodyK c;
+    c.ax = ld3(L.ax[b]); c.Ua = ld3(L.Ua[b]); c.Ub = ld3(L.Ub[b]); c.r = ld3(L.r[b]);
+    c.Dinv = L.Dinv[b];
+    return c;
+}
 template <class LT, int KIND>
 __device__ void build_batch_v2(LT& L, const DevModel& M, int lane, int nc, int base = 0) {
     constexpr int N = LT::kN;
@@ -699,20 +711,28 @@ __device__ void build_batch_v2(LT& L, const DevModel& M, int lane, int nc, int b
             d = KIND == 1 ? (ci < L.nplane ? mk3(0.f, 0.f, 1.f) : ld3(L.obn[ci - L.nplane])) : ld3(L.cdir[L.ccds[ci]][lane >> 5]);
         }
         f3 pN = mk3(0, 0, 0), pF = mk3(0, 0, 0);
+        // Both sweeps are serial chains over the bodies, and every body's constants sit at addresses that depend on no
+        // computed value: they are read ONE BODY AHEAD of the arithmetic that consumes them (in front of the staging
+        // store, which the loads of the same body otherwise queue behind), so the chain waits for loads issued a whole
+        // body earlier.  Only the loads move; the arithmetic and its order are what they were.
+        const f3 oK = ld3(L.o[motor ? 0 : k]);     // origin of the row's own body (the one lane-dependent read)
+        BodyK cur = load_body_k(L, N);
 #pragma unroll 4
         for (int b = N; b >= 1; b--) {
-            f3 ax = ld3(L.ax[b]);
+            const BodyK nxt = load_body_k(L, b > 1 ? b - 1 : 1);
+            f3 ax = cur.ax;
             if (!motor && b == k) {
-                pN = pN - cross(P - ld3(L.o[b]), d);
+                pN = pN - cross(P - oK, d);
                 pF = pF - d;
             }
             float u = -dot(ax, pN);
             if (motor && b == k) u += 1.0f;
             Mrow[6 + b - 1] = u;
-            float t = u * L.Dinv[b];
-            f3 paN = pN + ld3(L.Ua[b]) * t, paF = pF + ld3(L.Ub[b]) * t;
-            pN = paN + cross(ld3(L.r[b]), paF);
+            float t = u * cur.Dinv;
+            f3 paN = pN + cur.Ua * t, paF = pF + cur.Ub * t;
+            pN = paN + cross(cur.r, paF);
             pF = paF;
+            cur = nxt;
         }
         f3 J0 = mk3(0, 0, 0), J1 = mk3(0, 0, 0);
         if (!motor) {
@@ -733,21 +753,29 @@ __device__ void build_batch_v2(LT& L, const DevModel& M, int lane, int nc, int b
         const float* gb = L.base() + 7;
         float den = dot(J0, al) + dot(J1, a);
         float rv = dot(J0, ld3(gb)) + dot(J1, ld3(gb + 3));
+        cur = load_body_k(L, 1);
+        f3 ob = ld3(L.o[1]);
+        float qdb = L.qd()[0], ub = Mrow[6];
 #pragma unroll 4
         for (int b = 1; b <= N; b++) {
-            a = a + cross(al, ld3(L.r[b]));
-            float u = Mrow[6 + b - 1];
-            float qdd = (u - (dot(ld3(L.Ua[b]), al) + dot(ld3(L.Ub[b]), a))) * L.Dinv[b];
-            f3 ax = ld3(L.ax[b]);
+            const int bn = b < N ? b + 1 : N;
+            const BodyK nxt = load_body_k(L, bn);
+            const f3 obn = ld3(L.o[bn]);
+            const float qdn = L.qd()[bn - 1], un = Mrow[6 + bn - 1];
+            a = a + cross(al, cur.r);
+            float u = ub;
+            float qdd = (u - (dot(cur.Ua, al) + dot(cur.Ub, a))) * cur.Dinv;
+            f3 ax = cur.ax;
             al = al + ax * qdd;
             Mrow[6 + b - 1] = qdd;
             if (!motor) {
-                float Jb = (b <= k) ? dot(ax, cross(P - ld3(L.o[b]), d)) : 0.f;
+                float Jb = (b <= k) ? dot(ax, cross(P - ob, d)) : 0.f;
                 den += Jb * qdd;
-                rv += Jb * L.qd()[b - 1];
+                rv += Jb * qdb;
             } else if (b == k) {
                 den = qdd;
             }
+            cur = nxt; ob = obn; qdb = qdn; ub = un;
         }
         float dinv = den > 1.1920929e-7f ? 1.0f / den : 0.f;
         float target;
@@ -1534,13 +1562,20 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
         if (nc > 24) load_slots8<LT, 4, 24, kSlotFric>(L, K, nc, 0, ms, RJ, RM, wsum);
         lds_sync();
         SNK_STAMP(6)
-        build_batch_v2<LT, 4>(L, M, lane, nc, 32);      // no active lanes when nc <= 32
-        SNK_STAMP(7)
-        if (nc > 32) load_slots8<LT, 4, 32, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
-        if (nc > 40) load_slots8<LT, 4, 40, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
-        if (nc > 48) load_slots8<LT, 4, 48, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
-        if (nc > 56) load_slots8<LT, 4, 56, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
-        lds_sync();
+        // the second batch has no active lane when nc <= 32 (about half of the gait's substeps): the batch, its barrier and
+        // the barrier behind its slot loads sit behind ONE wave-uniform branch (the barrier after the first batch's loads
+        // already stands between them and the normals' staging rows)
+        if (nc > 32) {
+            build_batch_v2<LT, 4>(L, M, lane, nc, 32);
+            SNK_STAMP(7)
+            load_slots8<LT, 4, 32, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
+            if (nc > 40) load_slots8<LT, 4, 40, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
+            if (nc > 48) load_slots8<LT, 4, 48, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
+            if (nc > 56) load_slots8<LT, 4, 56, kSlotFric>(L, K, nc, 32, ms, RJ, RM, wsum);
+            lds_sync();
+        } else {
+            SNK_STAMP(7)
+        }
         SNK_STAMP(8)
         build_batch_v2<LT, 1>(L, M, lane, nc);
         SNK_STAMP(9)
@@ -1570,16 +1605,19 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     // (the upper row is resolved after the lower one).  Pyramid friction resolves the two
     // directions of a contact one after the other, so its slots are duos as well.
     {
-#pragma unroll
-        for (int s = 0; s < kSlotFric; s++) {
-            swap2 sw = half_swap(RM[s], RM[s]);             // a = [RM_lower, RM_lower], b = [RM_upper, RM_upper]
-            float t = half_reduce(RJ[s] * sw.a);
-            RJ[s] = wrlane(RJ[s], rdlane(t, 63), 62);       // d = 30 of the upper half: duo_step's row_shr:1 source
-        }
-        // ... and the 2 x 2 block between the two slots of a quad_step (four normals per step): lanes d = 29, 28
+        // Groups of four normal slots (eight contacts) behind one scalar branch: the rows past the active count are zeros,
+        // their coupling scalar is the zero that lane 62 already holds.
 #pragma unroll
         for (int g = 0; g < 8; g++) {
             if (nc > 8 * g) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int s = kSlotNormal + 4 * g + i;
+                    swap2 sw = half_swap(RM[s], RM[s]);             // a = [RM_lower, RM_lower], b = [RM_upper, RM_upper]
+                    float t = half_reduce(RJ[s] * sw.a);
+                    RJ[s] = wrlane(RJ[s], rdlane(t, 63), 62);       // d = 30 of the upper half: duo_step's row_shr:1 source
+                }
+                // ... and the 2 x 2 block between the two slots of a quad_step (four normals per step): lanes d = 29, 28
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
                     const int s = kSlotNormal + 4 * g + 2 * i;
@@ -1589,10 +1627,16 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
         }
         if (M.cone == 0) {
 #pragma unroll
-            for (int s = kSlotFric; s < kSlots; s++) {
-                swap2 sw = half_swap(RM[s], RM[s]);
-                float t = half_reduce(RJ[s] * sw.a);
-                RJ[s] = wrlane(RJ[s], rdlane(t, 63), 62);
+            for (int g = 0; g < 8; g++) {
+                if (nc > 8 * g) {                           // (slot = contact: eight contacts per branch, as below)
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        const int s = kSlotFric + 8 * g + i;
+                        swap2 sw = half_swap(RM[s], RM[s]);
+                        float t = half_reduce(RJ[s] * sw.a);
+                        RJ[s] = wrlane(RJ[s], rdlane(t, 63), 62);
+                    }
+                }
             }
         } else {
             // cone friction resolves two contacts per step (cone2_step): the 2 x 2 coupling block of each pair of
@@ -1794,6 +1838,12 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     // (sensor_pass_v2 above), which protects every such value.  The detour stays: it costs one LDS write and read per
     // substep and takes a register out of the callee-saved set around the call.
     L.stM[lane][20] = dv;
+#ifdef SNK_PROFILE
+    // (a substep without the pass shows zero ticks for its two phases; the profile build counts the passes in the third
+    //  overflow counter, which is structurally zero on this solve: tools/dbg/sensor_rate.py)
+    prof_t[14] = prof_t[13]; prof_t[15] = prof_t[13];
+    if (sensor && lane == 0) atomicAdd(ovf + 2, 1ull);
+#endif
     if (sensor) {
 #ifdef SNK_PROFILE
         sensor_pass_v2(L, M, nc, nlim, prof_t);
