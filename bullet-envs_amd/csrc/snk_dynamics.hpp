@@ -1,0 +1,352 @@
+// snk_dynamics.hpp -- the chain's dynamics on an LDS image, shared by both solves: forward kinematics and link velocities,
+// checkSnakeHeight's mean height, the per-body bias forces, the articulated-body sweeps, and the rule for when a substep
+// needs its sensor pass.
+#pragma once
+#include "snk_lds.hpp"
+#include "snk_model.hpp"
+#include "snk_wave.hpp"
+
+namespace snk {
+
+// ----------------------------------------------------------------------------------
+// S1: forward kinematics + link velocities of the chain (serial recurrence, evaluated
+// uniformly by the wave; lane 0 stores)
+// ----------------------------------------------------------------------------------
+template <class LT>
+__device__ void fk_vel(LT& L, const DevModel& M, int lane) {
+    constexpr int N = LT::kN;
+    const float* bs = L.base();
+    float qx = bs[3], qy = bs[4], qz = bs[5], qw = bs[6];
+    float dd = qx * qx + qy * qy + qz * qz + qw * qw;
+    float s2 = 2.0f / dd;
+    float xs = qx * s2, ys = qy * s2, zs = qz * s2;
+    float wx = qw * xs, wy = qw * ys, wz = qw * zs;
+    float xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
+    float Rp[9] = {1 - (yy + zz), xy - wz, xz + wy, xy + wz, 1 - (xx + zz), yz - wx, xz - wy, yz + wx, 1 - (xx + yy)};
+    f3 op = ld3(bs), wp = ld3(bs + 7), vp = ld3(bs + 10);
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) L.R[0][i] = Rp[i];
+        st3(L.o[0], op); st3(L.w[0], wp); st3(L.v[0], vp);
+        st3(L.r[0], mk3(0, 0, 0)); st3(L.ax[0], mk3(0, 0, 0));
+#pragma unroll
+        for (int i = 0; i < 6; i++) L.zeta[0][i] = 0.f;
+    }
+    // sin/cos of all joint angles at once (lane = joint); the serial chain below picks them up
+    // with v_readlane instead of evaluating sincosf sixteen times one after the other
+    float snv = 0.f, csv = 1.f;
+    if (lane < N) sincosf(L.q()[lane], &snv, &csv);
+#pragma unroll 4
+    for (int b = 1; b <= N; b++) {
+        const float* Rf = M.Rfix[b];
+        float T[9];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                T[3 * i + j] = Rp[3 * i] * Rf[j] + Rp[3 * i + 1] * Rf[3 + j] + Rp[3 * i + 2] * Rf[6 + j];
+        float qdb = L.qd()[b - 1];
+        const float sn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(snv), b - 1));
+        const float cs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(csv), b - 1));
+        float Rn[9];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            Rn[3 * i + 0] = cs * T[3 * i] - sn * T[3 * i + 2];
+            Rn[3 * i + 1] = T[3 * i + 1];
+            Rn[3 * i + 2] = sn * T[3 * i] + cs * T[3 * i + 2];
+        }
+        f3 rb = mulRv(Rp, ld3(M.pfix[b]));
+        f3 o = op + rb;
+        f3 ax = mk3(T[1], T[4], T[7]);
+        f3 w = wp + ax * qdb;
+        f3 v = vp + cross(wp, rb);
+        f3 za = cross(wp, ax) * qdb;
+        f3 zl = cross(wp, cross(wp, rb));
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) L.R[b][i] = Rn[i];
+            st3(L.o[b], o); st3(L.r[b], rb); st3(L.ax[b], ax); st3(L.w[b], w); st3(L.v[b], v);
+            st3(&L.zeta[b][0], za); st3(&L.zeta[b][3], zl);
+        }
+#pragma unroll
+        for (int i = 0; i < 9; i++) Rp[i] = Rn[i];
+        op = o; wp = w; vp = v;
+    }
+    lds_sync();
+}
+
+// checkSnakeHeight's mean z over {`base` link COM, OUTPUT_BODY origins} (snake.py:237-245)
+template <class LT>
+__device__ float mean_height(LT& L, const DevModel& M, int lane) {
+    constexpr int N = LT::kN;
+    float z = 0.f;
+    if (lane == 0) z = L.o[0][2] + L.R[0][6] * M.hbase[0] + L.R[0][7] * M.hbase[1] + L.R[0][8] * M.hbase[2];
+    else if (lane <= N) z = L.o[lane][2];
+    return wave_sum<64>(z) * (1.0f / (N + 1));
+}
+
+// ----------------------------------------------------------------------------------
+// S2: per-body bias forces (lane = body): p_b = [w x I w ; m w x (w x c)] - external
+// ----------------------------------------------------------------------------------
+template <class LT, bool FIRST>
+__device__ void body_bias(LT& L, const DevModel& M, int lane) {
+    constexpr int N = LT::kN;
+    if (lane <= N) {
+        const int b = lane;
+        const float* R = L.R[b];
+        f3 w = ld3(L.w[b]), v = ld3(L.v[b]);
+        float m = M.mass[b];
+        f3 cw = mulRv(R, ld3(M.com[b]));
+        float Ibar[6];
+        rotSym(R, M.Ib[b], Ibar);
+        f3 pN = cross(w, mulSv(Ibar, w));
+        f3 pF = cross(w, cross(w, cw)) * m;
+        // [U] btMultiBody link damping, per original URDF link of the composite
+        float Irw[6];
+        rotSym(R, M.Irot[b], Irw);
+        float nw = sqrtf(dot(w, w));
+        pN = pN + mulSv(Irw, w) * (M.ang_damp + M.ang_damp * nw);
+        const int ns = M.nsub[b];
+        for (int s = 0; s < ns; s++) {
+            f3 cs = mulRv(R, ld3(M.sub_c[b][s]));
+            f3 vs = v + cross(w, cs);
+            float nv = sqrtf(dot(vs, vs));
+            f3 F = vs * (M.sub_m[b][s] * (M.lin_damp + M.lin_damp * nv));   // opposes motion
+            pF = pF + F;
+            pN = pN + cross(cs, F);
+        }
+        if (FIRST) {
+            f3 G = mk3(0.f, 0.f, m * M.gz);
+            pF = pF - G;
+            pN = pN - cross(cw, G);
+            st3(L.cw[b], cw);
+            // articulated inertia initial value  [[Ibar, m[c]x], [-m[c]x, m 1]]
+            float* IA = L.IA[b];
+#pragma unroll
+            for (int i = 0; i < 6; i++) IA[i] = Ibar[i];
+            float hx = m * cw.x, hy = m * cw.y, hz = m * cw.z;
+            IA[6] = 0.f; IA[7] = -hz; IA[8] = hy;
+            IA[9] = hz;  IA[10] = 0.f; IA[11] = -hx;
+            IA[12] = -hy; IA[13] = hx; IA[14] = 0.f;
+            IA[15] = m; IA[16] = 0.f; IA[17] = 0.f; IA[18] = m; IA[19] = 0.f; IA[20] = m;
+        } else {
+            pN = pN - ld3(L.ext(b));
+            pF = pF - ld3(L.ext(b) + 3);
+        }
+        st3(&L.p[b][0], pN);
+        st3(&L.p[b][3], pF);
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// S3: ABA sweeps, evaluated uniformly by the wave (serial recurrence over the chain).
+// FACTOR: also builds the articulated inertias IA, U = IA S, D = S^T U and the base inverse.
+// ----------------------------------------------------------------------------------
+template <class LT, bool FACTOR>
+__device__ void aba_main(LT& L, const DevModel& M, int lane) {
+    constexpr int N = LT::kN;
+    float cA[6], cB[9], cC[6];   // child contribution to the parent's articulated inertia
+#pragma unroll
+    for (int i = 0; i < 6; i++) { cA[i] = 0.f; cC[i] = 0.f; }
+#pragma unroll
+    for (int i = 0; i < 9; i++) cB[i] = 0.f;
+    f3 cN = mk3(0, 0, 0), cF = mk3(0, 0, 0);
+    for (int b = N; b >= 1; b--) {
+        float A[6], B[9], C[6];
+        float* IA = L.IA[b];
+#pragma unroll
+        for (int i = 0; i < 6; i++) { A[i] = IA[i]; C[i] = IA[15 + i]; }
+#pragma unroll
+        for (int i = 0; i < 9; i++) B[i] = IA[6 + i];
+        if (FACTOR) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) { A[i] += cA[i]; C[i] += cC[i]; }
+#pragma unroll
+            for (int i = 0; i < 9; i++) B[i] += cB[i];
+        }
+        f3 pN = ld3(&L.p[b][0]) + cN, pF = ld3(&L.p[b][3]) + cF;
+        f3 ax = ld3(L.ax[b]);
+        f3 Ua, Ub;
+        float Dinv;
+        if (FACTOR) {
+            Ua = mulSv(A, ax);
+            Ub = mk3(B[0] * ax.x + B[3] * ax.y + B[6] * ax.z, B[1] * ax.x + B[4] * ax.y + B[7] * ax.z,
+                     B[2] * ax.x + B[5] * ax.y + B[8] * ax.z);
+            Dinv = 1.0f / dot(ax, Ua);
+        } else {
+            Ua = ld3(L.Ua[b]); Ub = ld3(L.Ub[b]); Dinv = L.Dinv[b];
+        }
+        f3 za = ld3(&L.zeta[b][0]), zl = ld3(&L.zeta[b][3]);
+        float u = L.tauj[b - 1] - dot(ax, pN);
+        // IA zeta
+        f3 tN = mulSv(A, za) + mk3(B[0] * zl.x + B[1] * zl.y + B[2] * zl.z, B[3] * zl.x + B[4] * zl.y + B[5] * zl.z,
+                                   B[6] * zl.x + B[7] * zl.y + B[8] * zl.z);
+        f3 tF = mk3(B[0] * za.x + B[3] * za.y + B[6] * za.z, B[1] * za.x + B[4] * za.y + B[7] * za.z,
+                    B[2] * za.x + B[5] * za.y + B[8] * za.z) + mulSv(C, zl);
+        float uz = dot(Ua, za) + dot(Ub, zl);
+        float s = (u - uz) * Dinv;
+        f3 paN = pN + tN + Ua * s, paF = pF + tF + Ub * s;
+        f3 r = ld3(L.r[b]);
+        cN = paN + cross(r, paF);
+        cF = paF;
+        if (lane == 0) {
+            L.u[b] = u;
+            if (FACTOR) {
+#pragma unroll
+                for (int i = 0; i < 6; i++) { IA[i] = A[i]; IA[15 + i] = C[i]; }
+#pragma unroll
+                for (int i = 0; i < 9; i++) IA[6 + i] = B[i];
+                st3(L.Ua[b], Ua); st3(L.Ub[b], Ub); L.Dinv[b] = Dinv;
+            }
+        }
+        if (FACTOR) {
+            // Ia = IA - U U^T / D
+            float ua[3] = {Ua.x, Ua.y, Ua.z}, ub[3] = {Ub.x, Ub.y, Ub.z};
+            float Ap[6], Bp[9], Cp[6];
+            Ap[0] = A[0] - ua[0] * ua[0] * Dinv; Ap[1] = A[1] - ua[0] * ua[1] * Dinv; Ap[2] = A[2] - ua[0] * ua[2] * Dinv;
+            Ap[3] = A[3] - ua[1] * ua[1] * Dinv; Ap[4] = A[4] - ua[1] * ua[2] * Dinv; Ap[5] = A[5] - ua[2] * ua[2] * Dinv;
+            Cp[0] = C[0] - ub[0] * ub[0] * Dinv; Cp[1] = C[1] - ub[0] * ub[1] * Dinv; Cp[2] = C[2] - ub[0] * ub[2] * Dinv;
+            Cp[3] = C[3] - ub[1] * ub[1] * Dinv; Cp[4] = C[4] - ub[1] * ub[2] * Dinv; Cp[5] = C[5] - ub[2] * ub[2] * Dinv;
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+                for (int j = 0; j < 3; j++) Bp[3 * i + j] = B[3 * i + j] - ua[i] * ub[j] * Dinv;
+            // shift to the parent's origin: X = [[1,0],[-rx,1]];  IA_parent += X^T Ia X
+            //   Bn = Bp + rx Cp ;  An = Ap - Bp rx + rx Bn^T ;  Cn = Cp
+            f3 c0 = cross(r, mk3(Cp[0], Cp[1], Cp[2]));   // rx * column j of Cp (symmetric)
+            f3 c1 = cross(r, mk3(Cp[1], Cp[3], Cp[4]));
+            f3 c2 = cross(r, mk3(Cp[2], Cp[4], Cp[5]));
+            float Bn[9] = {Bp[0] + c0.x, Bp[1] + c1.x, Bp[2] + c2.x, Bp[3] + c0.y, Bp[4] + c1.y, Bp[5] + c2.y,
+                           Bp[6] + c0.z, Bp[7] + c1.z, Bp[8] + c2.z};
+            // (-Bp rx) row i = r x row_i(Bp);  (rx Bn^T) column j = r x row_j(Bn)
+            f3 e0 = cross(r, mk3(Bp[0], Bp[1], Bp[2])), e1 = cross(r, mk3(Bp[3], Bp[4], Bp[5])),
+               e2 = cross(r, mk3(Bp[6], Bp[7], Bp[8]));
+            f3 g0 = cross(r, mk3(Bn[0], Bn[1], Bn[2])), g1 = cross(r, mk3(Bn[3], Bn[4], Bn[5])),
+               g2 = cross(r, mk3(Bn[6], Bn[7], Bn[8]));
+            cA[0] = Ap[0] + e0.x + g0.x;
+            cA[1] = Ap[1] + e0.y + g1.x;
+            cA[2] = Ap[2] + e0.z + g2.x;
+            cA[3] = Ap[3] + e1.y + g1.y;
+            cA[4] = Ap[4] + e1.z + g2.y;
+            cA[5] = Ap[5] + e2.z + g2.z;
+#pragma unroll
+            for (int i = 0; i < 9; i++) cB[i] = Bn[i];
+#pragma unroll
+            for (int i = 0; i < 6; i++) cC[i] = Cp[i];
+        }
+    }
+    // base: [alpha0; a0] = -IA0^-1 p0
+    f3 pN = ld3(&L.p[0][0]) + cN, pF = ld3(&L.p[0][3]) + cF;
+    float p0[6] = {pN.x, pN.y, pN.z, pF.x, pF.y, pF.z};
+    if (FACTOR) {
+        float* IA = L.IA[0];
+        float A[6], B[9], C[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) { A[i] = IA[i] + cA[i]; C[i] = IA[15 + i] + cC[i]; }
+#pragma unroll
+        for (int i = 0; i < 9; i++) B[i] = IA[6 + i] + cB[i];
+        float G[6][6];
+        G[0][0] = A[0]; G[0][1] = A[1]; G[0][2] = A[2]; G[1][1] = A[3]; G[1][2] = A[4]; G[2][2] = A[5];
+        G[1][0] = A[1]; G[2][0] = A[2]; G[2][1] = A[4];
+        G[3][3] = C[0]; G[3][4] = C[1]; G[3][5] = C[2]; G[4][4] = C[3]; G[4][5] = C[4]; G[5][5] = C[5];
+        G[4][3] = C[1]; G[5][3] = C[2]; G[5][4] = C[4];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) { G[i][3 + j] = B[3 * i + j]; G[3 + j][i] = B[3 * i + j]; }
+        // Gauss-Jordan inverse of the SPD 6x6 (no pivoting)
+        float V[6][6];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = 0; j < 6; j++) V[i][j] = (i == j) ? 1.f : 0.f;
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            float piv = 1.0f / G[k][k];
+#pragma unroll
+            for (int j = 0; j < 6; j++) { G[k][j] *= piv; V[k][j] *= piv; }
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                if (i != k) {
+                    float f = G[i][k];
+#pragma unroll
+                    for (int j = 0; j < 6; j++) { G[i][j] -= f * G[k][j]; V[i][j] -= f * V[k][j]; }
+                }
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int j = 0; j < 6; j++) L.Inv0[6 * i + j] = V[i][j];
+        }
+        float a0[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 6; j++) s -= V[i][j] * p0[j];
+            a0[i] = s;
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) L.acc0[i] = a0[i];
+        }
+    } else {
+        float a0[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 6; j++) s -= L.Inv0[6 * i + j] * p0[j];
+            a0[i] = s;
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) L.acc0[i] = a0[i];
+        }
+    }
+    lds_sync();
+    if (!FACTOR) return;   // the sensor pass only needs the base acceleration (acc0)
+    // forward sweep: joint accelerations
+    f3 al = ld3(&L.acc0[0]), a = ld3(&L.acc0[3]);
+    for (int b = 1; b <= N; b++) {
+        f3 r = ld3(L.r[b]);
+        f3 ap = a + cross(al, r) + ld3(&L.zeta[b][3]);
+        f3 alp = al + ld3(&L.zeta[b][0]);
+        float qdd = (L.u[b] - (dot(ld3(L.Ua[b]), alp) + dot(ld3(L.Ub[b]), ap))) * L.Dinv[b];
+        al = alp + ld3(L.ax[b]) * qdd;
+        a = ap;
+        if (lane == 0) L.qdd[b - 1] = qdd;
+    }
+    lds_sync();
+}
+
+// True when the substep whose solve just produced `dv` (this lane's component of the velocity
+// change) can be the LAST of its env-step, i.e. when obs[55] (the joint-0 force sensor, the second
+// ABA pass) can be observed: the servo error after it is within the tolerance, or the counter
+// reaches its cap, or the mean height can cross its threshold.  The first two are evaluated
+// exactly as the loop does (with a 1e-3 safety factor on the tolerance); for the third, no
+// sampled point can move further in one substep than dt * (|v| + L_chain * (|omega| + sum |qd|)):
+// rigid rotations about the base and the joints.
+template <class LT>
+__device__ __forceinline__ bool sensor_pass_needed(LT& L, const DevModel& M, int lane, float dv, const SensorHint& hint) {
+    constexpr int N = LT::kN;
+    constexpr int ND = N + 6;
+    if (hint.always) return true;
+    const float dt = M.dt;
+    float e = 0.f, wgt = 0.f;
+    if (lane < ND) {
+        const float vold = lane < 6 ? L.base()[7 + lane] : L.qd()[lane - 6];
+        const float x = fminf(fmaxf(vold + dv, -M.max_vel), M.max_vel);
+        if (lane >= 6) e = L.targets[lane - 6] - (L.q()[lane - 6] + dt * x);
+        wgt = fabsf(x) * ((lane >= 3 && lane < 6) ? 1.0f : 0.0639f * (N + 2));
+    }
+    const float se = wave_sum<64>(e * e);
+    const float reach = dt * wave_sum<64>(wgt);
+    const float tol = M.servo_tol * 1.001f;
+    const bool sensor = !(se > tol * tol) || hint.counter_next > M.max_counter || !(hint.h_prev + reach < M.height_thr);
+    return __builtin_amdgcn_readfirstlane(sensor ? 1 : 0) != 0;
+}
+
+}  // namespace snk

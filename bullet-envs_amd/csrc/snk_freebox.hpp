@@ -1,7 +1,11 @@
 // snk_freebox.hpp -- obstacle 2: the box of snake/block.urdf as the reference loads it (snake_gait_test.py:51,
 // Snake.add_obstacle snake.py:83-84: useFixedBase=0), a FREE 200-kg body resting on the ground.
-// Included behind snk_pgs_v2.hpp (it uses the manifold helpers defined there); used by the streamed-row kernels only.
+// Uses the manifold helpers of snk_contacts.hpp; used by the streamed-row solve only (snk_pgs_v1.hpp).
 #pragma once
+#include "snk_contacts.hpp"
+#include "snk_lds.hpp"
+#include "snk_model.hpp"
+#include "snk_wave.hpp"
 
 namespace snk {
 

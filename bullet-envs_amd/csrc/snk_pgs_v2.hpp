@@ -41,15 +41,21 @@
 // itself is evaluated directly in the (half, d) layout from the contact point and the
 // per-lane joint axis/origin.
 //
-// Restates the same Bullet steps as v1's build_rows_v1/pgs_v1 (snk_device.hpp); the order
+// Restates the same Bullet steps as v1's build_rows_v1/pgs_v1 (snk_pgs_v1.hpp); the order
 // of row updates is identical, so both versions track the oracle.
 #pragma once
+#include "snk_contacts.hpp"
+#include "snk_dynamics.hpp"
+#include "snk_lds.hpp"
+#include "snk_model.hpp"
+#include "snk_selfcol.hpp"
+#include "snk_wave.hpp"
 
 namespace snk {
 
 // -DSNK_PROFILE: s_memtime stamps between the phases of substep_v2; the phase durations (ticks)
 // overwrite the motor-torque outputs of the substep (tools/profile_phases.py reads them).
-// (SNK_STAMP: snk_device.hpp)
+// (SNK_STAMP: snk_lds.hpp)
 
 // slot map (two rows per slot) and the layout of the accumulated impulses handed back in L.app
 constexpr int kSlotNormal = 0;    // 32 slots: contacts 2s (lower half), 2s+1 (upper half)
@@ -60,29 +66,6 @@ constexpr int kAppNormal = 16;    // app[16 + ci]          normal of contact ci
 constexpr int kAppFric = 80;      // app[80 + 2 ci + {0,1}] friction A / B of contact ci
 constexpr unsigned long long kLowMask = 0x00000000FFFFFFFFull;
 
-struct swap2 {
-    float a, b;
-};
-// v_permlane32_swap: returns a = [x.lo, y.lo], b = [x.hi, y.hi] (32-lane halves)
-__device__ __forceinline__ swap2 half_swap(float x, float y) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    swap2 o;
-    o.a = __uint_as_float(r[0]);
-    o.b = __uint_as_float(r[1]);
-    return o;
-}
-// sum over each 32-lane half; result valid in lane 31 (lower half) and lane 63 (upper half)
-__device__ __forceinline__ float half_reduce(float t) {
-    t = dpp_add<0xB1, 0xf>(t);
-    t = dpp_add<0x4E, 0xf>(t);
-    t = dpp_add<0x114, 0xf>(t);
-    t = dpp_add<0x118, 0xf>(t);
-    t = dpp_add<0x142, 0xa>(t);
-    return t;
-}
-__device__ __forceinline__ float rdlane(float x, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
-}
 // ------------------------------------------------------------------------------------
 // contacts of the current pose, written at their COMPACT index.
 //
@@ -98,299 +81,6 @@ __device__ __forceinline__ float rdlane(float x, int l) {
 // body's contact forces over the ranges of its cylinders).  At most 4 N contacts get rows (the register-resident
 // solve has that many slots): further manifold points are left out, in manifold order.
 // ------------------------------------------------------------------------------------
-// lowest rim point (x, y in the cylinder's frame) towards dl = world "down" in that frame
-__device__ __forceinline__ void rim_point(const DevModel& M, f3 dl, float& lx, float& ly) {
-    lx = 0.f; ly = 0.f;
-    if (M.hull_sides > 0) {
-        float best = -3.0e38f;
-        for (int s = 0; s < M.hull_sides; s++) {          // first maximum, the importer's vertex order
-            const float vx = M.hull_xy[s][0], vy = M.hull_xy[s][1];
-            const float val = dl.x * vx + dl.y * vy;
-            if (val > best) { best = val; lx = vx; ly = vy; }
-        }
-    } else {
-        const float rr = sqrtf(dl.x * dl.x + dl.y * dl.y);
-        if (rr > 1e-12f) { lx = M.cyl_r * dl.x / rr; ly = M.cyl_r * dl.y / rr; }
-    }
-}
-// world rotation of cylinder c's frame
-__device__ __forceinline__ void cyl_world_rot(const float* Rb, const float* Rc, float* Rw) {
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            Rw[3 * i + j] = Rb[3 * i] * Rc[j] + Rb[3 * i + 1] * Rc[3 + j] + Rb[3 * i + 2] * Rc[6 + j];
-}
-// friction directions (0,-1,0), (1,0,0) scaled anisotropically in the link's axes: d' = Rw diag(aniso) Rw^T d
-__device__ __forceinline__ void friction_dirs(const DevModel& M, const float* Rw, f3& dA, f3& dB) {
-    const f3 a = mk3(M.aniso[0], M.aniso[1], M.aniso[2]);
-    const f3 l1 = mulRtv(Rw, mk3(0.f, -1.f, 0.f));
-    const f3 l2 = mulRtv(Rw, mk3(1.f, 0.f, 0.f));
-    dA = mulRv(Rw, mk3(l1.x * a.x, l1.y * a.y, l1.z * a.z));
-    // friction_directions 1: the second tangent is a zero vector -- its row comes out J = 0, M^-1 J^T = 0, den = 0 and
-    // resolves to nothing in either friction form (the cone over (x, 0) is the box bound of the one row)
-    dB = mulRv(Rw, mk3(l2.x * a.x, l2.y * a.y, l2.z * a.z)) * M.fricB;
-}
-
-// One cached manifold point: the point on the link in the LINK's coordinates (cylinder frame + cyl_zoff along z),
-// the point on the ground in world coordinates (z = 0: the plane's), the refreshed distance, and the normal impulse
-// the point carried in the last substep (btManifoldPoint::m_appliedImpulse [U]; warm starting reads it).
-struct MPt {
-    f3 a, b;
-    float d, lam;
-};
-typedef float mf_v4 __attribute__((ext_vector_type(4)));
-// dst = c ? src : dst, field by field.  (A conditional struct assignment inside an unrolled `if (j == where)` chain gets
-// its stores merged into ONE store at a computed address, which puts the whole point cache into scratch memory: ~100
-// scratch round trips per substep, measured in the ISA of round 3's first build.)
-__device__ __forceinline__ void mpt_sel(MPt& dst, const MPt& src, bool c) {
-    dst.a.x = c ? src.a.x : dst.a.x; dst.a.y = c ? src.a.y : dst.a.y; dst.a.z = c ? src.a.z : dst.a.z;
-    dst.b.x = c ? src.b.x : dst.b.x; dst.b.y = c ? src.b.y : dst.b.y; dst.b.z = c ? src.b.z : dst.b.z;
-    dst.d = c ? src.d : dst.d; dst.lam = c ? src.lam : dst.lam;
-}
-__device__ __forceinline__ void f3_sel(f3& dst, f3 src, bool c) {
-    dst.x = c ? src.x : dst.x; dst.y = c ? src.y : dst.y; dst.z = c ? src.z : dst.z;
-}
-
-// btPersistentManifold::sortCachedPoints with gContactCalcArea3Points [U]: which cached point the new one replaces
-__device__ __forceinline__ int manifold_sort_cached(const MPt (&p)[4], const MPt& np) {
-    int mpi = -1;
-    float mp = np.d;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        if (p[i].d < mp) { mpi = i; mp = p[i].d; }
-    auto area = [](f3 a1, f3 a0, f3 b1, f3 b0) { const f3 c = cross(a1 - a0, b1 - b0); return dot(c, c); };
-    float res[4] = {0.f, 0.f, 0.f, 0.f};
-    if (mpi != 0) res[0] = area(np.a, p[1].a, p[3].a, p[2].a);
-    if (mpi != 1) res[1] = area(np.a, p[0].a, p[3].a, p[2].a);
-    if (mpi != 2) res[2] = area(np.a, p[0].a, p[3].a, p[1].a);
-    if (mpi != 3) res[3] = area(np.a, p[0].a, p[2].a, p[1].a);
-    int best = 0;
-    float bv = fabsf(res[0]);
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        if (fabsf(res[i]) > bv) { bv = fabsf(res[i]); best = i; }
-    return best;
-}
-
-// The manifold of this lane's cylinder (n cached points p[0 .. n-1], registers), updated for the current pose -- see
-// the oracle's find_contacts_manifold for the Bullet calls restated: a link's collider is a btCompoundShape, so
-// btCompoundCollisionAlgorithm first REFRESHES the child's manifold from the new pose (positions, distances, and the
-// removal of points that lifted off or drifted: refreshContactPoints), then the child's convex-plane algorithm adds
-// this step's support point (getCacheEntry / replaceContactPoint / addManifoldPoint with sortCachedPoints, which sees
-// the refreshed distances) [U].  Returns the new number of cached points; their world positions on the link and
-// distances in wa / p[].d.  Everything is a select (mpt_sel): the cache stays in registers.
-__device__ __forceinline__ int manifold_core(const DevModel& M, int n, MPt (&p)[4], const float* Rw, f3 centre, f3 dl,
-                                             f3 (&wa)[4]) {
-    n = n < 0 ? 0 : (n > 4 ? 4 : n);
-    const float thr = M.break_thr;
-    const f3 zoff = mk3(0.f, 0.f, M.cyl_zoff);
-    // refresh from the current pose, then drop what lifted off or drifted (last to first, the last one moves in)
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        wa[j] = centre + mulRv(Rw, p[j].a - zoff);
-        p[j].d = wa[j].z - p[j].b.z;
-    }
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        bool drop = !(p[j].d <= thr);
-        {
-            const float dx = p[j].b.x - wa[j].x, dy = p[j].b.y - wa[j].y, dz = p[j].b.z - (wa[j].z - p[j].d);
-            drop = drop || (dx * dx + dy * dy + dz * dz > thr * thr);
-        }
-        drop = drop && j < n;
-        const int last = n - 1;
-        MPt pl = p[0];
-        f3 wl = wa[0];
-#pragma unroll
-        for (int k = 1; k < 4; k++) { mpt_sel(pl, p[k], k == last); f3_sel(wl, wa[k], k == last); }
-        mpt_sel(p[j], pl, drop && j != last);
-        f3_sel(wa[j], wl, drop && j != last);
-        n = drop ? n - 1 : n;
-    }
-    // the new point: support vertex towards the plane (+ margin along that direction)
-    f3 sv;
-    if (M.hull_sides > 0) {
-        float best = -3.0e38f;
-        sv = mk3(0.f, 0.f, 0.f);
-        for (int k = 0; k < 2 * M.hull_sides; k++) {      // the importer's order: (+z, -z) of vertex 0, 1, ...
-            const f3 c = mk3(M.hull_xy[k >> 1][0], M.hull_xy[k >> 1][1], (k & 1) ? -M.cyl_hl : M.cyl_hl);
-            const float val = dot(dl, c);
-            if (val > best) { best = val; sv = c; }
-        }
-    } else {                                              // btCylinderShapeZ's support function [U]
-        const float rr = sqrtf(dl.x * dl.x + dl.y * dl.y);
-        sv = rr != 0.f ? mk3(M.cyl_r * dl.x / rr, M.cyl_r * dl.y / rr, 0.f) : mk3(M.cyl_r, 0.f, 0.f);
-        sv.z = dl.z < 0.f ? -M.cyl_hl : M.cyl_hl;
-    }
-    MPt np;
-    const f3 loc = sv + dl * M.margin;                    // in the cylinder's own (centred) frame
-    np.a = loc + zoff;
-    const f3 wnew = centre + mulRv(Rw, loc);
-    np.d = wnew.z;
-    np.b = mk3(wnew.x, wnew.y, 0.f);
-    np.lam = 0.f;
-    {
-        const bool add = np.d < thr;
-        int nearest = -1;
-        float shortest = thr * thr;
-        float lam_near = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const f3 d = p[j].a - np.a;
-            const float dd = dot(d, d);
-            const bool nr = j < n && dd < shortest;
-            shortest = nr ? dd : shortest; nearest = nr ? j : nearest; lam_near = nr ? p[j].lam : lam_near;
-        }
-        const int evict = manifold_sort_cached(p, np);
-        // replaceContactPoint keeps the cached point's applied impulse; a point that is added, or that evicts another
-        // one (addManifoldPoint -> sortCachedPoints), starts at zero [U]
-        np.lam = nearest >= 0 ? lam_near : 0.f;
-        const int where = nearest >= 0 ? nearest : (n < 4 ? n : evict);
-        n = (add && nearest < 0 && n < 4) ? n + 1 : n;
-#pragma unroll
-        for (int j = 0; j < 4; j++) { mpt_sel(p[j], np, add && j == where); f3_sel(wa[j], wnew, add && j == where); }
-    }
-    return n;
-}
-
-// Which of a cylinder's n cached points get rows when the environment holds more points than the solve has slots for
-// (`room` of them; Bullet has no such limit, snk_contact_overflow counts how often this build's is hit).  Every cylinder
-// ranks its points the way Bullet's own manifold reduction values them (sortCachedPoints: the deepest point, then
-// spread): first the deepest, second the one farthest from it (the other end cap), third the one that spans the
-// larger triangle with those two, then the last; ties go to the lower manifold index.  Slots are handed out in
-// passes: every cylinder's first point, in cylinder order, then every cylinder's second, ... until they are used up,
-// so a resting snake keeps one point per end cap of every cylinder before any cylinder keeps a third.  Lane =
-// cylinder; returns the lane's bit mask of kept points (the oracle's max_contacts mirrors the rule for the tests).
-__device__ __forceinline__ int manifold_keep_mask(int n, const MPt (&p)[4], int lane, int total, int room) {
-    if (total <= room) return (1 << n) - 1;
-    int rank[4] = {4, 4, 4, 4};
-    int p0 = 0, p1 = -1, p2 = -1;
-    {
-        float best = 3.0e38f;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            if (i < n && p[i].d < best) { best = p[i].d; p0 = i; }
-    }
-    f3 a0 = p[0].a;
-#pragma unroll
-    for (int i = 1; i < 4; i++) f3_sel(a0, p[i].a, i == p0);
-    {
-        float best = -1.f;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const f3 d = p[i].a - a0;
-            const float dd = dot(d, d);
-            if (i < n && i != p0 && dd > best) { best = dd; p1 = i; }
-        }
-    }
-    f3 a1 = p[0].a;
-#pragma unroll
-    for (int i = 1; i < 4; i++) f3_sel(a1, p[i].a, i == p1);
-    {
-        float best = -1.f;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const f3 c = cross(a1 - a0, p[i].a - a0);
-            const float cc = dot(c, c);
-            if (i < n && i != p0 && i != p1 && cc > best) { best = cc; p2 = i; }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) rank[i] = i == p0 ? 0 : (i == p1 ? 1 : (i == p2 ? 2 : 3));
-    int granted = 0;                       // passes in which this cylinder got a slot (monotone: once refused, refused)
-    int left = room;
-#pragma unroll
-    for (int pass = 0; pass < 4; pass++) {
-        const unsigned long long el = __ballot(n > pass);
-        const int before = __popcll(el & ((1ull << lane) - 1ull));
-        if (n > pass && before < left) granted = pass + 1;
-        left -= __popcll(el);
-        left = left < 0 ? 0 : left;
-    }
-    int mask = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        if (i < n && rank[i] < granted) mask |= 1 << i;
-    return mask;
-}
-
-// The streamed-row kernels keep the manifolds in global memory: mfc -> the cylinder's kMfFloats floats
-// [count, 3 pad, 4 x (a3, b.x, b.y, lambda)], read and written write-through (sc1): an env-step moves between waves at
-// substep boundaries, and the bytes must be where the next wave's loads look (same rule as the state record,
-// store_rec_through).
-__device__ __forceinline__ int manifold_load_global(const float* __restrict__ mfc, MPt (&p)[4]) {
-    mf_v4 v[7];
-    asm volatile(
-        "global_load_dwordx4 %0, %7, off sc1\n\t"
-        "global_load_dwordx4 %1, %7, off offset:16 sc1\n\t"
-        "global_load_dwordx4 %2, %7, off offset:32 sc1\n\t"
-        "global_load_dwordx4 %3, %7, off offset:48 sc1\n\t"
-        "global_load_dwordx4 %4, %7, off offset:64 sc1\n\t"
-        "global_load_dwordx4 %5, %7, off offset:80 sc1\n\t"
-        "global_load_dwordx4 %6, %7, off offset:96 sc1\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6])
-        : "v"(mfc)
-        : "memory");
-    float f[kMfFloats];
-#pragma unroll
-    for (int i = 0; i < 7; i++) { f[4 * i] = v[i].x; f[4 * i + 1] = v[i].y; f[4 * i + 2] = v[i].z; f[4 * i + 3] = v[i].w; }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        p[j].a = mk3(f[4 + 6 * j], f[5 + 6 * j], f[6 + 6 * j]);
-        p[j].b = mk3(f[7 + 6 * j], f[8 + 6 * j], 0.f);
-        p[j].lam = f[9 + 6 * j];
-        p[j].d = 0.f;
-    }
-    const int n = (int)f[0];
-    return n < 0 ? 0 : (n > 4 ? 4 : n);      // (manifold_core clamps as well; the count indexes registers here)
-}
-__device__ __forceinline__ void manifold_store_global(float* __restrict__ mfc, int n, const MPt (&p)[4]) {
-    mf_v4 v[7];
-    float f[kMfFloats];
-    f[0] = (float)n; f[1] = 0.f; f[2] = 0.f; f[3] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        f[4 + 6 * j] = p[j].a.x; f[5 + 6 * j] = p[j].a.y; f[6 + 6 * j] = p[j].a.z;
-        f[7 + 6 * j] = p[j].b.x; f[8 + 6 * j] = p[j].b.y; f[9 + 6 * j] = p[j].lam;
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) { v[i].x = f[4 * i]; v[i].y = f[4 * i + 1]; v[i].z = f[4 * i + 2]; v[i].w = f[4 * i + 3]; }
-    asm volatile(
-        "global_store_dwordx4 %7, %0, off sc1\n\t"
-        "global_store_dwordx4 %7, %1, off offset:16 sc1\n\t"
-        "global_store_dwordx4 %7, %2, off offset:32 sc1\n\t"
-        "global_store_dwordx4 %7, %3, off offset:48 sc1\n\t"
-        "global_store_dwordx4 %7, %4, off offset:64 sc1\n\t"
-        "global_store_dwordx4 %7, %5, off offset:80 sc1\n\t"
-        "global_store_dwordx4 %7, %6, off offset:96 sc1"
-        :
-        : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(mfc)
-        : "memory");
-}
-
-// exclusive prefix sum over lanes of a small count (0..7), wave-uniform total in `total`
-__device__ __forceinline__ int lane_prefix3(int cnt, int lane, int& total) {
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const unsigned long long b0 = __ballot(cnt & 1), b1 = __ballot(cnt & 2), b2 = __ballot(cnt & 4);
-    total = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
-    return __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below);
-}
-
-// Where cylinder `lane`'s points start in the compact contact list: the exclusive prefix of the kept counts in the ORDER THE
-// SOLVER SWEEPS THE MANIFOLDS (snk_params::contact_order; 0 = cylinder = link order, the prefix over the lanes as they are).
-// Otherwise position r fetches the count of the cylinder that sits there (DevModel::cyl_at), the prefix runs over
-// positions, and every cylinder fetches its own from its position (cyl_rank): two ds_bpermute per substep.
-// (wave-uniform branch: the model sits in constant memory)
-__device__ __forceinline__ int manifold_base(const DevModel& M, int ncyl, int kept, int lane, int& total) {
-    if (M.contact_order == 0) return lane_prefix3(kept, lane, total);
-    const int at = lane < ncyl ? (int)M.cyl_at[lane] : lane;
-    const int rk = lane < ncyl ? (int)M.cyl_rank[lane] : lane;
-    const int kept_r = __shfl(kept, at);
-    const int base_r = lane_prefix3(kept_r, lane, total);
-    return __shfl(base_r, rk);
-}
 
 // Contacts with the obstacle box for the register-resident solve (lane = cylinder, the two-tier GJK of
 // snk_selfcol.hpp): at most LT::kObs of them on this solve (a substep with more goes through the streamed-row solve,
@@ -607,72 +297,6 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
     return np_ + n_ob;
 }
 
-// The same persistent-manifold contacts for the streamed-row solve (chains up to 32 links: one cylinder per lane):
-// the manifolds in global memory, geometry records written at the COMPACT index (clist is the identity), at most NC
-// ground contacts (the same rule for which points keep their rows, the same counters).  geo[19] of a record: the
-// impulse its normal row starts from (warm starting).
-template <class LT>
-__device__ int find_contacts_manifold_v1(LT& L, const DevModel& M, int lane, float* __restrict__ rows, float* __restrict__ mf,
-                                         unsigned long long* __restrict__ ovf) {
-    constexpr int N = LT::kN;
-    static_assert(2 * N <= 64, "one cylinder per lane");
-    int cnt = 0;
-    MPt p[4];
-    f3 wa[4];
-    float Rw[9];
-    const int c = lane < 2 * N ? lane : 0;
-    const int b = (c + 1) >> 1;
-    if (lane < 2 * N) {
-        const float* Rb = L.R[b];
-        cyl_world_rot(Rb, M.cyl_R[c], Rw);
-        const f3 dl = mk3(-Rw[6], -Rw[7], -Rw[8]);
-        const f3 centre = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[c]));
-        const int n0 = manifold_load_global(mf + (size_t)c * kMfFloats, p);
-        cnt = manifold_core(M, n0, p, Rw, centre, dl, wa);
-    }
-    int total;
-    (void)lane_prefix3(cnt, lane, total);
-    const int room = LT::NC;
-    const int mask = manifold_keep_mask(cnt, p, lane, total, room);
-    const int kept = __popc(mask);
-    int tk;
-    const int base = manifold_base(M, 2 * N, kept, lane, tk);
-    if (total > room && lane == 0) {
-        atomicAdd(ovf, 1ull);
-        atomicAdd(ovf + 1, (unsigned long long)(total - tk));
-    }
-    if (lane < 2 * N) {
-        // the sensor pass finds a body's contacts through its cylinders: [first compact index, count] of cylinder `lane`
-        // (the slot -> contact table of the stateless model is not used in this one; its array holds these pairs) and,
-        // in the upper bits of the count word, which cached points they are (for the impulses' way back into the cache)
-        L.cidx[2 * lane] = base;
-        L.cidx[2 * lane + 1] = kept | (mask << 8);
-        f3 dA, dB;
-        friction_dirs(M, Rw, dA, dB);
-        int idx = base;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const bool on = (mask >> j) & 1;
-            if (!on) p[j].lam = 0.f;
-            if (on) {
-                float* geo = rows + LT::kGeoOff + (size_t)idx * LT::kGeo;
-                st3(geo, wa[j]);
-                geo[3] = p[j].d;
-                st3(geo + 4, dA);
-                st3(geo + 7, dB);
-                st3(geo + 10, mk3(0.f, 0.f, 1.f));
-                st3(geo + 13, mk3(0.f, 0.f, 0.f));
-                geo[16] = (float)b; geo[17] = -1.0f; geo[18] = 1.0f;
-                geo[19] = M.warm_start ? p[j].lam * M.warm_factor : 0.f;
-                L.clist[idx] = idx;
-                idx++;
-            }
-        }
-        manifold_store_global(mf + (size_t)c * kMfFloats, cnt, p);
-    }
-    return tk;
-}
-
 // ------------------------------------------------------------------------------------
 // one batch of rows, lane = row: M^-1 J^T by the ABA delta sweeps
 // (btMultiBody::calcAccelerationDeltasMultiDof [U]) plus the row's denominator and
@@ -885,11 +509,6 @@ __device__ __forceinline__ void load_slots8(LT& L, const LaneK& K, int count, in
                           RJ[DST + BASE + i], RM[DST + BASE + i], wsum);
         cur = nxt;
     }
-}
-
-// old with lane l replaced by a wave-uniform value (once per substep: a select is fine)
-__device__ __forceinline__ float wrlane(float old, float v_uniform, int l) {
-    return ((int)threadIdx.x == l) ? v_uniform : old;
 }
 
 // DPP sum over each 32-lane half of %[t]; results in lane 31 / 63.  A dependent DPP read needs

@@ -1,5 +1,5 @@
 // snk_selfcol.hpp -- link-link (self) collision of the snake's cylinders: what URDF_USE_SELF_COLLISION
-// (/root/reference/snake.py:93) switches on in PyBullet [U].  SURVEY.md 8(f)-2.
+// (snake.py:93) switches on in PyBullet [U].  SURVEY.md 8(f)-2.
 //
 // Every pair of cylinder links except direct parent-child pairs (consecutive cylinders of the chain; the flag's
 // default excludes a link's parent) is tested each substep:
@@ -19,6 +19,9 @@
 // command range (|target| <= 30 deg: 15 mm of clearance, tools/self_collision_clearance.py), but a snake bent further
 // (a larger scaling_factor, states set from outside) does fold onto itself.
 #pragma once
+#include "snk_lds.hpp"
+#include "snk_model.hpp"
+#include "snk_wave.hpp"
 
 namespace snk {
 

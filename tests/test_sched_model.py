@@ -1,4 +1,4 @@
-"""A host model of the step kernel's in-launch schedule (snk_device.hpp: Sched, sched_pop, sched_push): the same
+"""A host model of the step kernel's in-launch schedule (snk_sched.hpp: Sched, sched_pop, sched_push): the same
 policy -- ticket FIFO filled longest-first, slices of `quantum` substeps, carry on unless a queued env-step has more
 substeps left -- replayed on the substep counts a real launch had (tests/golden/bench_substeps.npy: four launches of
 bench.py's workload on an MI355X, written by tools/balance_dump.py).  Pins the two claims DESIGN.md 4 makes about

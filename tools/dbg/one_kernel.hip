@@ -1,5 +1,5 @@
 // One instantiation of the step kernel by itself (tools/dbg/loop_spills.sh): -DKN=16 -DKV=true | -DKN=16 -DKV=false | -DKN=32 -DKV=false
-// (-DKR=1 | 2: a solver-rules variant, snk_device.hpp: LdsFor)
+// (-DKR=1 | 2: a solver-rules variant, snk_lds.hpp: LdsFor)
 #include <hip/hip_runtime.h>
 #include "../../include/snk.h"
 #include "../../bullet-envs_amd/csrc/snk_device.hpp"

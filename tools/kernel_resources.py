@@ -10,14 +10,22 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]
+
+
+def device_asm(root, args, out):
+    """Compiles <root>/bullet-envs_amd/csrc/snk_api.hip device-only to assembly with the product's own flags (that tree's
+    `build.py --print-flags`) plus `args`; returns the command.  (tools/same_isa.py compares two trees with it.)"""
+    pkg = os.path.join(root, "bullet-envs_amd")
+    flags = subprocess.check_output([sys.executable, os.path.join(pkg, "build.py"), "--print-flags"], text=True).split()
+    cmd = ["/opt/rocm/bin/hipcc"] + flags + list(args) + ["--offload-device-only", "-S", "csrc/snk_api.hip", "-o", out]
+    subprocess.run(cmd, cwd=pkg, check=True, stderr=subprocess.DEVNULL)
+    return cmd
 
 
 def main():
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "snk.s")
-        cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + sys.argv[1:] + ["--offload-device-only", "-S", "csrc/snk_api.hip", "-o", out]
-        subprocess.run(cmd, cwd=os.path.join(ROOT, "bullet-envs_amd"), check=True, stderr=subprocess.DEVNULL)
+        cmd = device_asm(ROOT, sys.argv[1:], out)
         lines = open(out).read().split("\n")
     print("# " + " ".join(cmd[:-2]))
     print("%-46s %6s %6s %9s %5s" % ("kernel", "VGPRs", "SGPRs", "scratch B", "occ"))

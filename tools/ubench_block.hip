@@ -34,6 +34,7 @@
 #include "../bullet-envs_amd/csrc/snk_device.hpp"
 
 struct MockLds {
+    static constexpr int kNCO = 0;      // motors16: the default motor order (snk_params::noncontact_order 0)
     float MmS[16][4];
 };
 

@@ -1,6 +1,6 @@
 // The streamed-row solve's contact steps on REGISTER-HELD rows (no loads), priced before building anything into pgs_v1
 // (VERDICT r5 item 2).  Today's steps -- row_step_normal2 (two normals per step, one coupling scalar) and row_step_cone (one
-// contact's friction pair) of snk_device.hpp, the real ones -- against the four-row forms:
+// contact's friction pair) of snk_pgs_v1.hpp, the real ones -- against the four-row forms:
 //   row_step_normal4   four normals' dots from ONE delta-v, their four reductions interleaved (every DPP add is the other
 //                      three's wait state: no s_nop left), rows 2..4 corrected by six coupling scalars
 //                      c_ij = (J_i / den_i) . (M^-1 J_j^T)  -- exactly the sequential sweep, as the 16-link quad_step
