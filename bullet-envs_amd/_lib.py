@@ -87,6 +87,7 @@ SYMBOLS = {
     "snk_debug_set_tickets": (C.c_int, [_vp, C.c_uint32]),
     "snk_debug_raise_alarm": (C.c_int, [_vp]),
     "snk_debug_noncontact_order": (C.c_int, [C.c_int32, _I32]),
+    "snk_debug_reach_bound": (C.c_int, [C.POINTER(SnkParams), _F]),
     "snk_selftest": (C.c_int, [C.c_int32]),
     "snk_timing_enable": (C.c_int, [_vp, C.c_int32]),
     "snk_timing_read": (C.c_int, [_vp, _D, _I32]),
@@ -156,6 +157,15 @@ def noncontact_order(n_modules):
     out = np.zeros(2 * int(n_modules), np.int32)
     check(load().snk_debug_noncontact_order(int(n_modules), out.ctypes.data_as(_I32)), "snk_debug_noncontact_order")
     return out
+
+
+def reach_bound(params=None, **over):
+    """What the kernels' bound on one substep's change of the mean height is made of (snk_debug_reach_bound):
+    (longest joint-to-joint offset [m], |COM of the base link| [m], both rounded up by 1.001; fixed slack [m])."""
+    p = params if params is not None else default_params(**over)
+    out = np.zeros(3, np.float32)
+    check(load().snk_debug_reach_bound(C.byref(p), out.ctypes.data_as(_F)), "snk_debug_reach_bound")
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 def fptr(a):

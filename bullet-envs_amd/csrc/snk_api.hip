@@ -336,6 +336,8 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     // SNK_FORCE_STREAMED=1 (diagnostics, tests): the streamed-row kernels for a 16-link handle too
     h->v2 = h->n == 16 && getenv("SNK_FORCE_STREAMED") == nullptr && p->obstacle != 2;      // (a free box: six more
                                                                                             //  components, streamed rows)
+    // SNK_MOTORS_APART=1 (cross-checks): the motor rows never ride in the normals' batch (snk_pgs_v2.hpp: substep_v2)
+    h->D.motors_apart = getenv("SNK_MOTORS_APART") != nullptr ? 1 : 0;
     size_t rf = 0, z0 = 0, zn = 0, m0 = 0, m1 = 0;      // the layout of a block of streamed constraint rows (below)
     int rc = dispatch(h, [&](auto k) {
         using LR = snk::Lds<decltype(k)::N, false>;
@@ -823,6 +825,18 @@ int snk_debug_noncontact_order(int32_t n_modules, int32_t* out) {
     if (n_modules == 16) return write(snk::NoncontactOrder<16>::tab);
     if (n_modules == 32) return write(snk::NoncontactOrder<32>::tab);
     return fail("snk_debug_noncontact_order: n_modules must be 16 or 32");
+}
+
+int snk_debug_reach_bound(const snk_params* p, float out[3]) {
+    if (!p || !out) return fail("snk_debug_reach_bound: null argument");
+    if (p->n_modules != 16 && p->n_modules != 32) return fail("snk_debug_reach_bound: n_modules must be 16 or 32");
+    // (the models are large: not on the stack)
+    std::vector<snk::HostModel> H(1);
+    std::vector<snk::DevModel> D(1);
+    snk::build_host_model(*p, H[0]);
+    snk::build_dev_model(*p, H[0], D[0]);
+    out[0] = D[0].reach_l; out[1] = D[0].reach_hb; out[2] = snk::kReachSlack;
+    return 0;
 }
 
 int snk_selftest(int32_t device) {

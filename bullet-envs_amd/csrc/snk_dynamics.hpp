@@ -326,9 +326,15 @@ __device__ void aba_main(LT& L, const DevModel& M, int lane) {
 // change) can be the LAST of its env-step, i.e. when obs[55] (the joint-0 force sensor, the second
 // ABA pass) can be observed: the servo error after it is within the tolerance, or the counter
 // reaches its cap, or the mean height can cross its threshold.  The first two are evaluated
-// exactly as the loop does (with a 1e-3 safety factor on the tolerance); for the third, no
-// sampled point can move further in one substep than dt * (|v| + L_chain * (|omega| + sum |qd|)):
-// rigid rotations about the base and the joints.
+// exactly as the loop does (with a 1e-3 safety factor on the tolerance).  For the third, the height
+// is the MEAN z of N + 1 points: the base link's COM (o[0] + R0 hbase) and the joint origins o[1..N],
+// with o[b] = o[b-1] + R[b-1] pfix[b].  One substep moves o[0] by dt v, turns the base by at most
+// dt |omega| and joint j by dt |x_j|; a joint turns only the origins behind it, about an axis through
+// o[j], and o[k] is at most (k - j) l from there (l = max_b |pfix[b]|: rigid distances).  So
+//   |d mean z| <= dt ( |v|_1 + |omega|_1 (|hbase| + l N(N+1)/2) / (N+1)
+//                      + sum_j |x_j| l (N-j)(N-j+1) / (2 (N+1)) )  + kReachSlack,
+// each lane's weight in closed form from its index and the model's two scalars (no table: a vector
+// load here would sit on every substep's chain).  DESIGN.md 4.
 template <class LT>
 __device__ __forceinline__ bool sensor_pass_needed(LT& L, const DevModel& M, int lane, float dv, const SensorHint& hint) {
     constexpr int N = LT::kN;
@@ -340,10 +346,13 @@ __device__ __forceinline__ bool sensor_pass_needed(LT& L, const DevModel& M, int
         const float vold = lane < 6 ? L.base()[7 + lane] : L.qd()[lane - 6];
         const float x = fminf(fmaxf(vold + dv, -M.max_vel), M.max_vel);
         if (lane >= 6) e = L.targets[lane - 6] - (L.q()[lane - 6] + dt * x);
-        wgt = fabsf(x) * ((lane >= 3 && lane < 6) ? 1.0f : 0.0639f * (N + 2));
+        const int m = N + 5 - lane;      // lanes >= 6: joint j = lane - 5 has m = N - j joint origins behind it
+        const float arm = lane < 3 ? (M.reach_hb + M.reach_l * (0.5f * N * (N + 1))) * (1.0f / (N + 1))
+                                   : (lane < 6 ? 1.0f : M.reach_l * ((float)(m * (m + 1)) * (0.5f / (N + 1))));
+        wgt = fabsf(x) * arm;
     }
     const float se = wave_sum<64>(e * e);
-    const float reach = dt * wave_sum<64>(wgt);
+    const float reach = dt * wave_sum<64>(wgt) + kReachSlack;
     const float tol = M.servo_tol * 1.001f;
     const bool sensor = !(se > tol * tol) || hint.counter_next > M.max_counter || !(hint.h_prev + reach < M.height_thr);
     return __builtin_amdgcn_readfirstlane(sensor ? 1 : 0) != 0;

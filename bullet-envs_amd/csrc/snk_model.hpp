@@ -80,7 +80,14 @@ struct DevModel {
     // split-impulse threshold, contact_erp (m_erp2) at or below it)
     float erp_shallow, erp_deep, erp_split;
     int noncontact_order, contact_erp_rule;   // the switches themselves (snk_device.hpp: rules_variant picks the kernels)
+    // sensor_pass_needed's bound on the mean height's motion (snk_dynamics.hpp): reach_l = the longest joint-to-joint
+    // offset max_b |pfix[b]|, reach_hb = |hbase|, each rounded up by 1.001 (snk_debug_reach_bound reads them back)
+    float reach_l, reach_hb;
+    int motors_apart;                    // SNK_MOTORS_APART=1 at snk_create: the motor rows always get a batch of their own (snk_pgs_v2.hpp)
 };
+// the fixed part of that bound [m]: ten times the float32 round-off of the forward kinematics of a 1.1 m chain
+// (17 x 6e-8 x 1.1 m), which is what separates the computed mean height from the rigid motion the bound is about
+constexpr float kReachSlack = 1e-5f;
 
 // btAlignedObjectArray::quickSort (Hoare partition, pivot = the middle element, `i <= j` swap) on LEN equal keys, restated:
 // every partition reverses its range and recurses into the two halves.  perm[position] = the element that ends there.
@@ -432,6 +439,14 @@ inline void build_dev_model(const snk_params& P, const HostModel& H, DevModel& D
     }
     D.m_root = (float)H.m_root;
     for (int i = 0; i < 3; i++) { D.zbase[i] = (float)H.zbase[i]; D.hbase[i] = (float)H.hbase[i]; }
+    {
+        double l = 0.0;
+        for (int b = 1; b <= n; b++)
+            l = std::fmax(l, std::sqrt(H.pfix[b][0] * H.pfix[b][0] + H.pfix[b][1] * H.pfix[b][1] + H.pfix[b][2] * H.pfix[b][2]));
+        const double hb = std::sqrt(H.hbase[0] * H.hbase[0] + H.hbase[1] * H.hbase[1] + H.hbase[2] * H.hbase[2]);
+        D.reach_l = (float)(1.001 * l);
+        D.reach_hb = (float)(1.001 * hb);
+    }
 }
 
 }  // namespace snk

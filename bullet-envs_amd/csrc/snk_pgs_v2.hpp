@@ -303,6 +303,11 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
 // right-hand side.  KIND 0 motor (-> L.Mm, kept for the limit rows), 1 normal (contact = lane),
 // 4 friction pairs of 32 contacts: lane -> contact base + (lane & 31), direction lane >> 5
 // (A in staging rows 0..31, B in rows 32..63, so one pass over the slots fills both halves).
+// KIND 5 is KIND 1 with the sixteen motor rows riding in lanes 48..63, for a substep with at most 48 contacts: the sweeps
+// are serial chains whose cost does not depend on how many lanes are active, so the motors cost nothing there instead
+// of a batch (and a barrier) of their own.  `motor` is then a property of the lane: lane 48 + j does what lane j of
+// KIND 0 does -- the same operations in the same order, into L.Mm[j] / L.MmS[j] --, lanes < nc what they do in KIND 1,
+// the lanes in between nothing.  (SNK_MOTORS_APART=1 keeps the two batches apart: tests/test_gpu_motor_batch.py.)
 // Staging row layout: [0..21] M^-1 J^T, [22] rhs impulse, [23] denominator, [24] 1/denominator.
 // ------------------------------------------------------------------------------------
 // the wave-uniform constants one body contributes to a delta sweep
@@ -320,19 +325,22 @@ __device__ __forceinline__ BodyK load_body_k(LT& L, int b) {
 template <class LT, int KIND>
 __device__ void build_batch_v2(LT& L, const DevModel& M, int lane, int nc, int base = 0) {
     constexpr int N = LT::kN;
+    constexpr int kMotorLane0 = KIND == 5 ? 64 - N : 0;        // the lane of motor 0
+    constexpr bool NORMAL = KIND == 1 || KIND == 5;
     const int ci = KIND == 4 ? base + (lane & 31) : lane;      // contact (or motor) of this lane
-    if (ci < (KIND == 0 ? N : nc)) {
-        const bool motor = KIND == 0;
+    const bool motor = KIND == 0 || (KIND == 5 && lane >= kMotorLane0);
+    const int mj = motor ? lane - kMotorLane0 : 0;             // its joint, for a motor row
+    if (KIND == 0 ? ci < N : (motor || ci < nc)) {
         int k;
         f3 P = mk3(0, 0, 0), d = mk3(0, 0, 0);
-        float* Mrow = motor ? L.Mm[lane] : L.stM[lane];
+        float* Mrow = motor ? L.Mm[mj] : L.stM[lane];
         if (motor) {
-            k = lane + 1;
+            k = mj + 1;
         } else {
             k = L.ccbody[ci];
             P = ld3(L.ccP[ci]);
             // a ground contact's normal is +z, the obstacle's contacts (behind the nplane ground contacts) carry theirs
-            d = KIND == 1 ? (ci < L.nplane ? mk3(0.f, 0.f, 1.f) : ld3(L.obn[ci - L.nplane])) : ld3(L.cdir[L.ccds[ci]][lane >> 5]);
+            d = NORMAL ? (ci < L.nplane ? mk3(0.f, 0.f, 1.f) : ld3(L.obn[ci - L.nplane])) : ld3(L.cdir[L.ccds[ci]][lane >> 5]);
         }
         f3 pN = mk3(0, 0, 0), pF = mk3(0, 0, 0);
         // Both sweeps are serial chains over the bodies, and every body's constants sit at addresses that depend on no
@@ -403,11 +411,11 @@ __device__ void build_batch_v2(LT& L, const DevModel& M, int lane, int nc, int b
         }
         float dinv = den > 1.1920929e-7f ? 1.0f / den : 0.f;
         float target;
-        if (KIND == 0) {
-            float cur = L.qd()[lane];
-            float want = M.kp * (L.targets[lane] - L.q()[lane]) * M.inv_dt + cur + M.kd * (0.f - cur);
+        if (motor) {
+            float cur = L.qd()[mj];
+            float want = M.kp * (L.targets[mj] - L.q()[mj]) * M.inv_dt + cur + M.kd * (0.f - cur);
             target = want - cur;
-        } else if (KIND == 1) {
+        } else if (NORMAL) {
             float pen = L.ccdist[lane] + M.slop;
             float erp = M.contact_erp;
             if constexpr (LT::kERP) erp = pen > M.erp_split ? M.erp_shallow : M.erp_deep;     // contact_erp_rule
@@ -415,7 +423,7 @@ __device__ void build_batch_v2(LT& L, const DevModel& M, int lane, int nc, int b
         } else {
             target = -rv;
         }
-        float* S = motor ? L.MmS[lane] : &L.stM[lane][22];
+        float* S = motor ? L.MmS[mj] : &L.stM[lane][22];
         S[0] = target * dinv;
         S[1] = den;
         S[2] = dinv;
@@ -1168,7 +1176,12 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
         const float mu_ob = fminf(M.mu_link * M.mu_obs, 10.0f);
         ms.fJo = sgpr(mu_ob > 0.f ? 1.0f / mu_ob : 0.f); ms.fMo = sgpr(mu_ob > 0.f ? mu_ob : 0.f);
         ms.nplane = __builtin_amdgcn_readfirstlane(L.nplane);
-        build_batch_v2<LT, 0>(L, M, lane, nc);
+        // With at most 48 contacts the motor rows ride in the idle lanes of the normals' batch below (build_batch_v2,
+        // KIND 5) and this batch with its barrier falls away: nothing reads L.Mm / L.MmS before the motor registers are
+        // loaded behind that batch, and q, qd and the targets stay what they are until the solve is through.  The test is
+        // wave-uniform (nc and the model's switch are scalars) and made afresh at either place: no register crosses the
+        // friction batches for it.
+        if (nc > 64 - N || M.motors_apart) build_batch_v2<LT, 0>(L, M, lane, nc);
         SNK_STAMP(4)
         // friction pairs: two batches of 32 contacts x {A, B}
 #pragma unroll
@@ -1196,7 +1209,8 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
             SNK_STAMP(7)
         }
         SNK_STAMP(8)
-        build_batch_v2<LT, 1>(L, M, lane, nc);
+        if (nc > 64 - N || M.motors_apart) build_batch_v2<LT, 1>(L, M, lane, nc);
+        else build_batch_v2<LT, 5>(L, M, lane, nc);
         SNK_STAMP(9)
 #pragma unroll
         for (int s = 0; s < kSlotFric; s++) { RJ[kSlotNormal + s] = 0.f; RM[kSlotNormal + s] = 0.f; }
@@ -1449,8 +1463,9 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     // its env-step (obs[55] is not observable otherwise): the servo error after it is within the
     // tolerance, or the counter reaches its cap, or the mean height can cross its threshold.  The
     // first two are evaluated exactly as the loop does (with a 1e-3 safety factor on the
-    // tolerance); for the third, no sampled point can move further in one substep than
-    // dt * (|v| + L_chain * (|omega| + sum |qd|)): rigid rotations about the base and the joints.
+    // tolerance); for the third, the mean of the sampled heights cannot move further in one substep than
+    // sensor_pass_needed's bound (snk_dynamics.hpp): rigid rotations about the base and the joints, each joint
+    // with the lever arms of the points behind it.
     const bool sensor = sensor_pass_needed(L, M, lane, dv, hint);
     // delta-v crosses the sensor pass in LDS (a free column of the staging rows), not in a register -- round 4's first
     // answer to a build that lost its lanes 16..21 on the way; round 5 put the pass itself behind a call boundary

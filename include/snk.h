@@ -180,7 +180,8 @@ int snk_reset(snk_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stre
  * Every wait inside the kernel is bounded; if one ever runs out the kernel drains, and this and
  * every later call on the handle return non-zero ("env-step scheduler: ...").  Environment:
  * SNK_QUANTUM=<substeps per slice> (default 1; 0 = the unscheduled kernel), SNK_FORCE_STREAMED=1 (16 links on the
- * streamed-row kernels of the 32-link chain: diagnostics and cross-checks), both read by snk_create. */
+ * streamed-row kernels of the 32-link chain: diagnostics and cross-checks), SNK_MOTORS_APART=1 (the register-resident
+ * substep builds its motor rows in a batch of their own at every contact count: cross-checks), all read by snk_create. */
 int snk_step(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev,
              uint8_t* done_dev, int32_t* substeps_dev, int32_t vec_mode, void* stream);
 
@@ -290,6 +291,12 @@ int snk_debug_raise_alarm(snk_handle* h);
  * the forward sweep, entries 0..n-1 naming limit j, entries n..2n-1 motor j - n.  Read from the same constexpr table
  * the kernels unroll their sweeps over. */
 int snk_debug_noncontact_order(int32_t n_modules, int32_t* out);
+
+/* Test hook (host only, no handle): what the kernels' bound on one substep's change of the mean height is made of for
+ * this parameter set ("when the sensor pass runs"): out[0] = the longest joint-to-joint offset of the chain
+ * and out[1] = the distance of the base link's COM from the root origin, both in metres and rounded up by 1.001 as the
+ * device model holds them; out[2] = the bound's fixed slack in metres. */
+int snk_debug_reach_bound(const snk_params* p, float out[3]);
 
 /* Device-side self test of the wave primitives (DPP reductions); 0 = pass. */
 int snk_selftest(int32_t device);
