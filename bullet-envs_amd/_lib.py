@@ -64,6 +64,9 @@ SYMBOLS = {
     "snk_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
     "snk_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "snk_step_packed": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp]),
+    "snk_trace_row_floats": (C.c_int32, [_vp]),
+    "snk_step_traced": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "snk_step_traced_host": (C.c_int, [_vp, _F, _F, _F, _U8, _I32, _F, C.c_int32, C.c_int32]),
     "snk_reset_host": (C.c_int, [_vp, _U8, _F]),
     "snk_step_host": (C.c_int, [_vp, _F, _F, _F, _U8, _I32, C.c_int32]),
     "snk_substep_host": (C.c_int, [_vp, _F, C.c_int32, _I32]),
@@ -172,6 +175,34 @@ def fptr(a):
     return a.ctypes.data_as(_F)
 
 
+def trace_row_floats(n_modules):
+    """Floats per row of the step kernels' trace buffer (snk_trace_row_floats): the payload [obs 3n + 8 | link positions
+    3(n + 1)] rounded up to whole 128-byte lines."""
+    n = int(n_modules)
+    return (3 * n + 8 + 3 * (n + 1) + 31) // 32 * 32
+
+
+def trace_to_lists(trace, sub, n_modules):
+    """What test mode's info holds (SnakeGymEnv.py:43-44, snake.py:292-293), from a trace of snk_step_traced: per env
+    the lists (internal_observations, link_positions) of its first sub[i] rows, float64 arrays of 3n + 8 and 3(n + 1)
+    values ([x.., y.., z..] of links 0, 3, ..., 3n).  Rows at and beyond sub[i] are never looked at (the kernel never
+    writes them).  Pure numpy."""
+    n = int(n_modules)
+    no, nl = 3 * n + 8, 3 * (n + 1)
+    trace = np.asarray(trace)
+    sub = np.asarray(sub)
+    if trace.ndim != 3 or trace.shape[0] != len(sub) or trace.shape[2] < no + nl:
+        raise ValueError("trace must be [n_envs, rows, >= %d], got %s for %d envs" % (no + nl, trace.shape, len(sub)))
+    if len(sub) and int(sub.max()) > trace.shape[1]:
+        raise ValueError("trace holds %d rows per env, an env ran %d substeps" % (trace.shape[1], int(sub.max())))
+    io, lp = [], []
+    for i in range(len(sub)):
+        rows = trace[i, :int(sub[i])].astype(np.float64)
+        io.append([rows[s, :no].copy() for s in range(len(rows))])
+        lp.append([rows[s, no:no + nl].copy() for s in range(len(rows))])
+    return io, lp
+
+
 class Stepper:
     """Thin owner of one `snk_handle`: N environments on one GPU (host-buffer API)."""
 
@@ -221,6 +252,26 @@ class Stepper:
         check(self.lib.snk_step_host(self.h, fptr(actions), fptr(obs), fptr(rew), done.ctypes.data_as(_U8),
                                      sub.ctypes.data_as(_I32), 1 if vec_mode else 0), "snk_step_host")
         return obs, rew, done.astype(bool), sub
+
+    def trace_shape(self):
+        """[n_envs, rows, floats per row] of the trace step_traced returns (rows = max_counter + 1)."""
+        return (self.n_envs, int(self.params.max_counter) + 1, int(self.lib.snk_trace_row_floats(self.h)))
+
+    def step_traced(self, actions, vec_mode=True):
+        """step() that also records every physics substep (snk_step_traced_host).  Returns obs, rew, done, substeps,
+        trace; trace [n_envs, max_counter + 1, row] float32: row s < substeps[i] of env i = [observation after substep s
+        (3n + 8) | link positions (3(n + 1), x.. y.. z..) | padding]; the other rows are left as allocated (NaN here)."""
+        assert actions.dtype == np.float32 and actions.flags.c_contiguous
+        assert actions.shape == (self.n_envs, self.act_dim)
+        obs = np.empty((self.n_envs, self.obs_dim), dtype=np.float32)
+        rew = np.empty(self.n_envs, dtype=np.float32)
+        done = np.empty(self.n_envs, dtype=np.uint8)
+        sub = np.empty(self.n_envs, dtype=np.int32)
+        trace = np.full(self.trace_shape(), np.nan, dtype=np.float32)
+        check(self.lib.snk_step_traced_host(self.h, fptr(actions), fptr(obs), fptr(rew), done.ctypes.data_as(_U8),
+                                            sub.ctypes.data_as(_I32), fptr(trace), trace.shape[1], 1 if vec_mode else 0),
+              "snk_step_traced_host")
+        return obs, rew, done.astype(bool), sub, trace
 
     def substep(self, targets, k=1):
         t = np.ascontiguousarray(targets, dtype=np.float32)
@@ -350,6 +401,13 @@ class Stepper:
     def step_device(self, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr=0, vec_mode=True, stream=0):
         check(self.lib.snk_step(self.h, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr or None,
                                 1 if vec_mode else 0, stream or None), "snk_step")
+
+    def step_traced_device(self, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr, trace_ptr, trace_rows, vec_mode=True,
+                           stream=0):
+        """snk_step_traced: snk_step plus one trace row per physics substep, [n_envs x trace_rows x trace row floats] f32
+        at trace_ptr (128-byte aligned); sub_ptr is required (it says how many rows of each env are valid)."""
+        check(self.lib.snk_step_traced(self.h, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr or None, trace_ptr or None,
+                                       int(trace_rows), 1 if vec_mode else 0, stream or None), "snk_step_traced")
 
     def step_packed_device(self, actions_ptr, packed_ptr, row_stride, sub_ptr=0, vec_mode=True, stream=0):
         """snk_step_packed: rows [obs | reward f32 | done u32] of `row_stride` floats in one device buffer."""

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +52,8 @@ struct snk_handle {
     int32_t* d_info = nullptr;
     float* d_h = nullptr;
     float* d_linkpos = nullptr;   // allocated on first snk_link_positions
+    float* d_trace = nullptr;     // allocated on first snk_step_traced_host: [n_envs][d_trace_rows][trace row floats]
+    int d_trace_rows = 0;
     float* d_mf = nullptr;        // contact_model 1: the persistent contact manifolds, [n_envs][2n][kMfFloats]
     float* d_rows = nullptr;      // 32-link chains: constraint rows streamed from global memory (snk_device.hpp: pgs_v1)
     unsigned long long* d_ovf = nullptr;   // contacts the solves had no room for (snk_contact_overflow): 3 counters
@@ -94,27 +97,32 @@ int dispatch(const snk_handle* h, F&& fn) {
     return fail("unsupported n_modules (16 or 32)");
 }
 
+// floats per row of the trace buffer (snk_trace_row_floats): the payload [obs | link positions] in whole 128-byte lines
+int trace_row_floats(int n) { return (3 * n + 8 + 3 * (n + 1) + 31) / 32 * 32; }
+
 // packed_stride > 0 (snk_step_packed): obs rows of that stride, reward and done flag behind each row's observation.
-template <class K>
+// TRACE (snk_step_traced): the kernels that also write `trace`, trace_rows rows per env.
+template <bool TRACE, class K>
 int launch_step(K, snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode,
-                hipStream_t st, int packed_stride) {
+                hipStream_t st, int packed_stride, float* trace, int trace_rows) {
     snk::StepArgs a;
     a.recs = h->d_recs; a.mu_plane = h->d_mu; a.actions = act; a.obs = obs; a.rew = rew; a.done = done; a.substeps = sub;
     a.rows_all = h->d_rows; a.mf_all = h->d_mf; a.ovf = h->d_ovf; a.box_all = h->d_box; a.sc = h->sched;
     a.model_slot = h->model_slot; a.vec_mode = vec_mode; a.n_envs = h->n_envs;
     a.obs_stride = packed_stride > 0 ? packed_stride : h->D.obs_dim; a.packed = packed_stride > 0 ? 1 : 0; a.pad_ = 0;
     a.model = h->d_model; a.order = h->plan ? h->d_order : nullptr;
+    a.trace = trace; a.trace_rows = trace_rows; a.trace_stride = trace_row_floats(h->n);
     if (h->use_sched) {
         hipLaunchKernelGGL((snk::plan_sched_kernel<K::N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->sched,
                            h->n_envs);
-        hipLaunchKernelGGL((snk::env_step_sched_kernel<K::N, K::V2, K::RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes,
-                           st, a);
+        hipLaunchKernelGGL((snk::env_step_sched_kernel<K::N, K::V2, K::RULES, TRACE>), dim3(h->grid_waves), dim3(64),
+                           h->lds_bytes, st, a);
         return 0;
     }
     if (h->plan)
         hipLaunchKernelGGL((snk::plan_kernel<K::N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->d_order,
                            h->n_envs);
-    hipLaunchKernelGGL((snk::env_step_kernel<K::N, K::V2, K::RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, a);
+    hipLaunchKernelGGL((snk::env_step_kernel<K::N, K::V2, K::RULES, TRACE>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st, a);
     return 0;
 }
 template <class K>
@@ -152,6 +160,8 @@ template <class K>
 int set_lds_attr(K, size_t bytes) {
     const void* kernels[] = {reinterpret_cast<const void*>(&snk::env_step_kernel<K::N, K::V2, K::RULES>),
                              reinterpret_cast<const void*>(&snk::env_step_sched_kernel<K::N, K::V2, K::RULES>),
+                             reinterpret_cast<const void*>(&snk::env_step_kernel<K::N, K::V2, K::RULES, true>),
+                             reinterpret_cast<const void*>(&snk::env_step_sched_kernel<K::N, K::V2, K::RULES, true>),
                              reinterpret_cast<const void*>(&snk::substep_kernel<K::N, K::V2, K::RULES>),
                              reinterpret_cast<const void*>(&snk::reset_kernel<K::N, K::V2>),
                              reinterpret_cast<const void*>(&snk::obs_kernel<K::N, K::V2>)};
@@ -197,13 +207,17 @@ int check_launch() {
     return 0;
 }
 
-// the launch of snk_step / snk_step_packed, between a pair of snk_timing_enable's events while the pool has one left
+// the launch of snk_step / snk_step_packed / snk_step_traced (trace != null), between a pair of snk_timing_enable's
+// events while the pool has one left
 int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode, hipStream_t st,
-               int packed_stride) {
+               int packed_stride, float* trace = nullptr, int trace_rows = 0) {
     HIP_TRY(hipSetDevice(h->device));
     const bool timed = 2 * h->ev_used + 1 < (int)h->ev.size();
     if (timed) HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used], st));
-    const int rc = dispatch(h, [&](auto k) { return launch_step(k, h, act, obs, rew, done, sub, vec_mode, st, packed_stride); });
+    const int rc = dispatch(h, [&](auto k) {
+        return trace ? launch_step<true>(k, h, act, obs, rew, done, sub, vec_mode, st, packed_stride, trace, trace_rows)
+                     : launch_step<false>(k, h, act, obs, rew, done, sub, vec_mode, st, packed_stride, nullptr, 0);
+    });
     if (rc) return rc;
     if (timed) {
         HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used + 1], st));
@@ -510,7 +524,7 @@ int snk_destroy(snk_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     void* bufs[] = {h->d_model, h->d_recs, h->d_mu, h->d_act, h->d_obs, h->d_rew, h->d_done,
-                    h->d_sub, h->d_mask, h->d_tgt, h->d_info, h->d_h, h->d_order, h->d_rows, h->d_linkpos, h->d_mf, h->d_ovf, h->d_box,
+                    h->d_sub, h->d_mask, h->d_tgt, h->d_info, h->d_h, h->d_order, h->d_rows, h->d_linkpos, h->d_trace, h->d_mf, h->d_ovf, h->d_box,
 
                     h->sched.head, h->sched.tail, h->sched.ent, h->sched.waiting, h->sched.counter, h->sched.finished};
     for (void* b : bufs) (void)hipFree(b);
@@ -560,6 +574,27 @@ int snk_step_packed(snk_handle* h, float* actions_dev, float* packed_dev, int32_
     if (row_stride < h->D.obs_dim + 2) return fail("snk_step_packed: row_stride must be at least obs_dim + 2");
     if (check_alarm(h)) return 1;
     return timed_step(h, actions_dev, packed_dev, nullptr, nullptr, substeps_dev, vec_mode, (hipStream_t)stream, row_stride);
+}
+
+int32_t snk_trace_row_floats(const snk_handle* h) { return h ? trace_row_floats(h->n) : 0; }
+
+int snk_step_traced(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev,
+                    int32_t* substeps_dev, float* trace_dev, int32_t trace_rows, int32_t vec_mode, void* stream) {
+    if (!h) return fail("snk_step_traced: null handle");
+    if (!actions_dev || !obs_dev || !rew_dev || !done_dev) return fail("snk_step_traced: null buffer");
+    if (!substeps_dev) return fail("snk_step_traced: substeps_dev is required (it says how many rows of each env are valid)");
+    if (!trace_dev) return fail("snk_step_traced: null trace buffer");
+    if (trace_rows < h->P.max_counter + 1) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "snk_step_traced: trace_rows %d is less than max_counter + 1 = %d (an env-step runs up to "
+                 "that many physics substeps)", (int)trace_rows, (int)h->P.max_counter + 1);
+        return fail(msg);
+    }
+    if (reinterpret_cast<uintptr_t>(trace_dev) % 128 != 0)
+        return fail("snk_step_traced: the trace buffer must be 128-byte aligned (a row is a whole number of 128-byte lines)");
+    if (check_alarm(h)) return 1;
+    return timed_step(h, actions_dev, obs_dev, rew_dev, done_dev, substeps_dev, vec_mode, (hipStream_t)stream, 0, trace_dev,
+                      trace_rows);
 }
 
 int snk_timing_enable(snk_handle* h, int32_t capacity) {
@@ -620,6 +655,38 @@ int snk_step_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t
     HIP_TRY(hipMemcpy(rew, h->d_rew, ne * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(done, h->d_done, ne, hipMemcpyDeviceToHost));
     if (substeps) HIP_TRY(hipMemcpy(substeps, h->d_sub, ne * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int snk_step_traced_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
+                         float* trace, int32_t trace_rows, int32_t vec_mode) {
+    if (!h) return fail("snk_step_traced_host: null handle");
+    if (!actions || !obs || !rew || !done || !substeps || !trace) return fail("snk_step_traced_host: null buffer");
+    if (trace_rows <= 0) return fail("snk_step_traced_host: trace_rows must be positive");
+    if (check_alarm(h)) return 1;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t ne = (size_t)h->n_envs;
+    const size_t tbytes = ne * (size_t)trace_rows * trace_row_floats(h->n) * sizeof(float);
+    if (!h->d_trace || h->d_trace_rows != trace_rows) {
+        HIP_TRY(hipDeviceSynchronize());
+        if (h->d_trace) { (void)hipFree(h->d_trace); h->d_trace = nullptr; h->d_trace_rows = 0; }
+        HIP_TRY(hipMalloc(&h->d_trace, tbytes));
+        h->d_trace_rows = trace_rows;
+    }
+    // what the kernel does not write -- the padding of a row, the rows from an env's count on -- comes back as NaNs
+    // (all bits set), whatever the caller's buffer held
+    HIP_TRY(hipMemsetAsync(h->d_trace, 0xFF, tbytes, nullptr));
+    HIP_TRY(hipMemcpy(h->d_act, actions, ne * h->D.act_dim * sizeof(float), hipMemcpyHostToDevice));
+    int rc = snk_step_traced(h, h->d_act, h->d_obs, h->d_rew, h->d_done, h->d_sub, h->d_trace, trace_rows, vec_mode, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (check_alarm(h)) return 1;
+    HIP_TRY(hipMemcpy(actions, h->d_act, ne * h->D.act_dim * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(obs, h->d_obs, ne * h->D.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rew, h->d_rew, ne * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(done, h->d_done, ne, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(substeps, h->d_sub, ne * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(trace, h->d_trace, tbytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

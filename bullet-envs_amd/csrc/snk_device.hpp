@@ -246,6 +246,10 @@ struct StepArgs {
     // so that the scheduled kernel's offsets stay as they were
     const DevModel* model;
     const int32_t* order;
+    // the TRACE kernels only (snk_step_traced): one row per physics substep of every env-step, row s of env e at
+    // trace[(e * trace_rows + s) * trace_stride] (write_trace_row).  Appended, like the two above
+    float* trace;
+    int32_t trace_rows, trace_stride;
 };
 typedef const StepArgs __attribute__((address_space(4))) * StepArgPtr;
 __device__ __forceinline__ StepArgPtr step_args() {
@@ -323,8 +327,36 @@ __device__ __forceinline__ void finish_env_step(LT& L, const DevModel& M, StepAr
     }
 }
 
+// Test-mode telemetry (snake.py:292-293: step_internal_observations.append(getObservation()),
+// link_positions.append(getLinkPositions()) after every stepSimulation; SnakeGymEnv.py:43-44 hands the lists out as
+// info): the TRACE kernels write row `row` = counter - 1 of env after each substep,
+//   [ obs (3n + 8, write_obs's) | link positions 3 (n + 1) as x_0..x_n, y_0..y_n, z_0..z_n (obs_kernel's formula) | padding ].
+// Both substeps end in fk_vel (snk_pgs_v1.hpp, snk_pgs_v2.hpp; the streamed-row substep a register-resident wave calls
+// for its rare substeps works on the same first members of the image), whose closing lds_sync leaves L.rec, L.o and
+// L.R[0] current: what mean_height reads right behind this.  The row stride is a whole number of 128-byte lines and the
+// buffer is aligned to one (snk_step_traced checks both), so a row's lines are written by the one wave that ran its
+// substep, whoever ran the substeps before and after a hand-off (a wave owns whole lines).  Plain stores:
+// nothing reads a row inside the launch.  The padding and the rows from the env's count on are never touched.
+template <class LT>
+__device__ __forceinline__ void write_trace_row(LT& L, const DevModel& M, StepArgPtr a, int env, int row, int lane) {
+    constexpr int N = LT::kN;
+    const int rows = a->trace_rows;
+    if (row < 0 || row >= rows) return;        // never: counter <= max_counter + 1 <= trace_rows (snk_step_traced)
+    float* out = a->trace + ((size_t)env * rows + row) * a->trace_stride;
+    write_obs(L, out, lane);
+    lane = launder_lane(lane);
+    if (lane <= N) {
+        f3 c = ld3(L.o[lane]);
+        if (lane == 0) c = c + mulRv(L.R[0], ld3(M.hbase));
+        float* lp = out + (3 * N + 8);
+        lp[lane] = c.x; lp[(N + 1) + lane] = c.y; lp[2 * (N + 1) + lane] = c.z;
+    }
+}
+
 // Whole env-steps in launch order, without the scheduler: SNK_QUANTUM=0, and the handles that find no model slot.
-template <int N, bool V2, int RULES = 0>
+// TRACE (snk_step_traced): a trace row after every substep, and the sensor pass on every substep (hint.always, as
+// substep_kernel has it), so that every row's obs[3n + 7] and motor torques are that substep's own.
+template <int N, bool V2, int RULES = 0, bool TRACE = false>
 __global__ __launch_bounds__(64, 2) void env_step_kernel(StepArgs args_by_value) {
     (void)args_by_value;            // read through step_args() only
     extern __shared__ float4 smem_raw[];
@@ -351,7 +383,7 @@ __global__ __launch_bounds__(64, 2) void env_step_kernel(StepArgs args_by_value)
     bool end_height = false;
     int it_dummy = 0, nc_dummy = 0;
     SensorHint hint;
-    hint.always = false;
+    hint.always = TRACE;
     hint.h_prev = mean_height(L, M, lane);
     while (true) {
         float e = (lane < N) ? (L.targets[lane] - L.q()[lane]) : 0.f;
@@ -360,6 +392,7 @@ __global__ __launch_bounds__(64, 2) void env_step_kernel(StepArgs args_by_value)
         hint.counter_next = counter + 1;
         substep(L, M, lane, mu, it_dummy, nc_dummy, hint, env_rows, env_mf, ovf);
         counter++;
+        if constexpr (TRACE) write_trace_row(L, M, step_args(), env, counter - 1, lane_id());
         hint.h_prev = mean_height(L, M, lane);
         if (hint.h_prev > M.height_thr) { end_height = true; break; }
         if (counter > M.max_counter) break;
@@ -371,7 +404,9 @@ __global__ __launch_bounds__(64, 2) void env_step_kernel(StepArgs args_by_value)
     }
 }
 
-template <int N, bool V2, int RULES = 0>
+// TRACE: as in env_step_kernel.  The row index is `counter`, which already travels with a handed-off env-step
+// (Sched::counter): no new queue state.
+template <int N, bool V2, int RULES = 0, bool TRACE = false>
 __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs args_by_value) {
     (void)args_by_value;            // read through step_args() only
     extern __shared__ float4 smem_raw[];
@@ -427,7 +462,7 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
         bool end_height = false, complete = false;
         int it_dummy = 0, nc_dummy = 0, in_slice = 0;
         SensorHint hint;
-        hint.always = false;
+        hint.always = TRACE;
         hint.h_prev = mean_height(L, M, lane);
         while (true) {
             float e = (lane < N) ? (L.targets[lane] - L.q()[lane]) : 0.f;
@@ -459,6 +494,7 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
 #endif
             counter++;
             in_slice++;
+            if constexpr (TRACE) write_trace_row(L, M, step_args(), env, counter - 1, lane);
             hint.h_prev = mean_height(L, M, lane);
             if (uni(hint.h_prev > M.height_thr)) { end_height = true; complete = true; break; }
             if (counter > M.max_counter) { complete = true; break; }

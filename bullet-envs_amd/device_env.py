@@ -52,11 +52,37 @@ class DeviceVecEnv(object):
         assert substeps.is_cuda and substeps.dtype == t.int32 and substeps.is_contiguous() and substeps.numel() == self.num_envs
         return substeps.data_ptr()
 
-    def step(self, actions, vec_mode=True, substeps=None):
-        """actions: float32 CUDA tensor [E, A], contiguous; clipped in place.  Asynchronous."""
+    def trace_shape(self):
+        """Shape of the float32 CUDA tensor step(trace=...) fills: [E, max_counter + 1, floats per row]."""
+        return self.stepper.trace_shape()
+
+    def _trace_ptr(self, trace):
+        """a caller-owned trace tensor (trace_shape(); more rows are allowed, the kernel leaves them alone)"""
+        t = self.torch
+        want = self.trace_shape()
+        if not isinstance(trace, t.Tensor) or not trace.is_cuda or trace.device != self.device:
+            raise ValueError("trace must be a CUDA tensor on %s" % (self.device,))
+        if trace.dtype != t.float32:
+            raise ValueError("trace must be float32, got %s" % (trace.dtype,))
+        if trace.dim() != 3 or trace.shape[0] != want[0] or trace.shape[1] < want[1] or trace.shape[2] != want[2]:
+            raise ValueError("trace must have shape %s (or more rows), got %s" % (want, tuple(trace.shape)))
+        if not trace.is_contiguous():
+            raise ValueError("trace must be contiguous")
+        return trace.data_ptr()
+
+    def step(self, actions, vec_mode=True, substeps=None, trace=None):
+        """actions: float32 CUDA tensor [E, A], contiguous; clipped in place.  Asynchronous.
+        trace: a float32 CUDA tensor of trace_shape(): the step kernel then also writes row s of env e after its physics
+        substep s, [obs | link positions | padding] (snk_step_traced); rows at and beyond the env's substep count (in
+        self.substeps, or `substeps`) are not touched."""
         t = self.torch
         assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous()
         assert tuple(actions.shape) == (self.num_envs, self.act_dim)
+        if trace is not None:
+            self.stepper.step_traced_device(actions.data_ptr(), self.obs.data_ptr(), self.rew.data_ptr(),
+                                            self.done.data_ptr(), self._sub_ptr(substeps), self._trace_ptr(trace),
+                                            trace.shape[1], vec_mode, self._stream())
+            return self.obs, self.rew, self.done
         self.stepper.step_device(actions.data_ptr(), self.obs.data_ptr(), self.rew.data_ptr(),
                                  self.done.data_ptr(), self._sub_ptr(substeps), vec_mode, self._stream())
         return self.obs, self.rew, self.done

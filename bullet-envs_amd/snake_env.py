@@ -20,6 +20,16 @@ from .spaces import make_box
 
 PI = math.pi
 
+#: where test mode's per-substep telemetry comes from: 'replay' = the env-step replayed substep by substep on a scratch
+#: handle (the default), 'kernel' = rows the fused step kernel writes itself (snk_step_traced)
+TELEMETRY = ('replay', 'kernel')
+
+
+def _check_telemetry(telemetry):
+    if telemetry not in TELEMETRY:
+        raise ValueError("telemetry must be 'replay' or 'kernel', got %r" % (telemetry,))
+    return telemetry
+
 
 def params_from_args(args=None, n_modules=16, **over):
     """snk_params from the reference's argparse namespace (ppo/params.py:5-46).
@@ -55,8 +65,9 @@ class Snake(object):
     the model is generated from the snake.urdf constants and the world lives on the GPU.
     """
 
-    def __init__(self, pybullet_client=None, urdf_root=None, args=None, n_modules=16):
+    def __init__(self, pybullet_client=None, urdf_root=None, args=None, n_modules=16, telemetry=None):
         self.numMotors = n_modules
+        self.telemetry = None if telemetry is None else _check_telemetry(telemetry)   # None: the env's own setting
         self._pybulletClient = pybullet_client
         self._urdf = urdf_root
         self._timeStep = 1 / 100.0                       # snake.py:9,19
@@ -208,8 +219,11 @@ class Snake(object):
 class SnakeGymEnv(object):
     """Single environment with SnakeGymEnv's API, backed by a 1-env GPU stepper."""
 
-    def __init__(self, robot=None, args=None, device=0, n_modules=None, **over):
+    def __init__(self, robot=None, args=None, device=0, n_modules=None, telemetry=None, **over):
         print("Snake Gym environment Created!")          # SnakeGymEnv.py:6
+        # test mode's telemetry: the robot's setting when it has one, else 'replay'
+        self.telemetry = _check_telemetry(telemetry if telemetry is not None else
+                                          (getattr(robot, "telemetry", None) or 'replay'))
         if robot is None:
             robot = Snake(None, None, args, n_modules=n_modules or 16)
         n_modules = n_modules or robot.numMotors
@@ -257,11 +271,16 @@ class SnakeGymEnv(object):
         a32 = np.ascontiguousarray(np.asarray(action, dtype=np.float32).reshape(1, -1))
         if a32.shape[1] != self._stepper.act_dim:
             raise SystemError("Action not executed!")
-        if self.mode == 'test':
+        traced = self.mode == 'test' and self.telemetry == 'kernel'
+        if self.mode == 'test' and not traced:
             before = self._stepper.get_state() + (self._stepper.get_manifold(),
                                                   self._stepper.get_box() if self.params.obstacle == 2 else None)
-        obs, rew, done, sub = self._stepper.step(a32, vec_mode=False)
-        if self.mode == 'test':
+        if traced:
+            obs, rew, done, sub, trace = self._stepper.step_traced(a32, vec_mode=False)
+            self._kernel_telemetry(trace, sub, obs[0])
+        else:
+            obs, rew, done, sub = self._stepper.step(a32, vec_mode=False)
+        if self.mode == 'test' and not traced:
             self._record_telemetry(before, a32[0], int(sub[0]), obs[0])
         try:
             for idx in range(len(action)):
@@ -278,6 +297,17 @@ class SnakeGymEnv(object):
         else:
             info = {}
         return observation, float(rew[0]), bool(done[0]), info
+
+    def _kernel_telemetry(self, trace, sub, final_obs):
+        """Test mode with telemetry='kernel': the same lists as _record_telemetry's, from the rows the step kernel wrote
+        after every substep (snk_step_traced): no scratch handle, no state downloads.  vec_mode is 0 here, so the
+        returned observation is the last substep's whether the episode ended or not."""
+        r = self.robot
+        r.imgs = []
+        io, lp = _lib.trace_to_lists(trace, sub, self.params.n_modules)
+        r.step_internal_observations, r.link_positions = io[0], lp[0]
+        if io[0] and not np.array_equal(io[0][-1].astype(np.float32), final_obs):
+            raise SystemError("test-mode trace diverged from the step kernel's observation")
 
     def _record_telemetry(self, before, clipped_action, n_substeps, final_obs):
         """Test mode (snake.py:275-293, SnakeGymEnv.py:43-44): the observation and the link
@@ -428,7 +458,9 @@ class SnakeVecEnv(VecEnv):
     (multiprocessing_env.py:13-16, SnakeGymEnv.py:39-41).
     """
 
-    def __init__(self, num_envs, args=None, device=0, n_modules=16, params=None, shared_infos=False, mode=None, **over):
+    def __init__(self, num_envs, args=None, device=0, n_modules=16, params=None, shared_infos=False, mode=None,
+                 telemetry='replay', **over):
+        self.telemetry = _check_telemetry(telemetry)
         self.params = params if params is not None else params_from_args(args, n_modules=n_modules, **over)
         self._stepper = _lib.Stepper(num_envs, device=device, params=self.params)
         self.nenvs = num_envs
@@ -453,6 +485,11 @@ class SnakeVecEnv(VecEnv):
         self.waiting = True
 
     def step_wait(self):
+        if self.mode == 'test' and self.telemetry == 'kernel':
+            obs, rew, done, sub, trace = self._stepper.step_traced(self._pending, vec_mode=True)
+            self.waiting = False
+            self.last_substeps = sub
+            return obs, rew, done, self._kernel_telemetry(trace, sub, obs, done)
         if self.mode == 'test':
             st = self._stepper
             before = st.get_state() + (st.get_manifold(), st.get_box() if self.params.obstacle == 2 else None)
@@ -466,6 +503,17 @@ class SnakeVecEnv(VecEnv):
         # may pickle them.  0.15 ms for 4096 envs; shared_infos=True hands out one read-only FrozenInfo instead.
         infos = self._shared_infos if self._shared_infos is not None else tuple({} for _ in range(self.nenvs))
         return obs, rew, done, infos
+
+    def _kernel_telemetry(self, trace, sub, obs, done):
+        """_telemetry's infos from the rows the step kernel wrote after every substep (telemetry='kernel',
+        snk_step_traced): no scratch handle, no state downloads, no replay.  The rows of a done env hold the step that
+        ended its episode (its returned observation is the post-reset one); the last row of every other env must be the
+        observation the step returned, bit for bit."""
+        io, lp = _lib.trace_to_lists(trace, sub, self.params.n_modules)
+        for i in range(self.nenvs):
+            if sub[i] and not done[i] and not np.array_equal(io[i][-1].astype(np.float32), obs[i]):
+                raise SystemError("test-mode trace diverged from the step kernel's observation (env %d)" % i)
+        return tuple({'frames': [], 'internal_observations': io[i], 'link_positions': lp[i]} for i in range(self.nenvs))
 
     def _telemetry(self, before, clipped_actions, sub, obs, done):
         """Test mode through the vector seam: what each of the reference's workers would put into its info -- the
@@ -543,7 +591,7 @@ class SubprocVecEnv(SnakeVecEnv):
     #: spaced ones (a thunk builds a one-env handle of its own: 4096 of them would take seconds)
     kHeteroProbe = 64
 
-    def __init__(self, env_fns, spaces=None, device=0):
+    def __init__(self, env_fns, spaces=None, device=0, telemetry=None):
         env_fns = list(env_fns)
         if not env_fns:
             raise ValueError("SubprocVecEnv: no env_fns")
@@ -552,19 +600,20 @@ class SubprocVecEnv(SnakeVecEnv):
             probe = list(range(n))
         else:
             probe = sorted(set([0, n - 1] + [int(round(i * (n - 1) / (self.kHeteroProbe - 1.0))) for i in range(self.kHeteroProbe)]))
-        params = mode = None
+        params = mode = tel = None
         for i in probe:
             fn = env_fns[i]
             proto = (fn.x if isinstance(fn, CloudpickleWrapper) else fn)()
             p_i = getattr(proto, "params", None)
             m_i = getattr(proto, "mode", "train")
+            t_i = getattr(proto, "telemetry", "replay")
             if hasattr(proto, "close"):
                 proto.close()
             if p_i is None:
                 raise TypeError("env_fns must build bullet-envs_amd SnakeGymEnv objects (env_fns[%d] built %r)"
                                 % (i, type(proto).__name__))
             if params is None:
-                params, mode = p_i, m_i
+                params, mode, tel = p_i, m_i, t_i
                 continue
             # The reference forks one process per thunk and honours each one's own settings
             # (ppo/multiprocessing_env.py:106-111); one handle has ONE parameter set, so thunks that differ are refused
@@ -572,9 +621,14 @@ class SubprocVecEnv(SnakeVecEnv):
             if m_i != mode:
                 raise ValueError("SubprocVecEnv: env_fns[%d] differs from env_fns[0] in `mode` (%r vs %r); one GPU handle "
                                  "runs one parameter set -- build one SubprocVecEnv per distinct configuration" % (i, m_i, mode))
+            if telemetry is None and t_i != tel:
+                raise ValueError("SubprocVecEnv: env_fns[%d] differs from env_fns[0] in `telemetry` (%r vs %r); pass "
+                                 "telemetry=... to choose one for the whole vector env" % (i, t_i, tel))
             diff = params_first_difference(params, p_i)
             if diff is not None:
                 raise ValueError("SubprocVecEnv: env_fns[%d] differs from env_fns[0] in `%s` (%r vs %r); one GPU handle "
                                  "runs one parameter set -- build one SubprocVecEnv per distinct configuration"
                                  % (i, diff[0], diff[2], diff[1]))
-        SnakeVecEnv.__init__(self, n, device=device, params=params, mode=mode)
+        # test mode's telemetry source: the argument, else what the thunks' envs were built with
+        SnakeVecEnv.__init__(self, n, device=device, params=params, mode=mode,
+                             telemetry=telemetry if telemetry is not None else tel)

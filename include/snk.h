@@ -193,10 +193,37 @@ int snk_step(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev,
 int snk_step_packed(snk_handle* h, float* actions_dev, float* packed_dev, int32_t row_stride,
                     int32_t* substeps_dev, int32_t vec_mode, void* stream);
 
+/* Test-mode telemetry, written by the step kernel itself.  Replaces what Snake.step collects in mode 'test' after
+ * every stepSimulation of its servo loop (snake.py:275-293: step_internal_observations.append(getObservation()),
+ * link_positions.append(getLinkPositions())) and SnakeGymEnv.step hands out as info['internal_observations'] /
+ * info['link_positions'] (SnakeGymEnv.py:43-44; ppo/test.py:84-105 concatenates them into the saved trajectories).
+ *
+ * snk_trace_row_floats: floats per trace row = the payload, 3n + 8 observation floats + 3(n + 1) link-position floats,
+ * rounded up to a multiple of 32 floats (whole 128-byte lines): 107 -> 128 for 16 links, 203 -> 224 for 32 links.
+ *
+ * snk_step_traced: snk_step (same contract, same results bit for bit) that also writes, after physics substep s of env
+ * e's env-step, row s of that env:
+ *   trace_dev [n_envs x trace_rows x snk_trace_row_floats] f32, device, 128-byte aligned;
+ *   row = [ getObservation after the substep (3n + 8) | getLinkPositions x_0..x_n, y_0..y_n, z_0..z_n | padding ].
+ * Rows s >= substeps_dev[e] and every row's padding are never touched; an env-step of 0 substeps writes nothing.  The
+ * rows of an env whose episode ended in this step hold that step (pre-reset state: the reference clears its lists at the
+ * start of the next step, snake.py:276-278, not in reset).  Every row's joint-0 force and motor torques are its own
+ * substep's (the kernel evaluates the sensor pass on every substep of a traced step; snk_step only where it can be
+ * observed).  substeps_dev is required; trace_rows >= max_counter + 1, else the call refuses.  A misaligned trace_dev is
+ * refused. */
+int32_t snk_trace_row_floats(const snk_handle* h);
+int snk_step_traced(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev,
+                    int32_t* substeps_dev, float* trace_dev, int32_t trace_rows, int32_t vec_mode, void* stream);
+
 /* Host-buffer convenience forms (upload, run, download, synchronise). */
 int snk_reset_host(snk_handle* h, const uint8_t* mask, float* obs);
 int snk_step_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done,
                   int32_t* substeps, int32_t vec_mode);
+/* snk_step_traced with host buffers; trace [n_envs x trace_rows x snk_trace_row_floats] f32.  The device trace buffer
+ * belongs to the handle (allocated on the first call, again when trace_rows changes).  What the kernel does not write
+ * (padding, rows >= substeps[e]) comes back as NaN (all bits set), whatever `trace` held before. */
+int snk_step_traced_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
+                         float* trace, int32_t trace_rows, int32_t vec_mode);
 
 /* Replaces pybullet.stepSimulation (snake.py:286) preceded by setJointMotorControlArray
  * (snake.py:221): k physics substeps with motor targets [n_envs x n] (radians), host buffer.
@@ -279,7 +306,7 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
 
 /* Test hook for the failure path: raises this handle's alarm from the HOST -- the host-mapped word a wave of the step
  * kernel sets when one of its bounded waits runs out (nothing waits, nothing hangs).  Afterwards the handle behaves as
- * after a real alarm: snk_step / snk_step_packed / snk_step_host / snk_reset(_host) / snk_substep_host and the state
+ * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
  * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction) return
  * non-zero with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
