@@ -104,14 +104,28 @@ def _path(monkeypatch, path):
 
 GROUND = [("register-resident", "default"), ("streamed-row", "default"), ("32 links", "default"),
           pytest.param("register-resident", "cone_friction 0",
-                       marks=_open("worst velocity 0.125 against the float32 oracle's 0.031 (4.0 x) over 128 states")),
+                       marks=_open("worst velocity 0.125 against the float32 oracle's 0.031 (4.0 x) over 128 states "
+                                   "(sweep ladder, tests/test_gpu_np_sweeps.py: passes at 1, 2, 3 sweeps, first fails "
+                                   "at 5 -- one state 0.20 against 1.0e-4 --, passes at 10; the model's own spread "
+                                   "under one-ulp input noise at 50 sweeps is 6.1e-7 at worst: not a bifurcation, "
+                                   "open from sweep 5)")),
           pytest.param("streamed-row", "cone_friction 0",
-                       marks=_open("worst velocity 9.8 against the float32 oracle's 0.24 (41 x) over 128 states")),
+                       marks=_open("worst velocity 9.8 against the float32 oracle's 0.24 (41 x) over 128 states "
+                                   "(sweep ladder, tests/test_gpu_np_sweeps.py: first fails at sweep 1, p90 4.8e-5 "
+                                   "against 2.0e-5 (2.4 x), as the streamed-row solve does under every friction "
+                                   "setting, mu 0 included; the model's own spread at 50 sweeps 1.1e-5 at worst: open "
+                                   "from sweep 1)")),
           pytest.param("32 links", "cone_friction 0",
-                       marks=_open("worst velocity 7.5 against the float32 oracle's 0.21 (36 x) over 64 states")),
+                       marks=_open("worst velocity 7.5 against the float32 oracle's 0.21 (36 x) over 64 states (sweep "
+                                   "ladder, tests/test_gpu_np_sweeps.py: 8 states pass at 1 ... 25 sweeps, so it "
+                                   "first fails between 26 and 50; the model's own spread at 50 sweeps 1.7e-6 at "
+                                   "worst: amplification that one-ulp input noise does not explain, open)")),
           ("register-resident", "friction_directions 1"),
           pytest.param("streamed-row", "friction_directions 1",
-                       marks=_open("velocity p90 3.7e-4 against the float32 oracle's 1.5e-4 (2.4 x) over 128 states")),
+                       marks=_open("velocity p90 3.7e-4 against the float32 oracle's 1.5e-4 (2.4 x) over 128 states "
+                                   "(sweep ladder, tests/test_gpu_np_sweeps.py: passes at 1, first fails at 2 sweeps, "
+                                   "p90 1.3e-4 against 3.3e-5 (4.0 x); the model's own spread at 50 sweeps 9.7e-7 "
+                                   "at worst: open from sweep 2)")),
           ("32 links", "friction_directions 1")]
 
 
@@ -129,7 +143,13 @@ def test_ground_states_per_path(pkg, oracle_mod, monkeypatch, path, switch):
 @pytest.mark.parametrize("path,mu", [("register-resident", 0.0), ("register-resident", 6.0), ("streamed-row", 0.0),
                                      ("streamed-row", 6.0), ("32 links", 0.0),
                                      pytest.param("32 links", 6.0, marks=_open(
-                                         "motor-torque median 3.3e-5 against the float32 oracle's 1.8e-5 (1.8 x)"))])
+                                         "motor-torque median 3.3e-5 against the float32 oracle's 1.8e-5 (1.8 x) "
+                                         "(sweep ladder, tests/test_gpu_np_sweeps.py: passes at 1, 2, 3, first fails "
+                                         "at 5 sweeps, motor-torque p90 6.7e-5 against 2.2e-5 (3.0 x); the model's "
+                                         "own velocity "
+                                         "spread under one-ulp input noise at 50 sweeps: median 4.2e-5, worst 5.0e-2 "
+                                         "-- the tail is a "
+                                         "bifurcation, the median is not: open from sweep 5)"))])
 def test_ground_friction_edges(pkg, oracle_mod, monkeypatch, path, mu):
     """mu = 2 x mu_plane: 0 (a zero cone radius) and 12, clamped at 10 (fminf(mu_link * mu_plane, 10))."""
     n, streamed = _path(monkeypatch, path)
@@ -140,9 +160,12 @@ def test_ground_friction_edges(pkg, oracle_mod, monkeypatch, path, mu):
 
 
 @pytest.mark.parametrize("path", ["register-resident", pytest.param("streamed-row", marks=_open(
-    "worst velocity 0.39 against the float32 oracle's 0.14 (2.9 x) over 96 states")), "32 links"])
+    "worst velocity 0.39 against the float32 oracle's 0.14 (2.9 x) over 96 states (sweep ladder, "
+    "tests/test_gpu_np_sweeps.py: 16 states pass at 1 ... 25 sweeps; the model's own spread at 50 sweeps 1.7e-6 at "
+    "worst: a heavy tail of 96 states, open)")), "32 links"])
 def test_velocity_clamp(pkg, oracle_mod, monkeypatch, path):
-    """Weak motors (max_motor_impulse 0.05) and qd near +-100, in the air and on the ground: max_coord_vel clamps v + a dt
+    """Weak motors (max_motor_impulse 0.05) and qd near +-100, in the air and on the ground: max_coord_vel clamps v + "
+    "a dt
     and v_free + dv.  Velocities and torques are gated; the iteration count is not compared.  With every motor but one
     or two at its bound, the sweep's residual falls geometrically (1e4, 5e2, 1e-5, 1e-10, 6e-18, 5e-23 in (dI/dinv)^2)
     and the exit waits for it to be EXACTLY zero, i.e. for the last free motor's update to vanish in its accumulator's
@@ -207,7 +230,12 @@ def test_static_box(pkg, oracle_mod):
 
 
 @pytest.mark.parametrize("path", [p[0] for p in PATHS[:2]] + [pytest.param("32 links", marks=_open(
-    "velocity median 4.1e-2 against the float32 oracle's 1.8e-4 (230 x) over 8 states"))])
+    "velocity median 4.1e-2 against the float32 oracle's 1.8e-4 (230 x) over 8 states (sweep ladder, "
+    "tests/test_gpu_np_sweeps.py: the same states fail at 64 sweeps, median 1.9 x and p90 109 x, and at 128 the "
+    "median is 4.2e-2 against 4.0e-3; the "
+    "model's own spread under one-ulp input noise: worst 8.9e-7 at 64 sweeps, p90 1.5 / worst 4.8 at 128 -- the tail "
+    "is a "
+    "bifurcation from 128 sweeps on, the median, spread 2.8e-6, is not: open from sweep 64)"))])
 def test_converged_solve(pkg, oracle_mod, monkeypatch, path):
     """1000 sweeps without the residual exit, a handful of ground states per path, gated the same way.  Observed on 16
     links: GPU and float32 oracle equally far from the model (ratios 0.4-1.3), and no closer than at 50 sweeps -- 1000

@@ -435,3 +435,30 @@ def test_converged_complementarity(oracle_mod):
         print("  BOUND converged complementarity: %-32s largest %.2e <= %.0e" % (k, worst[k], b))
     for k, b in bounds.items():
         assert worst[k] <= b, (k, worst[k], b)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the sweep ladder: both references mean the same thing by "k sweeps"
+# ------------------------------------------------------------------------------------------------------------------
+LADDER = (1, 2, 3, 5, 10, 25)
+
+
+@pytest.mark.parametrize("k", LADDER)
+@pytest.mark.parametrize("switch", ["default", "cone_friction 0", "friction_directions 1"])
+@pytest.mark.parametrize("n", [16, 32])
+def test_sweep_ladder(oracle_mod, n, switch, k):
+    """n_iterations k without the residual exit, the same 8 ground states per (n, switch) at every k: sweep 1 takes the
+    non-contact rows backward and meets the friction rows while most normal impulses are still zero, sweep 2 takes them
+    forward with the bounds live.  Velocities to 1e-9 relative (largest observed 1.0e-10, on 32 links), both iteration counts k:
+    tests/test_gpu_np_sweeps.py holds the kernels to the model at these k."""
+    rng = np.random.default_rng(1900 + 7 * n + len(switch))
+    e = oracle_mod.OracleEnv(n_modules=n, residual_threshold=0.0, n_iterations=k, **SWITCHES[switch])
+    worst, contacts = 0.0, 0
+    for s in ground_states(rng, n, 8):
+        d = compare(e, s, rng.uniform(-0.5, 0.5, n))
+        assert d["iters"] == k and e.last_iterations == k, (d["iters"], e.last_iterations, k)
+        worst = max(worst, d["vel"])
+        contacts += d["nc"]
+    print("  BOUND %-58s largest %.2e <= 1e-09" % ("%d links, %s, %d sweeps: vel" % (n, switch, k), worst))
+    assert contacts >= 3 * 8
+    assert worst <= 1e-9, (n, switch, k, worst)
