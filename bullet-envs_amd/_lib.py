@@ -63,6 +63,10 @@ SYMBOLS = {
     "snk_record_floats": (C.c_int32, [_vp]),
     "snk_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
     "snk_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
+    "snk_reset_pose_floats": (C.c_int32, [_vp]),
+    "snk_set_reset_pose": (C.c_int, [_vp, _U8, _F]),
+    "snk_get_reset_pose": (C.c_int, [_vp, _F]),
+    "snk_set_reset_pose_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
     "snk_step_packed": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp]),
     "snk_trace_row_floats": (C.c_int32, [_vp]),
     "snk_step_traced": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
@@ -296,6 +300,36 @@ class Stepper:
             assert a.shape == (self.n_envs, self.n + 2)
         check(self.lib.snk_set_state(self.h, fptr(s) if s is not None else None, fptr(a) if a is not None else None),
               "snk_set_state")
+
+    def get_reset_pose(self):
+        """The reset-pose table (snk_get_reset_pose): [n_envs, 7 + n] = per env [position 3 | quaternion xyzw 4 | joint
+        angles n], what the env's next soft reset -- reset() or the step kernel's own on `done` -- lands on."""
+        p = np.zeros((self.n_envs, 7 + self.n), dtype=np.float32)
+        check(self.lib.snk_get_reset_pose(self.h, fptr(p)), "snk_get_reset_pose")
+        return p
+
+    def set_reset_pose(self, pose, mask=None):
+        """snk_set_reset_pose: rows [position 3 | quaternion xyzw 4 | joint angles n] for the envs of `mask` (None: all).
+        pose is [n_envs, 7 + n], or one row [7 + n] that every (masked) env gets.  Rows of unmasked envs are ignored."""
+        p = np.asarray(pose, dtype=np.float32)
+        if p.shape == (7 + self.n,):
+            p = np.broadcast_to(p, (self.n_envs, 7 + self.n))
+        if p.shape != (self.n_envs, 7 + self.n):
+            raise ValueError("reset pose must have shape (%d, %d) or (%d,), got %s"
+                             % (self.n_envs, 7 + self.n, 7 + self.n, np.shape(pose)))
+        p = np.ascontiguousarray(p)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if m.shape != (self.n_envs,):
+                raise ValueError("mask must have shape (%d,), got %s" % (self.n_envs, m.shape))
+        check(self.lib.snk_set_reset_pose(self.h, m.ctypes.data_as(_U8) if m is not None else None, fptr(p)),
+              "snk_set_reset_pose")
+
+    def set_reset_pose_device(self, pose_ptr, mask_ptr=0, stream=0):
+        """snk_set_reset_pose_dev: the same update from device buffers ([n_envs, 7 + n] f32, mask [n_envs] u8 or 0 for
+        all), asynchronous on `stream`; nothing is validated."""
+        check(self.lib.snk_set_reset_pose_dev(self.h, mask_ptr or None, pose_ptr, stream or None), "snk_set_reset_pose_dev")
 
     def get_manifold(self):
         """contact_model 1: [n_envs, 2n, 29] contact cache (see snk.h); None for a contact_model 0 handle."""

@@ -3,8 +3,9 @@
 The reference checkpoints only trainer state (`ppo/train.py:155-167`, `ars/train.py:171-173`);
 a PyBullet world cannot be resumed mid-rollout.  Here the whole simulator state of N
 environments is the per-env record (`snk_get_state`): pose, velocities, joint state, last
-motor torques, joint-0 force, previous x for the reward -- plus the per-env plane friction and
-the model parameters it was produced with.  Restoring it continues bit-for-bit.
+motor torques, joint-0 force, previous x for the reward -- plus the per-env plane friction, the
+per-env reset poses (`snk_get_reset_pose`: where the next episodes start) and the model parameters
+it was produced with.  Restoring it continues bit-for-bit.
 `save_state` / `load_state` synchronise the device (the state accessors of the C ABI do).
 """
 import numpy as np
@@ -46,7 +47,8 @@ def save_state(env, path):
                         ground_friction=st.get_ground_friction(),
                         manifold=np.zeros(0, np.float32) if mf is None else mf,
                         box_state=np.zeros(0, np.float32) if box is None else box[0],
-                        box_manifold=np.zeros(0, np.float32) if box is None else box[1])
+                        box_manifold=np.zeros(0, np.float32) if box is None else box[1],
+                        reset_pose=st.get_reset_pose())       # where the next episodes start (snk_set_reset_pose)
 
 
 def _check_params(z, st):
@@ -90,3 +92,11 @@ def load_state(env, path):
             st.set_manifold(z["manifold"])
         if "box_state" in z.files and z["box_state"].size:
             st.set_box(z["box_state"], z["box_manifold"])
+        # always restored, like the friction: a checkpoint from before the reset-pose table (no such entry) ran with the
+        # reference's defaults -- zeros and the unit quaternion -- and must also undo the target's own poses
+        if "reset_pose" in z.files:
+            st.set_reset_pose(z["reset_pose"])
+        else:
+            default = np.zeros(7 + st.n, np.float32)
+            default[6] = 1.0
+            st.set_reset_pose(default)

@@ -58,6 +58,7 @@ struct snk_handle {
     float* d_rows = nullptr;      // 32-link chains: constraint rows streamed from global memory (snk_device.hpp: pgs_v1)
     unsigned long long* d_ovf = nullptr;   // contacts the solves had no room for (snk_contact_overflow): 3 counters
     float* d_box = nullptr;       // obstacle 2: the free box of every env, [n_envs][kBoxFloats] (state 13, count, manifold 24)
+    float* d_reset = nullptr;     // the reset-pose table, [n_envs][reset_row_floats(n)] = [pos 3 | quat xyzw 4 | q n | padding]
     int32_t* d_order = nullptr;
     bool plan = true;
     // in-launch scheduler of env_step_sched_kernel (snk_device.hpp): rings, counters, the host-mapped alarm word
@@ -100,6 +101,9 @@ int dispatch(const snk_handle* h, F&& fn) {
 // floats per row of the trace buffer (snk_trace_row_floats): the payload [obs | link positions] in whole 128-byte lines
 int trace_row_floats(int n) { return (3 * n + 8 + 3 * (n + 1) + 31) / 32 * 32; }
 
+// floats per row of the reset-pose table (snk::kResetRow): the payload [pos 3 | quat 4 | q n] in whole 128-byte lines
+int reset_row_floats(int n) { return (7 + n + 31) / 32 * 32; }
+
 // packed_stride > 0 (snk_step_packed): obs rows of that stride, reward and done flag behind each row's observation.
 // TRACE (snk_step_traced): the kernels that also write `trace`, trace_rows rows per env.
 template <bool TRACE, class K>
@@ -112,6 +116,7 @@ int launch_step(K, snk_handle* h, float* act, float* obs, float* rew, uint8_t* d
     a.obs_stride = packed_stride > 0 ? packed_stride : h->D.obs_dim; a.packed = packed_stride > 0 ? 1 : 0; a.pad_ = 0;
     a.model = h->d_model; a.order = h->plan ? h->d_order : nullptr;
     a.trace = trace; a.trace_rows = trace_rows; a.trace_stride = trace_row_floats(h->n);
+    a.reset_all = h->d_reset;
     if (h->use_sched) {
         hipLaunchKernelGGL((snk::plan_sched_kernel<K::N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->sched,
                            h->n_envs);
@@ -134,7 +139,7 @@ int launch_substep(K, snk_handle* h, const float* tgt, int k, int32_t* info, hip
 template <class K>
 int launch_reset(K, snk_handle* h, const uint8_t* mask, float* obs, int hard, hipStream_t st) {
     hipLaunchKernelGGL((snk::reset_kernel<K::N, K::V2>), dim3(h->n_envs), dim3(64), h->lds_bytes, st, h->d_recs, mask, obs,
-                       hard, h->n_envs);
+                       h->d_reset, hard, h->n_envs);
     return 0;
 }
 // Waves of the step kernel a CU holds: __launch_bounds__(64, 2) = 2 per SIMD, 4 SIMDs, and the CU's LDS (160 KB on
@@ -419,6 +424,14 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
         HIP_TRY(hipMalloc(&h->d_box, b.size() * sizeof(float)));
         HIP_TRY(hipMemcpy(h->d_box, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    {
+        // the reset-pose table at the reference's defaults (snake.py:22-24): zeros, quaternion 0 0 0 1
+        const size_t R = (size_t)reset_row_floats(h->n);
+        std::vector<float> t(ne * R, 0.f);
+        for (size_t e = 0; e < ne; e++) t[e * R + 6] = 1.0f;
+        HIP_TRY(hipMalloc(&h->d_reset, t.size() * sizeof(float)));
+        HIP_TRY(hipMemcpy(h->d_reset, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     HIP_TRY(hipMalloc(&h->d_ovf, (snk::kOvfCounters + snk::kHistBins) * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(h->d_ovf, 0, (snk::kOvfCounters + snk::kHistBins) * sizeof(unsigned long long)));
     if (p->contact_model == 1) {
@@ -525,7 +538,7 @@ int snk_destroy(snk_handle* h) {
     (void)hipDeviceSynchronize();
     void* bufs[] = {h->d_model, h->d_recs, h->d_mu, h->d_act, h->d_obs, h->d_rew, h->d_done,
                     h->d_sub, h->d_mask, h->d_tgt, h->d_info, h->d_h, h->d_order, h->d_rows, h->d_linkpos, h->d_trace, h->d_mf, h->d_ovf, h->d_box,
-
+                    h->d_reset,
                     h->sched.head, h->sched.tail, h->sched.ent, h->sched.waiting, h->sched.counter, h->sched.finished};
     for (void* b : bufs) (void)hipFree(b);
     if (h->h_alarm) (void)hipHostFree(h->h_alarm);
@@ -730,6 +743,71 @@ int snk_set_state(snk_handle* h, const float* state, const float* aux) {
     }
     HIP_TRY(hipMemcpy(h->d_recs, recs.data(), recs.size() * sizeof(float), hipMemcpyHostToDevice));
     return 0;
+}
+
+int32_t snk_reset_pose_floats(const snk_handle* h) {
+    if (!h) { fail("snk_reset_pose_floats: null handle"); return 0; }
+    if (check_alarm(h)) return 0;
+    return 7 + h->n;
+}
+
+int snk_get_reset_pose(snk_handle* h, float* pose) {
+    if (!h || !pose) return fail("snk_get_reset_pose: null argument");
+    SNK_SYNC_ALIVE(h);
+    const size_t ne = (size_t)h->n_envs, R = (size_t)reset_row_floats(h->n), W = (size_t)(7 + h->n);
+    // (the padded rows to the caller's dense ones)
+    HIP_TRY(hipMemcpy2D(pose, W * sizeof(float), h->d_reset, R * sizeof(float), W * sizeof(float), ne, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int snk_set_reset_pose(snk_handle* h, const uint8_t* mask, const float* pose) {
+    if (!h || !pose) return fail("snk_set_reset_pose: null argument");
+    SNK_SYNC_ALIVE(h);
+    const size_t ne = (size_t)h->n_envs, R = (size_t)reset_row_floats(h->n), W = (size_t)(7 + h->n);
+    // validated before anything is written: a refused call leaves the table as it was
+    for (size_t e = 0; e < ne; e++) {
+        if (mask && !mask[e]) continue;
+        const float* r = pose + e * W;
+        char msg[200];
+        for (size_t i = 0; i < W; i++)
+            if (!std::isfinite(r[i])) {
+                if (i < 3) snprintf(msg, sizeof(msg), "snk_set_reset_pose: env %zu: position[%zu] is not finite", e, i);
+                else if (i < 7) snprintf(msg, sizeof(msg), "snk_set_reset_pose: env %zu: quaternion[%zu] is not finite", e, i - 3);
+                else snprintf(msg, sizeof(msg), "snk_set_reset_pose: env %zu: joint angle[%zu] is not finite", e, i - 7);
+                return fail(msg);
+            }
+        const double nq = std::sqrt((double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5] + (double)r[6] * r[6]);
+        if (std::fabs(nq - 1.0) > 1e-3) {
+            snprintf(msg, sizeof(msg), "snk_set_reset_pose: env %zu: quaternion has norm %.6g, not 1 (it is stored as given, "
+                     "not normalised)", e, nq);
+            return fail(msg);
+        }
+    }
+    if (!mask) {
+        HIP_TRY(hipMemcpy2D(h->d_reset, R * sizeof(float), pose, W * sizeof(float), W * sizeof(float), ne, hipMemcpyHostToDevice));
+        return 0;
+    }
+    // masked: the table read back (the device is idle), the masked rows patched on the host, one copy back
+    std::vector<float> t(ne * R);
+    HIP_TRY(hipMemcpy(t.data(), h->d_reset, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < ne; e++)
+        if (mask[e]) memcpy(&t[e * R], pose + e * W, W * sizeof(float));
+    HIP_TRY(hipMemcpy(h->d_reset, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int snk_set_reset_pose_dev(snk_handle* h, const uint8_t* mask_dev, const float* pose_dev, void* stream) {
+    if (!h || !pose_dev) return fail("snk_set_reset_pose_dev: null argument");
+    if (check_alarm(h)) return 1;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t total = (size_t)h->n_envs * (size_t)(7 + h->n);
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->n == 16)
+        hipLaunchKernelGGL((snk::reset_pose_copy_kernel<16>), dim3(blocks), dim3(256), 0, st, h->d_reset, mask_dev, pose_dev, h->n_envs);
+    else
+        hipLaunchKernelGGL((snk::reset_pose_copy_kernel<32>), dim3(blocks), dim3(256), 0, st, h->d_reset, mask_dev, pose_dev, h->n_envs);
+    return check_launch();
 }
 
 int32_t snk_manifold_floats(const snk_handle* h) { return (h && h->d_mf) ? 2 * h->n * 29 : 0; }

@@ -167,7 +167,8 @@ __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restri
 
 template <int N, bool V2>
 __global__ __launch_bounds__(64) void reset_kernel(float* __restrict__ recs, const uint8_t* __restrict__ mask,
-                                                   float* __restrict__ obs, int hard, int n_envs) {
+                                                   float* __restrict__ obs, const float* __restrict__ reset_all, int hard,
+                                                   int n_envs) {
     extern __shared__ float4 smem_raw[];
     using LT = Lds<N, V2>;
     LT& L = *reinterpret_cast<LT*>(smem_raw);
@@ -176,16 +177,29 @@ __global__ __launch_bounds__(64) void reset_kernel(float* __restrict__ recs, con
     if (env >= n_envs) return;
     if (mask && !mask[env]) return;
     load_rec(L, recs + (size_t)env * LT::REC, lane);
-    soft_reset(L, lane);
+    soft_reset(L, reset_row_of<N>(reset_all, env), lane);
     lds_sync();
     if (hard) {
         for (int i = 13 + 2 * N + lane; i < LT::REC; i += 64) L.rec[i] = 0.f;
         lds_sync();
     }
-    if (lane == 0) L.prev_x() = 0.0f;   // _observation = reset obs (SnakeGymEnv.py:30), x = 0
+    if (lane == 0) L.prev_x() = L.rec[0];   // _observation = reset obs (SnakeGymEnv.py:30): the pose's x
     lds_sync();
     if (obs) write_obs(L, obs + (size_t)env * (3 * N + 8), lane);
     store_rec(L, recs + (size_t)env * LT::REC, lane);
+}
+
+// snk_set_reset_pose_dev: rows of the caller's dense [n_envs][7 + N] device buffer into the padded table, for the envs
+// whose mask byte is set (null: all).  One thread per float of the payload; a row's padding is never touched.
+template <int N>
+__global__ __launch_bounds__(256) void reset_pose_copy_kernel(float* __restrict__ reset_all, const uint8_t* __restrict__ mask,
+                                                              const float* __restrict__ pose, int n_envs) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t env = t / (7 + N);
+    const int i = (int)(t - env * (7 + N));
+    if (env >= (size_t)n_envs) return;
+    if (mask && !mask[env]) return;
+    reset_all[env * kResetRow<N> + i] = pose[t];
 }
 
 template <int N, bool V2>
@@ -250,6 +264,9 @@ struct StepArgs {
     // trace[(e * trace_rows + s) * trace_stride] (write_trace_row).  Appended, like the two above
     float* trace;
     int32_t trace_rows, trace_stride;
+    // the reset-pose table (snk_set_reset_pose): [n_envs][kResetRow<N>], read by finish_env_step when an episode ends.
+    // Appended, like the three above
+    const float* reset_all;
 };
 typedef const StepArgs __attribute__((address_space(4))) * StepArgPtr;
 __device__ __forceinline__ StepArgPtr step_args() {
@@ -307,14 +324,15 @@ __device__ __forceinline__ void finish_env_step(LT& L, const DevModel& M, StepAr
     if (!(dn && vec_mode)) write_obs(L, ob, lane);
     lds_sync();
     if (dn) {
-        soft_reset(L, lane);
+        soft_reset(L, reset_row_of<N>(af->reset_all, env), lane);
         lds_sync();
         if (vec_mode) write_obs(L, ob, lane);   // worker returns env.reset()'s obs
     }
     lds_sync();
     if (lane == 0) {
-        // _observation = terminal obs (SnakeGymEnv.py:42); the worker's reset() refreshes it
-        L.prev_x() = (dn && vec_mode) ? 0.0f : x;
+        // _observation = terminal obs (SnakeGymEnv.py:42); the worker's reset() refreshes it (the reset pose's x, which
+        // soft_reset has just put into the record)
+        L.prev_x() = (dn && vec_mode) ? L.rec[0] : x;
         if (af->packed) {       // snk_step_packed: [obs | reward | done] rows (StepArgs::packed)
             ob[3 * N + 8] = r;
             reinterpret_cast<uint32_t*>(ob)[3 * N + 9] = dn ? 1u : 0u;

@@ -1,6 +1,6 @@
 // snk_env_io.hpp -- an environment's way between global memory and the LDS image: the state record, the contact cache
 // and the free box (plain or write-through, for a hand-off between waves), the per-workgroup / per-environment blocks,
-// the observation row and the soft reset.
+// the observation row, the reset-pose table and the soft reset.
 #pragma once
 #include "snk_contacts.hpp"
 #include "snk_lds.hpp"
@@ -180,12 +180,29 @@ __device__ __forceinline__ void write_obs(LT& L, float* __restrict__ obs, int la
         obs[i] = x;
     }
 }
+// The reset-pose table (snk_set_reset_pose): one row per environment, [pos 3 | quat xyzw 4 | q n | padding], kResetRow
+// floats = whole 128-byte lines (32 floats for 16 links, 64 for 32).  What Snake.initPosition, initOrientation and
+// initState are to the reference's soft reset (snake.py:22-24).
+template <int N>
+constexpr int kResetRow = (7 + N + 31) / 32 * 32;
+template <int N>
+__device__ __forceinline__ const float* reset_row_of(const float* __restrict__ reset_all, int env) {
+    return reset_all + (size_t)env * kResetRow<N>;
+}
+// `row`: the environment's row of the reset-pose table.  Only the wave that ends the episode reads it, and nothing
+// writes the table inside a launch: plain loads.
 template <class LT>
-__device__ __forceinline__ void soft_reset(LT& L, int lane) {
+__device__ __forceinline__ void soft_reset(LT& L, const float* __restrict__ row, int lane) {
     constexpr int N = LT::kN;
     lane = launder_lane(lane);
-    // snake.py:96-99,119-127: base pose/twist and joint q, qd; motor-torque and sensor caches persist [U]
-    for (int i = lane; i < 13 + 2 * N; i += 64) L.rec[i] = (i == 6) ? 1.0f : 0.0f;
+    // snake.py:96-99,119-127: resetBasePositionAndOrientation(initPosition, initOrientation) -- which zeroes the base
+    // twist [U] -- and resetJointState(initState[j]) for every motor (qd = 0); motor-torque and sensor caches persist [U]
+    for (int i = lane; i < 13 + 2 * N; i += 64) {
+        float v = 0.0f;
+        if (i < 7) v = row[i];
+        else if (i >= 13 && i < 13 + N) v = row[i - 6];
+        L.rec[i] = v;
+    }
 }
 
 }  // namespace snk

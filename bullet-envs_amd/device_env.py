@@ -103,6 +103,44 @@ class DeviceVecEnv(object):
     def set_ground_friction(self, mu):
         self.stepper.set_ground_friction(np.asarray(mu, dtype=np.float32))
 
+    def set_reset_pose(self, pose, mask=None):
+        """Where the envs of `mask` (None: all) start their next episodes, at reset() and at the auto-reset inside
+        step(): rows [initPosition 3 | initOrientation xyzw 4 | initState n] (snake.py:22-24, 119-127).
+        A CUDA tensor [E, 7 + n] float32 (mask: None or a CUDA uint8 / bool tensor [E], e.g. the `done` a step returned)
+        goes through snk_set_reset_pose_dev on the current stream: asynchronous, ordered with the steps enqueued there,
+        nothing validated.  Anything else (ndarray, list, CPU tensor) goes through the host form, which synchronises and
+        refuses non-finite values and non-unit quaternions."""
+        t = self.torch
+        W = 7 + self.stepper.n
+        if isinstance(pose, t.Tensor) and pose.is_cuda:
+            if pose.device != self.device or pose.dtype != t.float32 or tuple(pose.shape) != (self.num_envs, W):
+                raise ValueError("reset pose must be a float32 tensor of shape (%d, %d) on %s, got %s %s on %s"
+                                 % (self.num_envs, W, self.device, pose.dtype, tuple(pose.shape), pose.device))
+            pose = pose.contiguous()
+            mptr = 0
+            if mask is not None:
+                if not isinstance(mask, t.Tensor) or mask.device != self.device or tuple(mask.shape) != (self.num_envs,) \
+                        or mask.dtype not in (t.uint8, t.bool):
+                    raise ValueError("with a CUDA pose the mask must be a uint8 or bool tensor of shape (%d,) on %s"
+                                     % (self.num_envs, self.device))
+                mask = mask.contiguous()
+                mptr = mask.data_ptr()          # (a bool tensor is one byte per element, 0 / 1)
+            self.stepper.set_reset_pose_device(pose.data_ptr(), mptr, self._stream())
+            # the copy kernel reads `pose` / `mask` when the stream gets there: they stay alive until then
+            pose.record_stream(t.cuda.current_stream(self.device))
+            if mptr:
+                mask.record_stream(t.cuda.current_stream(self.device))
+            return
+        if isinstance(pose, t.Tensor):
+            pose = pose.numpy()
+        if isinstance(mask, t.Tensor):
+            mask = mask.cpu().numpy()
+        self.stepper.set_reset_pose(pose, mask)
+
+    def get_reset_pose(self):
+        """[E, 7 + n] float32 ndarray: the reset-pose table (synchronises the device)."""
+        return self.stepper.get_reset_pose()
+
     def close(self):
         self.stepper.close()
 
@@ -222,6 +260,22 @@ class ShardedVecEnv(object):
             self._pack[:, self.O] = rew
             self._pack.view(t.int32)[:, self.O + 1] = (t.as_tensor(done) != 0).to(t.int32)
         return self._gather()
+
+    def set_reset_pose(self, pose, mask=None):
+        """Every rank calls this with the GLOBAL arrays, pose [world * E, 7 + n] and mask [world * E] or None (host
+        data: ndarray or CPU tensor), and hands its own slice (shard_slice) to its local env through the host form.  No
+        communication: like set_ground_friction on the local envs, the data is the caller's on every rank."""
+        t = self.torch
+        pose = pose.cpu().numpy() if isinstance(pose, t.Tensor) else np.asarray(pose, dtype=np.float32)
+        if pose.ndim != 2 or pose.shape[0] != self.num_envs:
+            raise ValueError("reset pose must have %d rows (all ranks' envs), got shape %s" % (self.num_envs, pose.shape))
+        sl = self.shard_slice()
+        if mask is not None:
+            mask = mask.cpu().numpy() if isinstance(mask, t.Tensor) else np.asarray(mask)
+            if mask.shape != (self.num_envs,):
+                raise ValueError("mask must have shape (%d,), got %s" % (self.num_envs, mask.shape))
+            mask = mask[sl]
+        self.env.set_reset_pose(np.ascontiguousarray(pose[sl]), mask)
 
     def close(self):
         if hasattr(self.env, "close"):

@@ -73,6 +73,12 @@ class Snake(object):
         self._timeStep = 1 / 100.0                       # snake.py:9,19
         self.counter = 0
         self.START_POSITION = [0, 0, 0]
+        # where every SOFT reset puts the snake (snake.py:22-24; read by resetPose / resetPositionOrientation,
+        # snake.py:119-127): joint angles, base position, base orientation (quaternion xyzw).  Assign or mutate them
+        # between resets; they stay on this object across a hard reset, which itself loads at the zero pose (snake.py:93)
+        self.initState = [0] * n_modules
+        self.initPosition = [0] * 3
+        self.initOrientation = [0, 0, 0, 1]
         self.endDue2Height = False
         self._args = args
         if args is not None:
@@ -114,6 +120,17 @@ class Snake(object):
 
     def getObservationLowerBound(self):
         return -self.getObservationUpperBound()
+
+    def reset_pose_row(self):
+        """[initPosition 3 | initOrientation 4 | initState n] as the float32 row of the handle's reset-pose table
+        (snk_set_reset_pose)."""
+        pos = np.asarray(self.initPosition, dtype=np.float32).reshape(-1)
+        orn = np.asarray(self.initOrientation, dtype=np.float32).reshape(-1)
+        q = np.asarray(self.initState, dtype=np.float32).reshape(-1)
+        if pos.shape != (3,) or orn.shape != (4,) or q.shape != (self.numMotors,):
+            raise ValueError("Snake: initPosition / initOrientation / initState must hold 3 / 4 / %d values, got %d / %d / %d"
+                             % (self.numMotors, pos.size, orn.size, q.size))
+        return np.concatenate([pos, orn, q])
 
     def _need_env(self):
         if self._env is None:
@@ -239,6 +256,7 @@ class SnakeGymEnv(object):
         self._action_bound = 1
         self.params = params_from_args(args, n_modules=n_modules, **over)
         self._stepper = _lib.Stepper(1, device=device, params=self.params)   # = hard reset
+        self._pushed_pose = None          # the robot's init* as the handle's table holds them (None: the defaults)
         self.robot._env = self
         self._observation = self._get_obs()
         self.defObservationSpace()
@@ -248,16 +266,26 @@ class SnakeGymEnv(object):
     def _get_obs(self):
         return self._stepper.get_obs()[0].astype(np.float64)
 
+    def _push_reset_pose(self):
+        """The robot's initPosition / initOrientation / initState into the handle's reset-pose table, when they differ
+        from what it holds: the reference reads them at every soft reset (snake.py:119-127), the kernels read the table."""
+        row = self.robot.reset_pose_row()
+        if self._pushed_pose is None or not np.array_equal(row.view(np.uint32), self._pushed_pose.view(np.uint32)):
+            self._stepper.set_reset_pose(row)
+            self._pushed_pose = row
+
     def _reset_robot(self, hardReset):
         if hardReset:
             self._stepper.close()
             self._stepper = _lib.Stepper(1, device=self._stepper.device, params=self.params)
+            self._pushed_pose = None      # (a new handle: the default table, and the zero pose, snake.py:93)
             # the test-mode replay handle was built for the old world (params, obstacle, contact cache): a new one is
             # made on the next test-mode step
             if getattr(self, "_scratch", None) is not None:
                 self._scratch.close()
                 self._scratch = None
         else:
+            self._push_reset_pose()
             self._stepper.reset()
 
     # --- SnakeGymEnv API ---
@@ -271,6 +299,9 @@ class SnakeGymEnv(object):
         a32 = np.ascontiguousarray(np.asarray(action, dtype=np.float32).reshape(1, -1))
         if a32.shape[1] != self._stepper.act_dim:
             raise SystemError("Action not executed!")
+        # SnakeGymEnv.step's own reset on done (SnakeGymEnv.py:39-41) happens inside the step kernel: the pose it reads
+        # must be the robot's current one
+        self._push_reset_pose()
         traced = self.mode == 'test' and self.telemetry == 'kernel'
         if self.mode == 'test' and not traced:
             before = self._stepper.get_state() + (self._stepper.get_manifold(),
@@ -557,6 +588,17 @@ class SnakeVecEnv(VecEnv):
     def reset(self):
         return self._stepper.reset()
 
+    def set_reset_pose(self, pose, mask=None):
+        """Where the envs of `mask` (None: all) start their next episodes -- at reset() and at the auto-reset inside
+        step(): pose [num_envs, 7 + n] (or one row for all) = [initPosition 3 | initOrientation xyzw 4 | initState n],
+        the per-env form of the three attributes the reference's Snake reads at every soft reset (snake.py:22-24,
+        119-127).  Rows of unmasked envs are ignored."""
+        self._stepper.set_reset_pose(pose, mask)
+
+    def get_reset_pose(self):
+        """[num_envs, 7 + n]: the rows set_reset_pose set (after construction: zeros and the unit quaternion)."""
+        return self._stepper.get_reset_pose()
+
     def reset_task(self):
         return self.reset()
 
@@ -585,6 +627,12 @@ class SubprocVecEnv(SnakeVecEnv):
     len(env_fns) environments are then created on the GPU in one handle.  Thunks that build
     mode='test' envs get what the reference's workers would send: every env's info carries its
     per-substep telemetry (SnakeVecEnv._telemetry).
+
+    A thunk's robot may carry its own initPosition / initOrientation / initState (snake.py:22-24): per-env data, not a
+    parameter, so thunks may differ in it and env i starts its episodes from thunk i's pose.  LIMIT: beyond kHeteroProbe
+    thunks only a sample of them is called; the others are called as well -- for their poses only -- when one of the SAMPLED
+    robots carries a pose other than the default.  A pose set on unsampled thunks alone is therefore not seen: with more
+    than kHeteroProbe envs hand the poses over with set_reset_pose(pose, mask) instead, which needs no thunk at all.
     """
 
     #: every thunk is called and compared up to this many; beyond it the first, the last and kHeteroProbe - 2 evenly
@@ -601,10 +649,13 @@ class SubprocVecEnv(SnakeVecEnv):
         else:
             probe = sorted(set([0, n - 1] + [int(round(i * (n - 1) / (self.kHeteroProbe - 1.0))) for i in range(self.kHeteroProbe)]))
         params = mode = tel = None
+        poses = {}      # env index -> its robot's reset pose (per-env data: thunks may differ in it)
         for i in probe:
             fn = env_fns[i]
             proto = (fn.x if isinstance(fn, CloudpickleWrapper) else fn)()
             p_i = getattr(proto, "params", None)
+            if hasattr(getattr(proto, "robot", None), "reset_pose_row"):
+                poses[i] = proto.robot.reset_pose_row()
             m_i = getattr(proto, "mode", "train")
             t_i = getattr(proto, "telemetry", "replay")
             if hasattr(proto, "close"):
@@ -632,3 +683,21 @@ class SubprocVecEnv(SnakeVecEnv):
         # test mode's telemetry source: the argument, else what the thunks' envs were built with
         SnakeVecEnv.__init__(self, n, device=device, params=params, mode=mode,
                              telemetry=telemetry if telemetry is not None else tel)
+        # Each worker of the reference resets ITS robot to that robot's initPosition / initOrientation / initState
+        # (snake.py:119-127): every env gets the row of its own thunk's robot.  Beyond kHeteroProbe thunks the others are
+        # called too, but only when a probed one carries a pose of its own (a thunk builds a one-env handle).
+        default = self._stepper.get_reset_pose()
+        if any(not np.array_equal(row, default[i]) for i, row in poses.items()):
+            for i in range(n):
+                if i not in poses:
+                    fn = env_fns[i]
+                    proto = (fn.x if isinstance(fn, CloudpickleWrapper) else fn)()
+                    if hasattr(getattr(proto, "robot", None), "reset_pose_row"):
+                        poses[i] = proto.robot.reset_pose_row()
+                    if hasattr(proto, "close"):
+                        proto.close()
+            mask = np.zeros(n, dtype=np.uint8)
+            for i, row in poses.items():
+                default[i] = row
+                mask[i] = 1
+            self.set_reset_pose(default, mask)

@@ -162,7 +162,9 @@ int32_t snk_record_floats(const snk_handle* h); /* floats per env in the HBM sta
 
 /* Replaces SnakeGymEnv.reset() (SnakeGymEnv.py:28-31 -> snake.py:96-99,119-127) for every
  * env whose mask byte is non-zero (mask == NULL: all).  obs_dev [n_envs x obs_dim] f32,
- * device pointer; rows of unmasked envs are left untouched.  stream = hipStream_t or NULL. */
+ * device pointer; rows of unmasked envs are left untouched.  stream = hipStream_t or NULL.
+ * The env lands on ITS row of the reset-pose table (snk_set_reset_pose below; after snk_create: zeros and the unit
+ * quaternion), with zero base twist and joint velocities; the reward's previous x becomes the pose's x. */
 int snk_reset(snk_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream);
 
 /* Replaces SubprocVecEnv.step (ppo/multiprocessing_env.py:119-128) = per env
@@ -184,6 +186,43 @@ int snk_reset(snk_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stre
  * substep builds its motor rows in a batch of their own at every contact count: cross-checks), all read by snk_create. */
 int snk_step(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev,
              uint8_t* done_dev, int32_t* substeps_dev, int32_t vec_mode, void* stream);
+
+/* The reset-pose table: what Snake.initPosition, Snake.initOrientation and Snake.initState (snake.py:22-24) are to the
+ * reference's soft reset -- resetPositionOrientation (snake.py:126-127) and resetPose (snake.py:119-124) read them at
+ * every reset -- held per environment on the device, because the reset of a finished episode happens inside the step
+ * kernel (SnakeGymEnv.py:39-41).  One row per env: [position 3 | orientation quaternion xyzw 4 | joint angles n].
+ * snk_create fills the reference's defaults (zeros, quaternion 0 0 0 1); the state right after snk_create is the zero
+ * pose whatever is set later (the hard reset loads the snake at [0,0,0]: snake.py:93).  snk_reset and the auto-reset of
+ * snk_step / snk_step_packed / snk_step_traced put an env on its row: pose as given, base twist zero
+ * (resetBasePositionAndOrientation [U]), q = the row's angles, qd = 0 (resetJointState); motor torques, the joint-0
+ * force, the contact cache and a free box persist.  The reward's previous x (SnakeGymEnv.py:30, 91) becomes the row's x
+ * after snk_reset and after a vec_mode 1 auto-reset; vec_mode 0 keeps the terminal x (SnakeGymEnv.py:41-42).
+ *
+ * snk_reset_pose_floats (replaces len(initPosition) + len(initOrientation) + len(initState), snake.py:22-24): 7 + n, the
+ * length of a caller-side row (the device rows are padded to whole 128-byte lines; callers never see that).
+ *
+ * snk_set_reset_pose (replaces assigning robot.initPosition / initOrientation / initState, snake.py:22-24): host
+ * buffers; mask [n_envs] bytes (NULL: all), pose [n_envs x (7 + n)].  Synchronises the device first, like the state
+ * accessors.  Rows of unmasked envs are neither read nor written.  Refused, with the env and the field named, and with
+ * nothing written: a non-finite value; a quaternion whose norm differs from 1 by more than 1e-3.  The quaternion is
+ * stored as given, not normalised.  Joint angles outside [joint_lo, joint_hi] are accepted: resetJointState does not
+ * clamp, and the limit rows act on the next substep.
+ *
+ * snk_get_reset_pose (replaces reading the three attributes back, snake.py:22-24): host buffer [n_envs x (7 + n)].
+ *
+ * snk_set_reset_pose_dev (replaces the same assignment, snake.py:22-24, for a trainer whose data never leaves the GPU):
+ * mask_dev [n_envs] bytes (NULL: all) and pose_dev [n_envs x (7 + n)] f32 are DEVICE pointers; a small copy kernel,
+ * asynchronous on `stream` (hipStream_t or NULL) and therefore ordered with the steps and resets enqueued there -- e.g. new
+ * poses for exactly the envs whose done flag the last step set, before the next step, without touching the host.  The
+ * values cannot be validated here: a non-finite value or a non-unit quaternion goes into the table as it is, and into
+ * the env's state at its next reset.
+ *
+ * All four refuse a null handle and a poisoned one (snk_debug_raise_alarm) with snk_last_error() set:
+ * snk_reset_pose_floats by returning 0, the others by returning non-zero. */
+int32_t snk_reset_pose_floats(const snk_handle* h);
+int snk_set_reset_pose(snk_handle* h, const uint8_t* mask /* host, NULL: all */, const float* pose /* host [n_envs x (7+n)] */);
+int snk_get_reset_pose(snk_handle* h, float* pose /* host [n_envs x (7+n)] */);
+int snk_set_reset_pose_dev(snk_handle* h, const uint8_t* mask_dev, const float* pose_dev, void* stream);
 
 /* The same step with ONE output buffer: packed_dev [n_envs x row_stride] f32 (row_stride >= obs_dim + 2), row e =
  * [obs of env e (obs_dim floats) | reward (f32) | done (u32: 0 or 1) | untouched padding].  This is the block a rank of a
@@ -307,8 +346,9 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
 /* Test hook for the failure path: raises this handle's alarm from the HOST -- the host-mapped word a wave of the step
  * kernel sets when one of its bounded waits runs out (nothing waits, nothing hangs).  Afterwards the handle behaves as
  * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
- * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction) return
- * non-zero with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
+ * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction,
+ * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) return
+ * non-zero -- and snk_reset_pose_floats 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */
 int snk_debug_raise_alarm(snk_handle* h);
