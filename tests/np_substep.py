@@ -20,12 +20,15 @@ Jacobians and mass matrix:
 * v = clamp(v_free + dv); q += dt qd, origin += dt v, the base quaternion by the exponential map with the angular
   motion limit of pi/4 per substep;
 * the order in which the solver meets the ground manifolds (`contact_order` 1 / 2 / k >= 3) from the link-ordered list:
-  `manifold_order`.
+  `manifold_order`;
+* warm starting (`warm_start 1`): the normal row of a contact starts at warmstarting_factor x the impulse its cached
+  point carried into the substep (`lam0`, one per contact), and the solve's velocity change starts at the sum of
+  M^-1 J^T of those starts; friction and non-contact rows start at zero.
 
-The contact list (points, depths, links, normals) is an input: contact generation has its own tests.
+The contact list (points, depths, links, normals) is an input, and so is `lam0`: tests/np_manifold.py is the model of
+the contact cache that yields both for the ground contacts.
 
 Out of scope (the callers do not ask for it):
-* warm starting (`warm_start 1`): the cached impulse each solved point started from is not exposed;
 * the free box (`obstacle 2`);
 * `noncontact_order 1`;
 * the joint-0 force sensor's constraint pass (obs[55]): its [U] rules are themselves open.
@@ -237,9 +240,10 @@ def _resolve(r, dv):
     return dI / r.dinv if r.dinv != 0 else 0.0
 
 
-def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_threshold=None):
+def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_threshold=None, lam0=None):
     """One substep from state s = [pos, quat xyzw, w, v, q, qd] with motor targets, on the contact list `contacts`
-    ([nc, 12]: P, dist, link, linkB (-1 ground, -2 the static box, >= 0 a link), normal, PB) in solve order.
+    ([nc, 12]: P, dist, link, linkB (-1 ground, -2 the static box, >= 0 a link), normal, PB) in solve order; lam0
+    [nc]: the impulse each contact's cached point carried (read only under warm_start 1; None: all zero).
     Returns a dict: state (after the substep), v_free, normal / friction / limit / motor impulses, motor torques
     (impulse / dt), iterations, and the rows themselves (for complementarity checks)."""
     ch = Chain(p)
@@ -314,6 +318,10 @@ def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_t
         pairs.append(fr)
 
     dv = np.zeros(nd)
+    if int(p.warm_start) and lam0 is not None:
+        for r0, l0 in zip(normals, np.asarray(lam0, float)):
+            r0.applied = float(p.warmstarting_factor) * l0
+            dv += r0.Mi * r0.applied
     iters = 0
     nn = len(noncontact)
     one_dir = int(p.friction_directions) == 1

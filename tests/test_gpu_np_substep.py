@@ -19,6 +19,7 @@ until the mark is removed.
 import numpy as np
 import pytest
 
+import np_manifold as nm
 import np_substep as ns
 from conftest import f32_gate, random_state
 
@@ -71,7 +72,13 @@ def _run(pkg, oracle_mod, name, n, S, T, over=None, mu=None, M=None, check_iters
         assert info[i, 1] == o.last_num_contacts == len(C), (name, i, info[i], len(C))
         if check_iters:
             assert info[i, 0] == o.last_iterations, (name, i, info[i], o.last_iterations)
-        r = ns.substep(o.params, s64, t64, C, mu_plane=1.0 if mu is None else float(np.float32(mu)))
+        lam0 = None
+        if over.get("warm_start"):
+            # the impulse every ground contact starts from: the cache model on the same float32-rounded cache
+            lam0 = nm.update_env(o.params, s64, np.asarray(M[i], np.float32).astype(np.float64))["contacts"][:, 5]
+            assert len(lam0) == (C[:, 5] == -1).sum(), (name, i, len(lam0), len(C))
+            lam0 = np.concatenate([lam0, np.zeros(len(C) - len(lam0))])
+        r = ns.substep(o.params, s64, t64, C, mu_plane=1.0 if mu is None else float(np.float32(mu)), lam0=lam0)
         x = r["state"]
         sc = max(1.0, np.abs(r["tau_motor"]).max())
         ev.append(_rel(G[i].astype(np.float64), x, n))
@@ -227,6 +234,36 @@ def test_static_box(pkg, oracle_mod):
     nc = _run(pkg, oracle_mod, "16 links against the static box", 16, np.array(S), rng.uniform(-0.5, 0.5, (12, 16)),
               dict(BOX, residual_threshold=0.0), M=np.array(M))
     assert nc > 12
+
+
+@pytest.mark.parametrize("path", [p[0] for p in PATHS])
+def test_warm_start(pkg, oracle_mod, monkeypatch, path):
+    """warm_start 1: states of a short gait run handed over with their caches, whose points carry non-zero impulses;
+    the normal rows start at warmstarting_factor x those (np_substep's lam0, from the cache model np_manifold).
+
+    State 6 of the 16-link runs is not such a state: its episode ended in the fourth env-step, so it is the reset pose
+    itself (straight snake, zero velocity, 32 fresh points, every start impulse 0).  There the float32 oracle and the
+    kernels sit 1.17 (under the torques drawn for the register-resident case) and 4.6e-2 (under the streamed-row
+    case's) of a velocity from the model, alike: the roll rate about the long axis, which 32 collinear contact pairs leave to friction alone.  The model's
+    own spread on that state under additive input noise of one float32 ulp is 1.0e-4 / 5.6e-5 at worst (3e-12 under
+    1e-15), so by the rule of tests/test_np_substep.py it is no bifurcation of the model: it is float32 arithmetic
+    inside the 50 sweeps, which oracle and kernels share; on the other eleven states the float32 oracle is within
+    7.3e-4 of the model."""
+    from bench import gait_actions
+    n, streamed = _path(monkeypatch, path)
+    rng = np.random.default_rng(1650 + n + 7 * streamed)
+    e = oracle_mod.OracleEnv(n_modules=n, warm_start=1)
+    S, M = [], []
+    for i in range(12 if n == 16 else 8):
+        e.hard_reset()
+        e.reset()
+        for j in range(3 + i % 5):
+            e.env_step(gait_actions(np.array([i + 1]), j, e.act_dim)[0], vec_mode=True)
+        S.append(e.get_state())
+        M.append(e.get_manifold())
+    assert np.abs(np.array(M)[:, :, 7::7]).max() > 1e-4
+    _run(pkg, oracle_mod, "%s, warm start" % path, n, np.array(S), rng.uniform(-0.5, 0.5, (len(S), n)),
+         dict(residual_threshold=0.0, warm_start=1), M=np.array(M))
 
 
 @pytest.mark.parametrize("path", [p[0] for p in PATHS[:2]] + [pytest.param("32 links", marks=_open(

@@ -68,7 +68,7 @@ def _errors(n, x, N, tau, ref, Nref, tauref):
     return d
 
 
-def compare(e, s, T, mu_plane=1.0, manifold=None):
+def compare(e, s, T, mu_plane=1.0, manifold=None, lam0=None):
     """One oracle substep from (s, manifold) and the numpy model on the contacts the oracle solved.
 
     A figure beyond its bound is a finding unless the state is a bifurcation for THAT figure: the numpy model itself, run
@@ -88,7 +88,9 @@ def compare(e, s, T, mu_plane=1.0, manifold=None):
     tau = e.get_aux()[0]
     N = e.last_normal_impulses()
     assert len(N) == len(C)
-    r = ns.substep(e.params, s, T, C, mu_plane=mu_plane)
+    if lam0 is not None:
+        lam0 = np.concatenate([lam0, np.zeros(len(C) - len(lam0))])      # link-link / box contacts carry none
+    r = ns.substep(e.params, s, T, C, mu_plane=mu_plane, lam0=lam0)
     d = _errors(n, r["state"], r["normal"], r["tau_motor"], ref, N, tau)
     d.update(nc=len(C), iters=r["iterations"], r=r, C=C, ref=ref, excused={})
     assert r["iterations"] == e.last_iterations, (r["iterations"], e.last_iterations)
@@ -97,7 +99,7 @@ def compare(e, s, T, mu_plane=1.0, manifold=None):
         spread = dict.fromkeys(BOUNDS, 0.0)
         for _ in range(2):
             s2 = s * (1 + 1e-15 * rng.uniform(-1, 1, s.shape))
-            r2 = ns.substep(e.params, s2, T, C, mu_plane=mu_plane)
+            r2 = ns.substep(e.params, s2, T, C, mu_plane=mu_plane, lam0=lam0)
             e2 = _errors(n, r2["state"], r2["normal"], r2["tau_motor"], r["state"], r["normal"], r["tau_motor"])
             for k in BOUNDS:
                 spread[k] = max(spread[k], e2[k])
@@ -193,6 +195,39 @@ def test_substep_gait_states(oracle_mod, n):
         e = oracle_mod.OracleEnv(n_modules=n, **over)
         for s, m in gait_states(oracle_mod, n, 3 if n == 16 else 2):
             w.add(compare(e, s, rng.uniform(-0.5, 0.5, n), manifold=m))
+    w.check()
+
+
+def warm_states(oracle_mod, n, k):
+    """(state, cache, lam0) from a short gait run under warm_start 1: populated caches with non-zero impulses; lam0 per
+    ground contact from the cache model (np_manifold), which must hold the points the oracle then solves."""
+    import np_manifold as nm
+    out = []
+    p = oracle_mod.default_params(n_modules=n, warm_start=1)
+    for s, m in gait_states(oracle_mod, n, k, warm_start=1):
+        c = nm.update_env(p, s, m)["contacts"]
+        assert np.abs(m[:, 7::7]).max() > 1e-4 and np.abs(c[:, 5]).max() > 1e-4
+        out.append((s, m, c[:, 5]))
+    return out
+
+
+@pytest.mark.parametrize("n", [16, 32])
+def test_substep_warm_start(oracle_mod, n):
+    """warm_start 1 from gait states with their caches, both chain lengths (the float64 oracle is one program for the
+    three GPU paths; tests/test_gpu_np_substep.py runs the same states on each of them)."""
+    rng = np.random.default_rng(250 + n)
+    w = Worst("%d links, warm start" % n)
+    moved = 0.0
+    for over in ({}, dict(residual_threshold=0.0)):
+        e = oracle_mod.OracleEnv(n_modules=n, warm_start=1, **over)
+        for s, m, lam0 in warm_states(oracle_mod, n, 3 if n == 16 else 2):
+            T = rng.uniform(-0.5, 0.5, n)
+            d = compare(e, s, T, manifold=m, lam0=lam0)
+            assert (d["C"][:len(lam0), 5] == -1).all() and (d["C"][len(lam0):, 5] != -1).all()
+            w.add(d)
+            cold = ns.substep(e.params, s, T, d["C"], lam0=None)["state"]
+            moved = max(moved, np.abs(cold[13 + n:] - d["r"]["state"][13 + n:]).max())
+    assert moved > 1e-6, moved                 # the start impulses are not a no-op on these states
     w.check()
 
 
