@@ -100,8 +100,27 @@ SYMBOLS = {
     "snk_timing_read": (C.c_int, [_vp, _D, _I32]),
     "snk_model_describe": (C.c_int, [_vp, _D, _D]),
     "snk_params_derived": (C.c_int, [C.c_void_p, _D]),
+    "snk_render": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "snk_render_host": (C.c_int, [_vp, _I32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _U8, _F, _I32]),
+    "snk_view_matrix_ypr": (C.c_int, [_F, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _F]),
+    "snk_projection_fov": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, _F]),
     "snk_last_error": (C.c_char_p, []),
 }
+RENDER_SHADOW = 1      # SNK_RENDER_SHADOW
+
+#: the camera behind render() / getCameraImage when the caller gives no matrices [U]: the reference calls
+#: resetDebugVisualizerCamera(1.5, -30, -90, [1.28, 0, 0]) right before its getCameraImage (snake.py:322-327) -- the reading
+#: that shows what its author meant; PyBullet's own headless default cannot be known here.  fov 60, near 0.01, far 100.
+DEFAULT_CAMERA = dict(distance=1.5, yaw=-30.0, pitch=-90.0, target=(1.28, 0.0, 0.0), fov=60.0, near=0.01, far=100.0)
+
+
+def default_camera(width, height, distance=None, yaw=None, pitch=None, target=None):
+    """(view16, proj16) of the [U] default camera for a width x height image; the four arguments override what the last
+    resetDebugVisualizerCamera said."""
+    d = DEFAULT_CAMERA
+    view = view_matrix_ypr(d["target"] if target is None else target, d["distance"] if distance is None else distance,
+                           d["yaw"] if yaw is None else yaw, d["pitch"] if pitch is None else pitch, 0.0, 2)
+    return view, projection_fov(d["fov"], float(width) / float(height), d["near"], d["far"])
 
 _lib = None
 
@@ -177,6 +196,36 @@ def reach_bound(params=None, **over):
 
 def fptr(a):
     return a.ctypes.data_as(_F)
+
+
+def view_matrix_ypr(target, distance, yaw, pitch, roll=0.0, up_axis=2):
+    """snk_view_matrix_ypr: PyBullet's computeViewMatrixFromYawPitchRoll [U], a column-major float32 16-vector."""
+    t = np.ascontiguousarray(target, dtype=np.float32)
+    if t.shape != (3,):
+        raise ValueError("camera target must hold 3 values, got %s" % (t.shape,))
+    out = np.zeros(16, np.float32)
+    check(load().snk_view_matrix_ypr(fptr(t), float(distance), float(yaw), float(pitch), float(roll), int(up_axis), fptr(out)),
+          "snk_view_matrix_ypr")
+    return out
+
+
+def projection_fov(fov, aspect, near, far):
+    """snk_projection_fov: PyBullet's computeProjectionMatrixFOV [U], a column-major float32 16-vector (far == near gives
+    the infinite entries the formula gives; nothing raises)."""
+    out = np.zeros(16, np.float32)
+    check(load().snk_projection_fov(float(fov), float(aspect), float(near), float(far), fptr(out)), "snk_projection_fov")
+    return out
+
+
+def camera_block(view, proj, n_images):
+    """([k, 32] float32 camera array, shared flag) from view / proj given as one 16-vector each (shared by every image)
+    or as [n_images, 16] each."""
+    v = np.asarray(view, dtype=np.float32).reshape(-1, 16)
+    p = np.asarray(proj, dtype=np.float32).reshape(-1, 16)
+    if v.shape[0] != p.shape[0] or v.shape[0] not in (1, n_images):
+        raise ValueError("view / proj must be one 16-vector each or [%d, 16] each, got %s / %s"
+                         % (n_images, np.shape(view), np.shape(proj)))
+    return np.ascontiguousarray(np.concatenate([v, p], axis=1)), v.shape[0] == 1
 
 
 def trace_row_floats(n_modules):
@@ -450,6 +499,32 @@ class Stepper:
 
     def reset_device(self, mask_ptr=0, obs_ptr=0, stream=0):
         check(self.lib.snk_reset(self.h, mask_ptr or None, obs_ptr or None, stream or None), "snk_reset")
+
+    # ---- the ray caster (snk_render / snk_render_host) ----
+    def render(self, view, proj, width, height, env_ids=None, shadow=False, depth=True, seg=True):
+        """snk_render_host: images of the envs `env_ids` (None: all; ids may repeat, any order) from their current state.
+        view / proj: column-major 16-vectors, one pair shared by every image or [n_images, 16] each.  Returns
+        (rgba [k, height, width, 4] uint8, depth [k, height, width] float32 or None, seg int32 primitive ids or None)."""
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        k = self.n_envs if ids is None else len(ids)
+        cams, shared = camera_block(view, proj, k)
+        W, H = int(width), int(height)
+        ok = 1 <= W <= 4096 and 1 <= H <= 4096 and k >= 1        # (the library refuses the rest by name; no huge buffers first)
+        rgba = np.zeros((k, H, W, 4) if ok else (1,), np.uint8)
+        dep = np.zeros((k, H, W), np.float32) if depth and ok else None
+        sg = np.zeros((k, H, W), np.int32) if seg and ok else None
+        check(self.lib.snk_render_host(self.h, ids.ctypes.data_as(_I32) if ids is not None else None, k, fptr(cams),
+                                       1 if shared else 0, W, H, RENDER_SHADOW if shadow else 0,
+                                       rgba.ctypes.data_as(_U8), fptr(dep) if dep is not None else None,
+                                       sg.ctypes.data_as(_I32) if sg is not None else None), "snk_render_host")
+        return rgba, dep, sg
+
+    def render_device(self, ids_ptr, n_images, cams_ptr, shared, width, height, flags, rgba_ptr, depth_ptr=0, seg_ptr=0,
+                      stream=0):
+        """snk_render: every buffer a device pointer (0: none), asynchronous on `stream`."""
+        check(self.lib.snk_render(self.h, ids_ptr or None, int(n_images), cams_ptr or None, 1 if shared else 0, int(width),
+                                  int(height), int(flags), rgba_ptr or None, depth_ptr or None, seg_ptr or None,
+                                  stream or None), "snk_render")
 
     def timing_enable(self, capacity):
         check(self.lib.snk_timing_enable(self.h, int(capacity)), "snk_timing_enable")

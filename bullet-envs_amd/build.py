@@ -13,8 +13,12 @@ LIB = os.path.join(HERE, "libsnk.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "snk.h")
 
 
+RENDER_OBJ = os.path.join(HERE, "snk_render.o")
+
+
 def sources():
-    """Every file under csrc/ is a dependency of the one translation unit (snk_api.hip includes the rest): a stale
+    """Every file under csrc/ is a dependency of the library (snk_api.hip includes the step kernels' headers, snk_render.hip
+    the layers it reuses): a stale
     libsnk.so after an edit of ANY of them would travel to the GPU box unnoticed (it is git-ignored, not gpurun-ignored)."""
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".h")))
 
@@ -38,8 +42,21 @@ def _command(out, defines=(), extra=()):
         ["-D" + d for d in defines] + list(extra)
 
 
+def _render_command(obj, defines=(), extra=()):
+    """The renderer's translation unit (csrc/snk_render.hip), compiled to an object of its own -- its kernels are a code
+    object apart from the step kernels' -- which the library's command then links in."""
+    return [_hipcc()] + FLAGS + ["-c", "-fPIC", os.path.join(CSRC, "snk_render.hip"), "-o", obj] + \
+        ["-D" + d for d in defines] + list(extra)
+
+
 def _stamp(out):
     return out + ".cmd"
+
+
+def _render_stamp(out):
+    """libsnk.so.cmd stays the command of the step kernels' translation unit alone, flags and source (the pinned bits of
+    tests/test_gpu_bits.py are keyed by it and by the toolchain); the renderer's object has a stamp of its own."""
+    return out + ".render.cmd"
 
 
 def toolchain_text():
@@ -70,7 +87,10 @@ def needs_build(cmd=None):
         return True
     try:
         with open(_stamp(LIB)) as f:
-            return f.read() != _stamp_text(cmd if cmd is not None else _command(LIB))
+            if f.read() != _stamp_text(cmd if cmd is not None else _command(LIB)):
+                return True
+        with open(_render_stamp(LIB)) as f:
+            return f.read() != _stamp_text(_render_command(RENDER_OBJ))
     except OSError:
         return True
 
@@ -90,13 +110,18 @@ def build(force=False, verbose=False, defines=(), out=None):
             with open(LIB + ".toolchain", "w") as f:
                 f.write(toolchain_text())
         return LIB
-    run = list(cmd)
-    if verbose:
-        run.insert(1, "-Rpass-analysis=kernel-resource-usage")
-        print(" ".join(run))
-    subprocess.check_call(run)
+    obj = RENDER_OBJ if out is None else os.path.splitext(target)[0] + "_render.o"
+    rcmd = _render_command(obj, defines, extra)
+    run = [cmd[0], obj] + list(cmd[1:])      # (the object first: hipcc reads every input behind a .hip file as HIP source)
+    for r in (rcmd, run):
+        if verbose:
+            r = [r[0], "-Rpass-analysis=kernel-resource-usage"] + r[1:]
+            print(" ".join(r))
+        subprocess.check_call(r)
     with open(_stamp(target), "w") as f:
         f.write(_stamp_text(cmd))
+    with open(_render_stamp(target), "w") as f:
+        f.write(_stamp_text(rcmd))
     with open(target + ".toolchain", "w") as f:
         f.write(toolchain_text())
     return target

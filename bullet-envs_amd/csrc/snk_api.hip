@@ -14,6 +14,7 @@
 
 #include "../../include/snk.h"
 #include "snk_device.hpp"
+#include "snk_render_view.hpp"
 
 namespace {
 
@@ -60,6 +61,8 @@ struct snk_handle {
     float* d_box = nullptr;       // obstacle 2: the free box of every env, [n_envs][kBoxFloats] (state 13, count, manifold 24)
     float* d_reset = nullptr;     // the reset-pose table, [n_envs][reset_row_floats(n)] = [pos 3 | quat xyzw 4 | q n | padding]
     int32_t* d_order = nullptr;
+    float* d_render = nullptr;    // snk_render's per-image primitive and camera tables (snk_render.hip), allocated on first use
+    size_t d_render_bytes = 0;
     bool plan = true;
     // in-launch scheduler of env_step_sched_kernel (snk_device.hpp): rings, counters, the host-mapped alarm word
     snk::Sched sched = {};
@@ -271,6 +274,20 @@ float manifold_from_host(const float* o, float* pts) {
 }
 
 }  // namespace
+
+// the renderer's seam (snk_render_view.hpp): its translation unit sees this much of a handle, and reports through g_err
+namespace snk {
+int api_fail(const char* msg) { return fail(msg); }
+int render_view(snk_handle* h, bool sync, RenderView* v) {
+    HIP_TRY(hipSetDevice(h->device));
+    if (sync) HIP_TRY(hipDeviceSynchronize());
+    if (check_alarm(h)) return 1;
+    v->device = h->device; v->n = h->n; v->n_envs = h->n_envs; v->v2 = h->v2;
+    v->D = &h->D; v->d_model = h->d_model; v->d_recs = h->d_recs; v->d_box = h->d_box;
+    v->scratch = &h->d_render; v->scratch_bytes = &h->d_render_bytes;
+    return 0;
+}
+}  // namespace snk
 
 extern "C" {
 
@@ -538,7 +555,7 @@ int snk_destroy(snk_handle* h) {
     (void)hipDeviceSynchronize();
     void* bufs[] = {h->d_model, h->d_recs, h->d_mu, h->d_act, h->d_obs, h->d_rew, h->d_done,
                     h->d_sub, h->d_mask, h->d_tgt, h->d_info, h->d_h, h->d_order, h->d_rows, h->d_linkpos, h->d_trace, h->d_mf, h->d_ovf, h->d_box,
-                    h->d_reset,
+                    h->d_reset, h->d_render,
                     h->sched.head, h->sched.tail, h->sched.ent, h->sched.waiting, h->sched.counter, h->sched.finished};
     for (void* b : bufs) (void)hipFree(b);
     if (h->h_alarm) (void)hipHostFree(h->h_alarm);

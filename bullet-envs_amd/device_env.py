@@ -103,6 +103,45 @@ class DeviceVecEnv(object):
     def set_ground_friction(self, mu):
         self.stepper.set_ground_friction(np.asarray(mu, dtype=np.float32))
 
+    def render(self, env_ids=None, view=None, proj=None, width=128, height=96, shadow=False, depth=True, seg=True):
+        """Images of the envs `env_ids` (None: all; an int32 CUDA tensor or a sequence; ids may repeat, any order) from
+        their current device state, enqueued on the current stream behind the steps already there (snk_render): what
+        Snake.render (snake.py:308-334) draws of one env, for any subset at once and without a host transfer.
+        view / proj: column-major 16-vectors as PyBullet's computeViewMatrix* / computeProjectionMatrix* return them,
+        one pair for every image or [k, 16] each (tensors or arrays); None: the [U] default camera (_lib.DEFAULT_CAMERA).
+        Returns CUDA tensors (rgba [k, height, width, 4] uint8, depth [k, height, width] float32 or None, seg int32
+        primitive ids or None: 0 ground, 1 + c cylinder c, 1 + 2n box, -1 background)."""
+        t = self.torch
+        if env_ids is None:
+            ids, k = None, self.num_envs
+        else:
+            ids = t.as_tensor(env_ids, dtype=t.int32, device=self.device).reshape(-1).contiguous()
+            k = int(ids.numel())
+        if view is None or proj is None:
+            dv, dp = _lib.default_camera(width, height)
+            view, proj = (dv if view is None else view), (dp if proj is None else proj)
+        v = t.as_tensor(view, dtype=t.float32, device=self.device).reshape(-1, 16)
+        p = t.as_tensor(proj, dtype=t.float32, device=self.device).reshape(-1, 16)
+        if v.shape[0] != p.shape[0] or v.shape[0] not in (1, k):
+            raise ValueError("view / proj must be one 16-vector each or [%d, 16] each, got %s / %s"
+                             % (k, tuple(v.shape), tuple(p.shape)))
+        cams = t.cat([v, p], dim=1).contiguous()
+        W, H = int(width), int(height)
+        ok = 1 <= W <= 4096 and 1 <= H <= 4096 and k >= 1          # (the library refuses the rest, naming the argument)
+        rgba = t.empty((k, H, W, 4) if ok else (4,), dtype=t.uint8, device=self.device)
+        dep = t.empty((k, H, W), dtype=t.float32, device=self.device) if depth and ok else None
+        sg = t.empty((k, H, W), dtype=t.int32, device=self.device) if seg and ok else None
+        self.stepper.render_device(ids.data_ptr() if ids is not None else 0, k, cams.data_ptr(), v.shape[0] == 1, W, H,
+                                   _lib.RENDER_SHADOW if shadow else 0, rgba.data_ptr(),
+                                   dep.data_ptr() if dep is not None else 0, sg.data_ptr() if sg is not None else 0,
+                                   self._stream())
+        # the kernels read ids / cams when the stream gets there: they stay alive until then
+        cur = t.cuda.current_stream(self.device)
+        cams.record_stream(cur)
+        if ids is not None:
+            ids.record_stream(cur)
+        return rgba, dep, sg
+
     def set_reset_pose(self, pose, mask=None):
         """Where the envs of `mask` (None: all) start their next episodes, at reset() and at the auto-reset inside
         step(): rows [initPosition 3 | initOrientation xyzw 4 | initState n] (snake.py:22-24, 119-127).

@@ -31,10 +31,17 @@ class BulletClient(object):
     URDF_USE_SELF_COLLISION = 8
     DIRECT = 2
     GUI = 1
+    ER_SEGMENTATION_MASK_OBJECT_AND_LINKINDEX = 1
+    ER_TINY_RENDERER = 65536
+    ER_BULLET_HARDWARE_OPENGL = 131072
 
     _PLANE, _SNAKE, _BLOCK = 0, 1, 2
 
-    def __init__(self, device=0, n_modules=16, **params):
+    def __init__(self, device=0, n_modules=16, render=None, **params):
+        if render not in (None, 'kernel'):
+            raise ValueError("render must be None or 'kernel', got %r" % (render,))
+        self._render = render                # 'kernel': getCameraImage draws (snk_render); None: PyBullet's 5-tuple, no pixels
+        self._camera = {}                    # what the last resetDebugVisualizerCamera said
         self._device = device
         self._n = n_modules
         self._over = dict(params)
@@ -116,11 +123,56 @@ class BulletClient(object):
         if enable:
             raise NotImplementedError("BulletClient: stepSimulation drives the clock (snake_gait_test.py:54)")
 
-    def resetDebugVisualizerCamera(self, *a, **k):
+    def resetDebugVisualizerCamera(self, cameraDistance=None, cameraYaw=None, cameraPitch=None, cameraTargetPosition=None,
+                                   *a, **k):
+        if self._render is not None:         # remembered: the camera of a getCameraImage without matrices [U]
+            self._camera = dict(distance=cameraDistance, yaw=cameraYaw, pitch=cameraPitch, target=cameraTargetPosition)
         return None
 
-    def getCameraImage(self, width, height, *a, **k):
-        return (width, height, [], [], [])
+    def computeViewMatrixFromYawPitchRoll(self, cameraTargetPosition, distance, yaw, pitch, roll, upAxisIndex, *a, **k):
+        """snake.py:310-316.  PyBullet's 16-tuple (column-major), from snk_view_matrix_ypr [U]."""
+        if self._render is None:
+            raise AttributeError("BulletClient(render=None) has no computeViewMatrixFromYawPitchRoll: pass render='kernel'")
+        return tuple(float(v) for v in _lib.view_matrix_ypr(cameraTargetPosition, distance, yaw, pitch, roll, upAxisIndex))
+
+    def computeProjectionMatrixFOV(self, fov, aspect, nearVal, farVal, *a, **k):
+        """snake.py:317-320 (which passes farVal = nearVal: the entries come out infinite, nothing raises).  PyBullet's
+        16-tuple, from snk_projection_fov [U]."""
+        if self._render is None:
+            raise AttributeError("BulletClient(render=None) has no computeProjectionMatrixFOV: pass render='kernel'")
+        return tuple(float(v) for v in _lib.projection_fov(fov, aspect, nearVal, farVal))
+
+    def default_camera(self, width, height):
+        """(view, proj) of a getCameraImage without matrices [U]: the last resetDebugVisualizerCamera (before any: the
+        reference's own, snake.py:322-325) with fov 60, near 0.01, far 100 -- _lib.DEFAULT_CAMERA says why."""
+        c = {k: v for k, v in self._camera.items() if v is not None}
+        return _lib.default_camera(width, height, **c)
+
+    def segmentation_ids(self, seg, flags=0):
+        """Primitive ids of snk_render (0 ground, 1 + c cylinder c, 1 + 2n box, -1 none) -> PyBullet's: the body ids this
+        client hands out (plane 0, snake 1, block 2), and under ER_SEGMENTATION_MASK_OBJECT_AND_LINKINDEX
+        + ((link index + 1) << 24) with the cylinder's Bullet link (INPUT_INTERFACE_k = 3k - 2, OUTPUT_BODY_k = 3k; the
+        plane and the block are base links, -1)."""
+        seg = np.asarray(seg)
+        n = self._n
+        c = seg - 1
+        out = np.where(seg == 0, self._PLANE, np.where(seg == 1 + 2 * n, self._BLOCK, self._SNAKE)).astype(np.int32)
+        if flags & self.ER_SEGMENTATION_MASK_OBJECT_AND_LINKINDEX:
+            link = np.where(c % 2 == 0, 3 * (c // 2 + 1) - 2, 3 * ((c + 1) // 2))
+            out = out + np.where((seg >= 1) & (seg <= 2 * n), (link + 1) << 24, 0).astype(np.int32)
+        return np.where(seg < 0, -1, out).astype(np.int32)
+
+    def getCameraImage(self, width, height, viewMatrix=None, projectionMatrix=None, shadow=0, flags=0, *a, **k):
+        """snake.py:326-327, snake_gait_test.py:19-26.  render=None: PyBullet's 5-tuple with no pixels, as before.
+        render='kernel': (width, height, rgba (h, w, 4) uint8, depth (h, w) float32, segmentation (h, w) int32)."""
+        if self._render is None:
+            return (width, height, [], [], [])
+        if viewMatrix is None or projectionMatrix is None:
+            dv, dp = self.default_camera(width, height)
+            viewMatrix = dv if viewMatrix is None else viewMatrix
+            projectionMatrix = dp if projectionMatrix is None else projectionMatrix
+        rgba, dep, seg = self._stepper().render(viewMatrix, projectionMatrix, width, height, shadow=bool(shadow))
+        return (width, height, rgba[0], dep[0], self.segmentation_ids(seg[0], flags))
 
     def getJointInfo(self, body, joint):
         """(index, name, type, ...) in PyBullet's layout, from the URDF's module pattern: joint 3k is

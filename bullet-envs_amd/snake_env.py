@@ -31,6 +31,17 @@ def _check_telemetry(telemetry):
     return telemetry
 
 
+#: what render() draws with: None = nothing (an empty array, as before the ray caster existed), 'kernel' = the HIP ray
+#: caster behind snk_render
+RENDER = (None, 'kernel')
+
+
+def _check_render(render):
+    if render not in RENDER:
+        raise ValueError("render must be None or 'kernel', got %r" % (render,))
+    return render
+
+
 def params_from_args(args=None, n_modules=16, **over):
     """snk_params from the reference's argparse namespace (ppo/params.py:5-46).
 
@@ -65,9 +76,13 @@ class Snake(object):
     the model is generated from the snake.urdf constants and the world lives on the GPU.
     """
 
-    def __init__(self, pybullet_client=None, urdf_root=None, args=None, n_modules=16, telemetry=None):
+    def __init__(self, pybullet_client=None, urdf_root=None, args=None, n_modules=16, telemetry=None, render=None):
         self.numMotors = n_modules
         self.telemetry = None if telemetry is None else _check_telemetry(telemetry)   # None: the env's own setting
+        self._render = _check_render(render)             # 'kernel': render() draws (snk_render); None: it returns []
+        # the frame's size (snake.py:48-49, 71-72)
+        self.RENDER_HEIGHT = int(getattr(args, "render_height", 720)) if args is not None else 720
+        self.RENDER_WIDTH = int(getattr(args, "render_width", 1280)) if args is not None else 1280
         self._pybulletClient = pybullet_client
         self._urdf = urdf_root
         self._timeStep = 1 / 100.0                       # snake.py:9,19
@@ -210,6 +225,18 @@ class Snake(object):
     def checkSnakeHeight(self):                          # snake.py:237-245
         return bool(self._need_env()._stepper.mean_height()[0] > 0.1)
 
+    def render(self):
+        """snake.py:308-334 with render='kernel': the (RENDER_HEIGHT, RENDER_WIDTH, 3) uint8 frame of the camera the
+        reference sets right before its getCameraImage (resetDebugVisualizerCamera(1.5, -30, -90, [1.28, 0, 0]); the
+        view / projection matrices it computes first are never passed on, snake.py:326-329).  render=None: an empty
+        array."""
+        if self._render is None:
+            return np.array([])
+        W, H = self.RENDER_WIDTH, self.RENDER_HEIGHT
+        view, proj = _lib.default_camera(W, H)
+        rgba, _, _ = self._need_env()._stepper.render(view, proj, W, H, depth=False, seg=False)
+        return rgba[0, :, :, :3]
+
     def calculateEnergy(self, observation):              # snake.py:336-341
         n = self.numMotors
         return float(np.sum(observation[n:2 * n] * observation[2 * n:3 * n] * self._timeStep))
@@ -236,13 +263,17 @@ class Snake(object):
 class SnakeGymEnv(object):
     """Single environment with SnakeGymEnv's API, backed by a 1-env GPU stepper."""
 
-    def __init__(self, robot=None, args=None, device=0, n_modules=None, telemetry=None, **over):
+    def __init__(self, robot=None, args=None, device=0, n_modules=None, telemetry=None, render=None, mode=None, **over):
         print("Snake Gym environment Created!")          # SnakeGymEnv.py:6
+        # render(): the robot's setting when it has one, else this argument (None: an empty array, as before)
+        self._render = _check_render(render if render is not None else getattr(robot, "_render", None))
         # test mode's telemetry: the robot's setting when it has one, else 'replay'
         self.telemetry = _check_telemetry(telemetry if telemetry is not None else
                                           (getattr(robot, "telemetry", None) or 'replay'))
         if robot is None:
-            robot = Snake(None, None, args, n_modules=n_modules or 16)
+            robot = Snake(None, None, args, n_modules=n_modules or 16, render=self._render)
+        elif hasattr(robot, "_render") and robot._render is None:
+            robot._render = self._render
         n_modules = n_modules or robot.numMotors
         if args is not None:
             self.alpha, self.beta, self.gamma = args.alpha, args.beta, args.gamma
@@ -252,6 +283,9 @@ class SnakeGymEnv(object):
             self.alpha, self.beta, self.gamma = 1, 0.01, 0.1
             self.mode = 'train'
             self._gaitSelection = 1
+        if mode is not None:              # (without an argparse namespace: SnakeGymEnv(mode='test', render='kernel'))
+            self.mode = mode
+            robot.mode = mode
         self.robot = robot
         self._action_bound = 1
         self.params = params_from_args(args, n_modules=n_modules, **over)
@@ -378,7 +412,11 @@ class SnakeGymEnv(object):
             raise SystemError("test-mode replay diverged from the step kernel")
 
     def render(self):
-        return np.array([])
+        """SnakeGymEnv.py:52-58: in test mode the robot's frame, in train mode an empty array.  Without render='kernel'
+        (the default) an empty array in every mode."""
+        if self._render is None or self.mode != 'test':
+            return np.array([])
+        return self.robot.render()
 
     def close(self):
         self._stepper.close()
@@ -587,6 +625,17 @@ class SnakeVecEnv(VecEnv):
 
     def reset(self):
         return self._stepper.reset()
+
+    def render(self, env_ids=None, view=None, proj=None, width=128, height=96, shadow=False):
+        """Images of the envs `env_ids` (None: all; ids may repeat, any order) from their current state, as numpy arrays:
+        (rgba [k, height, width, 4] uint8, depth [k, height, width] float32, seg [k, height, width] int32 primitive
+        ids: 0 ground, 1 + c cylinder c, 1 + 2n box, -1 background) -- what Snake.render (snake.py:308-334) draws of one
+        env.  view / proj: PyBullet's column-major 16-tuples, one pair or [k, 16] each; None: the [U] default camera
+        (_lib.DEFAULT_CAMERA, the one the reference sets before its getCameraImage)."""
+        if view is None or proj is None:
+            dv, dp = _lib.default_camera(width, height)
+            view, proj = (dv if view is None else view), (dp if proj is None else proj)
+        return self._stepper.render(view, proj, width, height, env_ids=env_ids, shadow=shadow)
 
     def set_reset_pose(self, pose, mask=None):
         """Where the envs of `mask` (None: all) start their next episodes -- at reset() and at the auto-reset inside

@@ -306,6 +306,92 @@ int snk_joint3_reaction_fz(snk_handle* h, float* out);
 int snk_get_box(snk_handle* h, float* state, float* manifold);
 int snk_set_box(snk_handle* h, const float* state, const float* manifold);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The rendered scene: the contract of snk_render.  The kernels (bullet-envs_amd/csrc/snk_render.hpp) and the independent
+ * float64 model of the tests (tests/np_render.py) are both written from this text.
+ *
+ * Camera.  A camera is 32 floats: the view matrix V, then the projection matrix P, each column-major 4x4 with the OpenGL
+ * clip convention, as PyBullet passes them.  M = P V; its inverse is taken in float64 and rounded to float32.  Pixel
+ * (row j from the top, column i) of a width x height image is sampled at its centre: x = 2 (i + 0.5) / width - 1,
+ * y = 1 - 2 (j + 0.5) / height.  a = M^-1 (x, y, -1, 1) and b = M^-1 (x, y, +1, 1) are the pixel centre on the near and on
+ * the far plane; o = a.xyz / a.w, f = b.xyz / b.w.  The ray is o + t d with d = (f - o) / |f - o|, t in metres, and only
+ * hits with 0 <= t <= |f - o| count: those between the near and the far plane, i.e. with a depth in [0, 1].
+ *
+ * Solids are convex and drawn one-sided: a ray meets a solid where it ENTERS it.  A solid the ray starts inside of (one
+ * the near plane cuts) is open along that ray: what lies behind it shows.
+ *   ground    the plane z = 0, normal +z, primitive id 0.  It carries a 0.5 m checkerboard: a hit at (x, y) has parity
+ *             (floor(x / 0.5) + floor(y / 0.5)) & 1; albedo (0.95, 0.95, 0.95) for parity 0, (0.55, 0.65, 0.85) for 1.
+ *   cylinder  c = 0 .. 2n - 1, primitive id 1 + c: the link colliders (the model's cyl_body / cyl_c / cyl_R on the body
+ *             frames of the forward kinematics; radius and half length as snk_params_derived reports them), finite and
+ *             capped: the points within the radius of the axis and within the half length of the centre along it.  The
+ *             normal is radial where the ray enters through the side, +-axis where it enters through a cap.  Albedo
+ *             (0.85, 0.35, 0.15) for even c, (0.25, 0.25, 0.28) for odd c.
+ *   box       primitive id 1 + 2n.  obstacle 1: centre obstacle_pos, half extents obstacle_half, axis aligned;
+ *             obstacle 2: the env's free box (centre and quaternion as snk_get_box reports them); obstacle 0: none.
+ *             The normal is that of the face (slab) the ray enters through.  Albedo (0.45, 0.75, 0.45).
+ * The hit drawn is the nearest; the primitives are tried in the order of their ids, and a later one replaces the kept hit
+ * only when its t is smaller by more than 2e-4 m.  (Two consecutive colliders of one body are coaxial, of one radius, and
+ * overlap by 5.7 mm along the axis -- snake.urdf:806-811, 862-867, 877 -- so their side surfaces coincide there: without
+ * the margin, round-off would pick the colour: the float32 twin of tests/np_render.py moved t by 3e-5 m at one such pixel
+ * near a silhouette.  The lower id is drawn.  The margin holds between ANY two primitives, the ground included: a solid
+ * less than 0.2 mm in front of an earlier one loses to it.)
+ * No hit: RGBA (200, 215, 235, 255), depth 1.0, segmentation -1.
+ *
+ * Shading.  colour = albedo x (0.4 + 0.6 x max(0, n.L) x lit), n the outward normal at the hit, L = (0.4, -0.3, 0.85)
+ * normalised.  lit = 1 without SNK_RENDER_SHADOW.  With it: lit = 0 where n.L <= 0 (the colour is the same either way),
+ * else lit = 0 when the ray from the hit point moved 1e-4 m along n, towards L, meets a cylinder or the box at any
+ * t >= 0 (a ray that starts inside one counts as meeting it), else 1.  Channel = (uint8) floor(255 c + 0.5); alpha 255.
+ * Depth = 0.5 (M X).z / (M X).w + 0.5 at the hit point X: the OpenGL depth-buffer value getCameraImage returns, which
+ * PyBullet's documented far near / (far - (far - near) depth) turns back into a distance along the view axis.
+ *
+ * Deviations from what PyBullet draws: it draws the STL visual meshes, this the collision geometry; the
+ * cylinder is the implicit one, at most r (1 - cos(pi / 32)) = 0.125 mm outside the 32-gon hull the physics uses; links
+ * without a collision shape are not drawn; no anti-aliasing, textures or specular term.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SNK_RENDER_SHADOW 1     /* flags bit: cast the shadow ray */
+
+/* Replaces Snake.render (snake.py:308-334: resetDebugVisualizerCamera + getCameraImage, the frame SnakeGymEnv.render
+ * hands out in test mode, SnakeGymEnv.py:52-58, and ppo/test.py:77 collects) and the getCameraImage of
+ * snake_gait_test.py:19-26,112 -- for any subset of the handle's envs at once, from their CURRENT device state.
+ *   env_ids_dev  [n_images] i32, device; NULL: envs 0 .. n_images - 1.  Ids may repeat and come in any order.  They
+ *                cannot be validated from the host on this path (as snk_set_reset_pose_dev's values cannot): an id
+ *                outside 0 .. n_envs - 1 reads nothing, and its image shows the ground alone.
+ *   cameras_dev  [n_images][32] f32, or [1][32] when shared_camera != 0: view, then projection (above).  Not validated:
+ *                a singular or non-finite camera gives an image of background and undefined depths, nothing worse.
+ *   flags        0 or SNK_RENDER_SHADOW.
+ *   rgba_dev     [n_images][height][width] u8 x 4 (4-byte aligned: a pixel is one 32-bit store);
+ *   depth_dev    [n_images][height][width] f32, may be NULL;   seg_dev  the same in i32, may be NULL: the primitive id.
+ * Asynchronous on `stream` (hipStream_t or NULL) and ordered with the steps enqueued there: a render behind a step
+ * shows the state after it.  Two launches -- one wave per image builds the image's table of primitives (64 bytes each)
+ * and its camera; one 256-thread workgroup per 16 x 16 pixel tile casts the rays -- with no atomics and no waits; every
+ * byte outside [n_images][height][width] is left alone; nothing of the handle's state is written.  The tables live in
+ * scratch memory of the handle, grown on demand -- the first call, and any call with more images than every call before,
+ * frees and allocates, i.e. waits for the whole device once and must not happen while a stream is being captured into a
+ * graph: render n_envs images once before capturing.  Like every call on a handle, renders are serialised by the caller.
+ * Refused, naming the argument: a null or poisoned handle; n_images < 1; width or height outside 1 .. 4096; more than
+ * 2^31 - 1 pixels in all; unknown bits in flags; a null (or misaligned) rgba_dev; a null cameras_dev. */
+int snk_render(snk_handle* h, const int32_t* env_ids_dev, int32_t n_images, const float* cameras_dev, int32_t shared_camera,
+               int32_t width, int32_t height, int32_t flags, uint8_t* rgba_dev, float* depth_dev, int32_t* seg_dev,
+               void* stream);
+/* The same (replaces snake.py:308-334 and snake_gait_test.py:19-26 for a caller on the host) with HOST buffers: it
+ * synchronises the device first, like the state accessors, and also refuses an env id outside 0 .. n_envs - 1, n_images
+ * above n_envs without ids, and a non-finite camera entry -- each with its index. */
+int snk_render_host(snk_handle* h, const int32_t* env_ids, int32_t n_images, const float* cameras, int32_t shared_camera,
+                    int32_t width, int32_t height, int32_t flags, uint8_t* rgba, float* depth, int32_t* seg);
+
+/* Replaces pybullet.computeViewMatrixFromYawPitchRoll (snake.py:310-316) [U]: bullet3's b3ComputeViewMatrixFromYawPitchRoll
+ * restated.  Host only, no handle.  The eye sits `distance` behind `target` along the forward axis (y for up_axis 2, z for
+ * up_axis 1) turned by yaw about the up axis and pitch about x; the up vector is turned with it, so a pitch of -90
+ * degrees (the reference's camera, snake.py:322-325) has no degenerate up vector.  roll_deg is accepted and NOT used:
+ * bullet3 sets its roll to zero.  out: column-major 4x4.  up_axis other than 1 or 2 is refused. */
+int snk_view_matrix_ypr(const float target[3], float distance, float yaw_deg, float pitch_deg, float roll_deg, int32_t up_axis,
+                        float out[16]);
+/* Replaces pybullet.computeProjectionMatrixFOV (snake.py:317-320) [U]: bullet3's b3ComputeProjectionMatrixFOV restated.
+ * Host only, no handle.  out[0] = y / aspect, out[5] = y = 1 / tan(fov / 2), out[10] = (near + far) / (near - far),
+ * out[11] = -1, out[14] = 2 far near / (near - far), the rest 0.  Nothing is refused: the reference's own call passes
+ * farVal = nearVal (snake.py:320), and gets the infinite entries the formula gives. */
+int snk_projection_fov(float fov_deg, float aspect, float near_val, float far_val, float out[16]);
+
 /* Where this build's structural limits were met, counted on the device since snk_create (Bullet has no such limits;
  * DESIGN.md 3).  Ground contacts have none left: the streamed-row solve has a slot for every point its chain's manifolds
  * can hold (8n), and the register-resident 16-link solve hands the substeps that outgrow its 64 slots to it.
@@ -347,7 +433,7 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
  * kernel sets when one of its bounded waits runs out (nothing waits, nothing hangs).  Afterwards the handle behaves as
  * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
  * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction,
- * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) return
+ * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) and snk_render / snk_render_host return
  * non-zero -- and snk_reset_pose_floats 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */

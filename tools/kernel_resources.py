@@ -12,23 +12,30 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def device_asm(root, args, out):
-    """Compiles <root>/bullet-envs_amd/csrc/snk_api.hip device-only to assembly with the product's own flags (that tree's
+def device_asm(root, args, out, src="csrc/snk_api.hip"):
+    """Compiles <root>/bullet-envs_amd/<src> (the step kernels' translation unit; main() also lists the renderer's,
+    csrc/snk_render.hip) device-only to assembly with the product's own flags (that tree's
     `build.py --print-flags`) plus `args`; returns the command.  (tools/same_isa.py compares two trees with it.)"""
     pkg = os.path.join(root, "bullet-envs_amd")
     flags = subprocess.check_output([sys.executable, os.path.join(pkg, "build.py"), "--print-flags"], text=True).split()
-    cmd = ["/opt/rocm/bin/hipcc"] + flags + list(args) + ["--offload-device-only", "-S", "csrc/snk_api.hip", "-o", out]
+    cmd = ["/opt/rocm/bin/hipcc"] + flags + list(args) + ["--offload-device-only", "-S", src, "-o", out]
     subprocess.run(cmd, cwd=pkg, check=True, stderr=subprocess.DEVNULL)
     return cmd
 
 
 def main():
+    print("%-46s %6s %6s %9s %5s" % ("kernel", "VGPRs", "SGPRs", "scratch B", "occ"))
+    for src in ("csrc/snk_api.hip", "csrc/snk_render.hip"):
+        if os.path.exists(os.path.join(ROOT, "bullet-envs_amd", src)):
+            one(src)
+
+
+def one(src):
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "snk.s")
-        cmd = device_asm(ROOT, sys.argv[1:], out)
+        cmd = device_asm(ROOT, sys.argv[1:], out, src)
         lines = open(out).read().split("\n")
     print("# " + " ".join(cmd[:-2]))
-    print("%-46s %6s %6s %9s %5s" % ("kernel", "VGPRs", "SGPRs", "scratch B", "occ"))
     name = None
     for i, l in enumerate(lines):
         m = re.match(r"^(_ZN3snk\w+):\s*; @", l)
