@@ -256,6 +256,37 @@ def trace_to_lists(trace, sub, n_modules):
     return io, lp
 
 
+class Snapshot:
+    """THE definition of the simulator state of a handle's environments: what Stepper.snapshot reads, Stepper.restore
+    writes, a checkpoint stores and a test-mode replay starts from.  A plain value: numpy arrays, axis 0 = environment.
+    A field that is None is absent: `manifold` on a contact_model 0 handle, the box without obstacle 2, `reset_pose`
+    when not asked for.  A new per-environment table is added HERE (FIELDS, Stepper.snapshot, Stepper.restore) and
+    nowhere else."""
+    FIELDS = ("state", "aux", "ground_friction", "manifold", "box_state", "box_manifold", "reset_pose")
+
+    def __init__(self, state=None, aux=None, ground_friction=None, manifold=None, box_state=None, box_manifold=None,
+                 reset_pose=None):
+        self.state, self.aux, self.ground_friction, self.manifold = state, aux, ground_friction, manifold
+        self.box_state, self.box_manifold, self.reset_pose = box_state, box_manifold, reset_pose
+
+    @property
+    def n_envs(self):
+        return len(next(v for v in map(self.__dict__.get, self.FIELDS) if v is not None))
+
+    def __getitem__(self, idx):
+        """numpy indexing on axis 0 of every field present: snap[perm], a subset, replicas (src[idx] = e; snap[src])."""
+        return Snapshot(**{k: None if v is None else v[idx] for k, v in self.__dict__.items()})
+
+    def arrays(self):
+        """The fields as a checkpoint stores them: an empty float32 array stands for an absent one."""
+        return {k: np.zeros(0, np.float32) if self.__dict__[k] is None else self.__dict__[k] for k in self.FIELDS}
+
+    @classmethod
+    def from_arrays(cls, mapping):
+        """The inverse of arrays(); a key the mapping does not have is an absent field too."""
+        return cls(**{k: mapping[k] for k in cls.FIELDS if k in mapping and np.size(mapping[k])})
+
+
 class Stepper:
     """Thin owner of one `snk_handle`: N environments on one GPU (host-buffer API)."""
 
@@ -410,6 +441,30 @@ class Stepper:
             assert m.shape == (self.n_envs, 29)
         check(self.lib.snk_set_box(self.h, fptr(s) if s is not None else None, fptr(m) if m is not None else None),
               "snk_set_box")
+
+    def snapshot(self, reset_pose=True):
+        """The simulator state of every env as a Snapshot (the EFFECTIVE friction, read back from the device);
+        reset_pose=False leaves the reset-pose table out (a replay that only substeps never reads it)."""
+        state, aux = self.get_state()
+        box = self.get_box() if self.params.obstacle == 2 else (None, None)
+        return Snapshot(state, aux, self.get_ground_friction(), self.get_manifold(), box[0], box[1],
+                        self.get_reset_pose() if reset_pose else None)
+
+    def restore(self, snap):
+        """Writes every field of `snap` that is present, through the setters above, in one fixed order: friction, state
+        and aux, contact cache, box, reset poses."""
+        if snap.n_envs != self.n_envs:
+            raise ValueError("snapshot holds %d environments, this handle %d" % (snap.n_envs, self.n_envs))
+        if snap.ground_friction is not None:
+            self.set_ground_friction(snap.ground_friction)
+        if snap.state is not None or snap.aux is not None:
+            self.set_state(snap.state, snap.aux)
+        if snap.manifold is not None:
+            self.set_manifold(snap.manifold)
+        if snap.box_state is not None or snap.box_manifold is not None:
+            self.set_box(snap.box_state, snap.box_manifold)
+        if snap.reset_pose is not None:
+            self.set_reset_pose(snap.reset_pose)
 
     def contact_overflow(self):
         """snk_contact_overflow since the handle was created: (substeps with more contact points than the solve's slots

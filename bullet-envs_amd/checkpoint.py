@@ -5,7 +5,8 @@ a PyBullet world cannot be resumed mid-rollout.  Here the whole simulator state 
 environments is the per-env record (`snk_get_state`): pose, velocities, joint state, last
 motor torques, joint-0 force, previous x for the reward -- plus the per-env plane friction, the
 per-env reset poses (`snk_get_reset_pose`: where the next episodes start) and the model parameters
-it was produced with.  Restoring it continues bit-for-bit.
+it was produced with.  Restoring it continues bit-for-bit.  Which arrays make up that state is said in one place,
+`_lib.Snapshot`; this module only puts a snapshot into a file and back.
 `save_state` / `load_state` synchronise the device (the state accessors of the C ABI do).
 """
 import numpy as np
@@ -33,22 +34,15 @@ def _params_fields(p):
 
 
 def save_state(env, path):
-    """env: Stepper, SnakeVecEnv or DeviceVecEnv.  Writes one .npz."""
+    """env: Stepper, SnakeVecEnv or DeviceVecEnv.  Writes one .npz: the handle's Snapshot (_lib.Snapshot: what the
+    simulator state IS) plus its size and parameters."""
     import json
     st = _stepper(env)
-    state, aux = st.get_state()
-    # the EFFECTIVE friction, read back from the device (also covers values set through the C ABI directly)
-    mf = st.get_manifold()           # the contact cache is simulator state too (contact_model 1)
-    box = st.get_box() if st.params.obstacle == 2 else None      # ... and so is a free obstacle box
     # The parameters travel field by field (JSON: names and values), not as the raw bytes of the C struct: a field
     # appended to snk_params in a later build must not make every older checkpoint unreadable (ADVICE r5).
-    np.savez_compressed(path, state=state, aux=aux, n_envs=np.int64(st.n_envs), format=np.int64(FORMAT),
+    np.savez_compressed(path, n_envs=np.int64(st.n_envs), format=np.int64(FORMAT),
                         params_json=np.frombuffer(json.dumps(_params_fields(st.params), sort_keys=True).encode(), dtype=np.uint8),
-                        ground_friction=st.get_ground_friction(),
-                        manifold=np.zeros(0, np.float32) if mf is None else mf,
-                        box_state=np.zeros(0, np.float32) if box is None else box[0],
-                        box_manifold=np.zeros(0, np.float32) if box is None else box[1],
-                        reset_pose=st.get_reset_pose())       # where the next episodes start (snk_set_reset_pose)
+                        **st.snapshot().arrays())
 
 
 def _check_params(z, st):
@@ -79,24 +73,17 @@ def _check_params(z, st):
 
 def load_state(env, path):
     """Restores a checkpoint into an env created with the same parameters and size."""
+    from ._lib import Snapshot
     st = _stepper(env)
     with np.load(path if str(path).endswith(".npz") else str(path) + ".npz") as z:
         if int(z["n_envs"]) != st.n_envs:
             raise ValueError("checkpoint holds %d environments, this handle %d" % (int(z["n_envs"]), st.n_envs))
         _check_params(z, st)
-        mu = z["ground_friction"]
-        # always restored: a checkpoint of a default-friction world must also undo the target's custom friction
-        st.set_ground_friction(mu if mu.size else np.ones(st.n_envs, np.float32))
-        st.set_state(z["state"], z["aux"])
-        if "manifold" in z.files and z["manifold"].size:
-            st.set_manifold(z["manifold"])
-        if "box_state" in z.files and z["box_state"].size:
-            st.set_box(z["box_state"], z["box_manifold"])
-        # always restored, like the friction: a checkpoint from before the reset-pose table (no such entry) ran with the
-        # reference's defaults -- zeros and the unit quaternion -- and must also undo the target's own poses
-        if "reset_pose" in z.files:
-            st.set_reset_pose(z["reset_pose"])
-        else:
-            default = np.zeros(7 + st.n, np.float32)
-            default[6] = 1.0
-            st.set_reset_pose(default)
+        snap = Snapshot.from_arrays({k: z[k] for k in Snapshot.FIELDS if k in z.files})
+    # Format history.  Both are always restored: a checkpoint of a default world must also undo the target's own values.
+    if snap.ground_friction is None:        # (an empty entry: ones)
+        snap.ground_friction = np.ones(st.n_envs, np.float32)
+    if snap.reset_pose is None:             # (from before the reset-pose table: the reference's defaults -- zeros and the
+        snap.reset_pose = np.zeros((st.n_envs, 7 + st.n), np.float32)       # unit quaternion)
+        snap.reset_pose[:, 6] = 1.0
+    st.restore(snap)

@@ -69,6 +69,66 @@ def params_first_difference(a, b):
     return None
 
 
+def joint_targets(params, clipped_actions):
+    """createAction + convertActionToJointCommand (snake.py:223-225, 247-269) of [N, act_dim] clipped actions with the
+    gait and scale the DEVICE uses (`params`: they may have been overridden through **over, which the robot facade does
+    not see): the [N, n] float32 joint targets of the env-step."""
+    a = np.asarray(clipped_actions, dtype=np.float32)
+    targets = np.zeros((len(a), params.n_modules), dtype=np.float32)
+    targets[:, {0: slice(0, None, 2), 1: slice(1, None, 2)}.get(params.gait, slice(None))] = a
+    targets *= np.float32(params.scaling_factor)
+    return targets
+
+
+#: what a test-mode step raises when its per-substep lists do not end on the observation the step kernel returned
+DIVERGED = {'replay': "test-mode replay diverged from the step kernel",
+            'kernel': "test-mode trace diverged from the step kernel's observation"}
+
+
+def _test_mode_step(env, actions, vec_mode):
+    """One test-mode env-step of `env` (SnakeVecEnv; SnakeGymEnv is N = 1 with vec_mode False) with its telemetry
+    (snake.py:275-293, SnakeGymEnv.py:43-44): obs, rew, done, sub and per env the lists (observations, link positions)
+    after every physics substep of ITS env-step.  The fused step kernel is the authority for state, reward and
+    termination either way.  telemetry='kernel': the lists are the rows that kernel wrote itself (snk_step_traced).
+    telemetry='replay': the substeps are replayed one launch at a time on a scratch handle of the same size, device and
+    parameters from the Snapshot the step started in -- friction included, whoever set it; without the reset-pose table,
+    which substeps never read and which may have been written through the unvalidated device path.  Env i's lists take
+    the first sub[i] substeps.  (Which solve a substep takes -- register-resident, or streamed rows when its contacts
+    outgrow the 64 slots -- is decided substep by substep from the state alone, so the replay follows the step kernel
+    bit for bit.)"""
+    st = env._stepper
+    if env.telemetry == 'kernel':
+        obs, rew, done, sub, trace = st.step_traced(actions, vec_mode=vec_mode)
+        return obs, rew, done, sub, _lib.trace_to_lists(trace, sub, env.params.n_modules)
+    before = st.snapshot(reset_pose=False)
+    obs, rew, done, sub = st.step(actions, vec_mode=vec_mode)        # (clips `actions` in place)
+    if env._scratch is None:
+        env._scratch = _lib.Stepper(st.n_envs, device=st.device, params=env.params)
+    sc = env._scratch
+    sc.restore(before)
+    targets = joint_targets(env.params, actions)
+    io, lp = [[] for _ in sub], [[] for _ in sub]
+    for s_ in range(int(sub.max())):
+        sc.substep(targets, 1)
+        o, l = sc.get_obs(), sc.link_positions()
+        for i in np.nonzero(sub > s_)[0]:
+            io[i].append(o[i].astype(np.float64))
+            lp[i].append(l[i].astype(np.float64))
+    return obs, rew, done, sub, (io, lp)
+
+
+def _telemetry_infos(lists, obs, unfinished, what, name_env):
+    """Test mode's infos from the per-env lists of _test_mode_step / trace_to_lists.  A done env's lists hold the step
+    that ended its episode (they are cleared at the start of the next step, not by the reset); the last row of every
+    env of `unfinished` -- the returned observation is its last substep's -- must be that observation bit for bit, else
+    SystemError(what), with the env's index behind it when `name_env`."""
+    io, lp = lists
+    for i in np.nonzero(unfinished)[0]:
+        if io[i] and not np.array_equal(io[i][-1].astype(np.float32), obs[i]):
+            raise SystemError(what + (" (env %d)" % i if name_env else ""))
+    return tuple({'frames': [], 'internal_observations': io[i], 'link_positions': lp[i]} for i in range(len(io)))
+
+
 class Snake(object):
     """Robot facade with the attribute surface the reference's callers touch.
 
@@ -290,6 +350,7 @@ class SnakeGymEnv(object):
         self._action_bound = 1
         self.params = params_from_args(args, n_modules=n_modules, **over)
         self._stepper = _lib.Stepper(1, device=device, params=self.params)   # = hard reset
+        self._scratch = None              # test mode's replay handle: made by the first replay (_test_mode_step)
         self._pushed_pose = None          # the robot's init* as the handle's table holds them (None: the defaults)
         self.robot._env = self
         self._observation = self._get_obs()
@@ -315,7 +376,7 @@ class SnakeGymEnv(object):
             self._pushed_pose = None      # (a new handle: the default table, and the zero pose, snake.py:93)
             # the test-mode replay handle was built for the old world (params, obstacle, contact cache): a new one is
             # made on the next test-mode step
-            if getattr(self, "_scratch", None) is not None:
+            if self._scratch is not None:
                 self._scratch.close()
                 self._scratch = None
         else:
@@ -336,17 +397,16 @@ class SnakeGymEnv(object):
         # SnakeGymEnv.step's own reset on done (SnakeGymEnv.py:39-41) happens inside the step kernel: the pose it reads
         # must be the robot's current one
         self._push_reset_pose()
-        traced = self.mode == 'test' and self.telemetry == 'kernel'
-        if self.mode == 'test' and not traced:
-            before = self._stepper.get_state() + (self._stepper.get_manifold(),
-                                                  self._stepper.get_box() if self.params.obstacle == 2 else None)
-        if traced:
-            obs, rew, done, sub, trace = self._stepper.step_traced(a32, vec_mode=False)
-            self._kernel_telemetry(trace, sub, obs[0])
+        info = {}
+        if self.mode == 'test':
+            # vec_mode 0: the returned observation is the last substep's whether the episode ended or not
+            obs, rew, done, sub, lists = _test_mode_step(self, a32, vec_mode=False)
+            info = _telemetry_infos(lists, obs, [True], DIVERGED[self.telemetry], name_env=False)[0]
+            r = self.robot
+            r.imgs, r.step_internal_observations, r.link_positions = (info['frames'], info['internal_observations'],
+                                                                      info['link_positions'])
         else:
             obs, rew, done, sub = self._stepper.step(a32, vec_mode=False)
-        if self.mode == 'test' and not traced:
-            self._record_telemetry(before, a32[0], int(sub[0]), obs[0])
         try:
             for idx in range(len(action)):
                 if action[idx] < -1 or action[idx] > 1:
@@ -356,60 +416,7 @@ class SnakeGymEnv(object):
         observation = obs[0].astype(np.float64)
         self.robot.counter = int(sub[0])
         self._observation = observation
-        if self.mode == 'test':
-            info = {'frames': self.robot.imgs, 'internal_observations': self.robot.step_internal_observations,
-                    'link_positions': self.robot.link_positions}
-        else:
-            info = {}
         return observation, float(rew[0]), bool(done[0]), info
-
-    def _kernel_telemetry(self, trace, sub, final_obs):
-        """Test mode with telemetry='kernel': the same lists as _record_telemetry's, from the rows the step kernel wrote
-        after every substep (snk_step_traced): no scratch handle, no state downloads.  vec_mode is 0 here, so the
-        returned observation is the last substep's whether the episode ended or not."""
-        r = self.robot
-        r.imgs = []
-        io, lp = _lib.trace_to_lists(trace, sub, self.params.n_modules)
-        r.step_internal_observations, r.link_positions = io[0], lp[0]
-        if io[0] and not np.array_equal(io[0][-1].astype(np.float32), final_obs):
-            raise SystemError("test-mode trace diverged from the step kernel's observation")
-
-    def _record_telemetry(self, before, clipped_action, n_substeps, final_obs):
-        """Test mode (snake.py:275-293, SnakeGymEnv.py:43-44): the observation and the link
-        positions after every physics substep of this env-step.  The fused step kernel stays the
-        authority for state, reward and termination; the substeps are replayed one at a time on a
-        scratch 1-env handle from the state the step started in (same device code, so the replay
-        ends on the observation the step returned)."""
-        r = self.robot
-        r.imgs, r.step_internal_observations, r.link_positions = [], [], []
-        if getattr(self, "_scratch", None) is None:
-            self._scratch = _lib.Stepper(1, device=self._stepper.device, params=self.params)
-        sc = self._scratch
-
-        sc.set_state(before[0], before[1])
-        if before[2] is not None:         # contact_model 1: the contact cache is part of the state the step started in
-            sc.set_manifold(before[2])
-        if before[3] is not None:         # ... and so is a free obstacle box
-            sc.set_box(*before[3])
-        n = self.params.n_modules
-        # createAction + convertActionToJointCommand with the gait and scale the DEVICE uses (self.params: they
-        # may have been overridden through **over, which the robot facade does not see)
-        targets = np.zeros((1, n), dtype=np.float32)
-        if self.params.gait == 0:
-            targets[0, 0::2] = clipped_action
-        elif self.params.gait == 1:
-            targets[0, 1::2] = clipped_action
-        else:
-            targets[0, :] = clipped_action
-        targets *= np.float32(self.params.scaling_factor)
-        for _ in range(n_substeps):
-            sc.substep(targets, 1)
-            r.step_internal_observations.append(sc.get_obs()[0].astype(np.float64))
-            r.link_positions.append(sc.link_positions()[0].astype(np.float64))
-        # (which solve a substep takes -- register-resident, or streamed rows when its contacts outgrow the 64 slots -- is
-        #  decided substep by substep from the state alone, so the replay follows the step kernel bit for bit)
-        if n_substeps and not np.array_equal(r.step_internal_observations[-1].astype(np.float32), final_obs):
-            raise SystemError("test-mode replay diverged from the step kernel")
 
     def render(self):
         """SnakeGymEnv.py:52-58: in test mode the robot's frame, in train mode an empty array.  Without render='kernel'
@@ -420,7 +427,7 @@ class SnakeGymEnv(object):
 
     def close(self):
         self._stepper.close()
-        if getattr(self, "_scratch", None) is not None:
+        if self._scratch is not None:
             self._scratch.close()
 
     def defObservationSpace(self):
@@ -554,74 +561,21 @@ class SnakeVecEnv(VecEnv):
         self.waiting = True
 
     def step_wait(self):
-        if self.mode == 'test' and self.telemetry == 'kernel':
-            obs, rew, done, sub, trace = self._stepper.step_traced(self._pending, vec_mode=True)
-            self.waiting = False
-            self.last_substeps = sub
-            return obs, rew, done, self._kernel_telemetry(trace, sub, obs, done)
         if self.mode == 'test':
-            st = self._stepper
-            before = st.get_state() + (st.get_manifold(), st.get_box() if self.params.obstacle == 2 else None)
-        obs, rew, done, sub = self._stepper.step(self._pending, vec_mode=True)
+            obs, rew, done, sub, lists = _test_mode_step(self, self._pending, vec_mode=True)
+        else:
+            obs, rew, done, sub = self._stepper.step(self._pending, vec_mode=True)
         self.waiting = False
         self.last_substeps = sub
         if self.mode == 'test':
-            return obs, rew, done, self._telemetry(before, self._pending, sub, obs, done)
+            # what each of the reference's workers would put into its info; a done env's returned observation is the
+            # post-reset one, so only the others are checked
+            return obs, rew, done, _telemetry_infos(lists, obs, ~done, DIVERGED[self.telemetry], name_env=True)
         # train mode: one fresh empty dict per env per step, as the reference's workers send (SnakeGymEnv.py:46-47 through
         # multiprocessing_env.py:11-16; zip(*results) makes the tuple): wrappers may annotate infos[i], rollout buffers
         # may pickle them.  0.15 ms for 4096 envs; shared_infos=True hands out one read-only FrozenInfo instead.
         infos = self._shared_infos if self._shared_infos is not None else tuple({} for _ in range(self.nenvs))
         return obs, rew, done, infos
-
-    def _kernel_telemetry(self, trace, sub, obs, done):
-        """_telemetry's infos from the rows the step kernel wrote after every substep (telemetry='kernel',
-        snk_step_traced): no scratch handle, no state downloads, no replay.  The rows of a done env hold the step that
-        ended its episode (its returned observation is the post-reset one); the last row of every other env must be the
-        observation the step returned, bit for bit."""
-        io, lp = _lib.trace_to_lists(trace, sub, self.params.n_modules)
-        for i in range(self.nenvs):
-            if sub[i] and not done[i] and not np.array_equal(io[i][-1].astype(np.float32), obs[i]):
-                raise SystemError("test-mode trace diverged from the step kernel's observation (env %d)" % i)
-        return tuple({'frames': [], 'internal_observations': io[i], 'link_positions': lp[i]} for i in range(self.nenvs))
-
-    def _telemetry(self, before, clipped_actions, sub, obs, done):
-        """Test mode through the vector seam: what each of the reference's workers would put into its info -- the
-        observation and the link positions after every physics substep of ITS env-step (snake.py:275-293; the lists are
-        cleared at the start of the next step, not by the worker's reset, so a done env's info still carries the step that
-        ended its episode).  As in the single-env seam the fused kernel stays the authority and the substeps are replayed
-        one launch at a time on a scratch handle of the same size from the state, contact cache and box the step started
-        in; env i's lists take the first sub[i] of them.  The replay of an env that did not end its episode must end bit
-        for bit on the observation the step returned."""
-        if self._scratch is None:
-            self._scratch = _lib.Stepper(self.nenvs, device=self._stepper.device, params=self.params)
-            self._scratch.set_ground_friction(self._stepper.get_ground_friction())
-        sc = self._scratch
-        sc.set_state(before[0], before[1])
-        if before[2] is not None:
-            sc.set_manifold(before[2])
-        if before[3] is not None:
-            sc.set_box(*before[3])
-        n = self.params.n_modules
-        targets = np.zeros((self.nenvs, n), dtype=np.float32)
-        if self.params.gait == 0:
-            targets[:, 0::2] = clipped_actions
-        elif self.params.gait == 1:
-            targets[:, 1::2] = clipped_actions
-        else:
-            targets[:, :] = clipped_actions
-        targets *= np.float32(self.params.scaling_factor)
-        io = [[] for _ in range(self.nenvs)]
-        lp = [[] for _ in range(self.nenvs)]
-        for s_ in range(int(sub.max()) if len(sub) else 0):
-            sc.substep(targets, 1)
-            o, l = sc.get_obs(), sc.link_positions()
-            for i in np.nonzero(sub > s_)[0]:
-                io[i].append(o[i].astype(np.float64))
-                lp[i].append(l[i].astype(np.float64))
-        for i in range(self.nenvs):
-            if sub[i] and not done[i] and not np.array_equal(io[i][-1].astype(np.float32), obs[i]):
-                raise SystemError("test-mode replay diverged from the step kernel (env %d)" % i)
-        return tuple({'frames': [], 'internal_observations': io[i], 'link_positions': lp[i]} for i in range(self.nenvs))
 
     def reset(self):
         return self._stepper.reset()
@@ -653,8 +607,6 @@ class SnakeVecEnv(VecEnv):
 
     def set_ground_friction(self, mu):
         self._stepper.set_ground_friction(mu)
-        if self._scratch is not None:
-            self._scratch.set_ground_friction(self._stepper.get_ground_friction())
 
     def close(self):
         if self.closed:
@@ -675,7 +627,7 @@ class SubprocVecEnv(SnakeVecEnv):
     parameters and mode (the envs are closed again; thunks that differ are refused, see below);
     len(env_fns) environments are then created on the GPU in one handle.  Thunks that build
     mode='test' envs get what the reference's workers would send: every env's info carries its
-    per-substep telemetry (SnakeVecEnv._telemetry).
+    per-substep telemetry (_test_mode_step).
 
     A thunk's robot may carry its own initPosition / initOrientation / initState (snake.py:22-24): per-env data, not a
     parameter, so thunks may differ in it and env i starts its episodes from thunk i's pose.  LIMIT: beyond kHeteroProbe

@@ -585,8 +585,8 @@ def test_sensor_pass_only_when_observable(pkg, n):
     rng = np.random.default_rng(3)
     for j in range(6 if n == 16 else 3):
         a = gait_actions(np.arange(B), j, A).astype(np.float32) if j % 2 == 0 else rng.uniform(-1, 1, (B, A)).astype(np.float32)
-        S, X = st.get_state()
-        Mf = st.get_manifold()                                           # the contact cache is simulator state too
+        before = st.snapshot(reset_pose=False)                           # the contact cache is simulator state too
+        X = before.aux
         obs, rew, done, sub = st.step(a.copy(), vec_mode=False)          # terminal obs even when done
         # replay with the substep API: group envs by their substep count
         T = np.zeros((B, n), np.float32)
@@ -594,9 +594,7 @@ def test_sensor_pass_only_when_observable(pkg, n):
         # Replay one substep per call (which solve a substep takes is decided from the state alone, substep by substep,
         # so the fused kernel and the one-substep calls go the same way)
         Xf = X.copy()
-        rp.set_state(S, X)
-        if Mf is not None:
-            rp.set_manifold(Mf)
+        rp.restore(before)
         for c in range(1, int(sub.max()) + 1):
             rp.substep(T, 1)
             if np.any(sub == c):
@@ -920,8 +918,7 @@ def test_overflow_substep_replicas_agree(pkg, monkeypatch):
     st.reset()
     st.set_ground_friction(fr)
     a = np.clip(gait(range(B), 0, A) * 1.2, -1, 1).astype(np.float32)
-    S, X = st.get_state()
-    Mf = st.get_manifold()
+    snap = st.snapshot()
     tg = np.zeros((B, n), np.float32)
     tg[:, 1::2] = a * np.float32(np.pi / 6)
     e = None
@@ -933,13 +930,13 @@ def test_overflow_substep_replicas_agree(pkg, monkeypatch):
             break
     assert e is not None, "no substep beyond 64 contacts in the gait's first env-step"
     idx = np.arange(7, B, 13)
-    S2, X2, M2, a2, f2 = S.copy(), X.copy(), Mf.copy(), a.copy(), fr.copy()
-    S2[idx], X2[idx], M2[idx], a2[idx], f2[idx] = S[e], X[e], Mf[e], a[e], fr[e]
+    src = np.arange(B)
+    src[idx] = e
+    a2, f2 = a[src], fr[src]
+    assert np.array_equal(snap[src].ground_friction, f2)
     first = None
     for rep in range(3):
-        st.set_ground_friction(f2)
-        st.set_state(S2, X2)
-        st.set_manifold(M2)
+        st.restore(snap[src])
         c0 = st.contact_overflow()[0]
         o, r, d, s = st.step(a2.copy())
         assert st.contact_overflow()[0] - c0 >= len(idx)             # every replica took the in-place streamed substep
@@ -974,25 +971,16 @@ def test_replicas_agree_whatever_runs_beside_them(pkg, monkeypatch, case):
         st.set_ground_friction(fr)
         for j in range(2):
             st.step((gait(range(B), j, A) * 1.2).astype(np.float32))
-        S, X = st.get_state()
-        Mf = st.get_manifold()
-        BX = st.get_box() if over.get("obstacle") == 2 else None
+        snap = st.snapshot()
         a = (gait(range(B), 2, A) * 1.2).astype(np.float32)
         o0, r0, d0, s0 = st.step(a.copy())
         idx = np.arange(7, B, 13)
         for e in (int(np.argmax(s0)), int(np.argmin(s0 + 100 * (s0 == 0))), 1234 % B):
-            S2, X2, a2, f2 = S.copy(), X.copy(), a.copy(), fr.copy()
-            S2[idx], X2[idx], a2[idx], f2[idx] = S[e], X[e], a[e], fr[e]
-            st.set_ground_friction(f2)
-            st.set_state(S2, X2)
-            if Mf is not None:
-                M2 = Mf.copy()
-                M2[idx] = Mf[e]
-                st.set_manifold(M2)
-            if BX is not None:
-                b0, b1 = BX[0].copy(), BX[1].copy()
-                b0[idx], b1[idx] = BX[0][e], BX[1][e]
-                st.set_box(b0, b1)
+            src = np.arange(B)
+            src[idx] = e
+            a2, f2 = a[src], fr[src]
+            assert np.array_equal(snap[src].ground_friction, f2)
+            st.restore(snap[src])
             o, r, d, s = st.step(a2.copy())
             assert len(np.unique(o[idx], axis=0)) == 1, (n, over, quantum, e)
             assert np.array_equal(o[idx[0]], o0[e]) and r[idx[0]] == r0[e] and s[idx[0]] == s0[e], (n, over, quantum, e)
@@ -1039,18 +1027,12 @@ def test_slot_permutation_invariance(pkg, n, B, over):
     st.set_ground_friction(fr)
     for j in range(2):
         st.step((gait(range(B), j, A) * 1.2).astype(np.float32))
-    S, X = st.get_state()
-    Mf = st.get_manifold()
-    BX = st.get_box() if over.get("obstacle") == 2 else None
+    snap = st.snapshot()
     acts = [(gait(range(B), 2 + j, A) * 1.2).astype(np.float32) for j in range(3)]
 
     def run(p):
-        st.set_ground_friction(fr[p])
-        st.set_state(S[p], X[p])
-        if Mf is not None:
-            st.set_manifold(Mf[p])
-        if BX is not None:
-            st.set_box(BX[0][p], BX[1][p])
+        assert np.array_equal(snap[p].ground_friction, fr[p])
+        st.restore(snap[p])
         outs = []
         for a in acts:
             o, r, d, s = st.step(a[p].copy())

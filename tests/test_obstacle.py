@@ -157,7 +157,7 @@ def test_add_obstacle_mirror(pkg):
 
 @gpu
 def test_test_mode_survives_world_rebuilds(pkg):
-    """mode='test' replays every env-step substep by substep on a scratch handle (SnakeGymEnv._record_telemetry) and
+    """mode='test' replays every env-step substep by substep on a scratch handle (snake_env._test_mode_step) and
     insists on ending on the step kernel's bits.  The scratch handle must follow the world: add_obstacle AFTER a first
     step rebuilds it with the box, a hard reset empties its contact cache like the main handle's."""
     import argparse
