@@ -7,7 +7,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
+#include <memory>
 #include <string>
 #include <mutex>
 #include <vector>
@@ -52,17 +54,15 @@ struct snk_handle {
     float* d_tgt = nullptr;
     int32_t* d_info = nullptr;
     float* d_h = nullptr;
-    float* d_linkpos = nullptr;   // allocated on first snk_link_positions
-    float* d_trace = nullptr;     // allocated on first snk_step_traced_host: [n_envs][d_trace_rows][trace row floats]
-    int d_trace_rows = 0;
+    float* d_linkpos = nullptr;   // made on first snk_link_positions (ensure)
+    float* d_trace = nullptr;     // made and grown by snk_step_traced_host (ensure): [n_envs][trace_rows][trace row floats]
     float* d_mf = nullptr;        // contact_model 1: the persistent contact manifolds, [n_envs][2n][kMfFloats]
     float* d_rows = nullptr;      // 32-link chains: constraint rows streamed from global memory (snk_device.hpp: pgs_v1)
     unsigned long long* d_ovf = nullptr;   // contacts the solves had no room for (snk_contact_overflow): 3 counters
     float* d_box = nullptr;       // obstacle 2: the free box of every env, [n_envs][kBoxFloats] (state 13, count, manifold 24)
     float* d_reset = nullptr;     // the reset-pose table, [n_envs][reset_row_floats(n)] = [pos 3 | quat xyzw 4 | q n | padding]
     int32_t* d_order = nullptr;
-    float* d_render = nullptr;    // snk_render's per-image primitive and camera tables (snk_render.hip), allocated on first use
-    size_t d_render_bytes = 0;
+    float* d_render = nullptr;    // snk_render's per-image primitive and camera tables (snk::render_scratch), made on first use
     bool plan = true;
     // in-launch scheduler of env_step_sched_kernel (snk_device.hpp): rings, counters, the host-mapped alarm word
     snk::Sched sched = {};
@@ -74,6 +74,10 @@ struct snk_handle {
     // timing: pool of event pairs, one pair per snk_step launch, read back in one go
     std::vector<hipEvent_t> ev;
     int ev_used = 0;
+    // THE OWNER of the handle's device memory: every d_* pointer above and every pointer of `sched` is one of these slots
+    // (ensure, below, is the only place that allocates one; snk_destroy frees the list)
+    struct Owned { void** slot; size_t bytes; };
+    std::vector<Owned> owned;
 };
 
 namespace {
@@ -103,9 +107,27 @@ int dispatch(const snk_handle* h, F&& fn) {
 
 // floats per row of the trace buffer (snk_trace_row_floats): the payload [obs | link positions] in whole 128-byte lines
 int trace_row_floats(int n) { return (3 * n + 8 + 3 * (n + 1) + 31) / 32 * 32; }
-
 // floats per row of the reset-pose table (snk::kResetRow): the payload [pos 3 | quat 4 | q n] in whole 128-byte lines
 int reset_row_floats(int n) { return (7 + n + 31) / 32 * 32; }
+
+// ensure: THE place where a handle gets device memory.  Afterwards *slot -- a member of *h or of h->sched: the list keeps
+// its address -- holds at least `bytes`: made now if it did not exist, replaced (contents NOT kept) if it was too small,
+// and a new buffer has every byte set to `fill` (kNoFill: left as it comes).  The device is idle before an old buffer
+// goes: nothing enqueued still reads it.
+constexpr int kNoFill = -1;
+template <class T>
+int ensure(snk_handle* h, T** slot, size_t bytes, int fill = kNoFill) {
+    snk_handle::Owned* o = nullptr;
+    for (snk_handle::Owned& x : h->owned)
+        if (x.slot == reinterpret_cast<void**>(slot)) o = &x;
+    if (o && o->bytes >= bytes) return 0;
+    if (!o) { h->owned.push_back({reinterpret_cast<void**>(slot), 0}); o = &h->owned.back(); }
+    if (*slot) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(*slot); *slot = nullptr; o->bytes = 0; }
+    HIP_TRY(hipMalloc(slot, bytes));
+    o->bytes = bytes;
+    if (fill != kNoFill) HIP_TRY(hipMemset(*slot, fill, bytes));
+    return 0;
+}
 
 // packed_stride > 0 (snk_step_packed): obs rows of that stride, reward and done flag behind each row's observation.
 // TRACE (snk_step_traced): the kernels that also write `trace`, trace_rows rows per env.
@@ -201,13 +223,31 @@ int check_alarm(const snk_handle* h) {
         return fail("env-step scheduler: a bounded wait ran out (state of this handle is no longer valid; snk_destroy it)");
     return 0;
 }
-// the state accessors: the device idle (a step enqueued on a non-blocking stream may still be running), then the alarm
-#define SNK_SYNC_ALIVE(h)                           \
-    do {                                            \
-        HIP_TRY(hipSetDevice((h)->device));         \
-        HIP_TRY(hipDeviceSynchronize());            \
-        if (check_alarm(h)) return 1;               \
-    } while (0)
+
+// THE ENTRY CONTRACT.  Every entry point calls enter(h, what) once, behind its own null-argument refusals (and where
+// a call today names another refusal first -- "null buffer", "no contact cache", "no free box" -- behind that too):
+//   D  kDev    hipSetDevice(h->device)
+//   I  kIdle   hipDeviceSynchronize(): a step enqueued on a non-blocking stream may still be running
+//   A  kAlive  refuses a poisoned handle (check_alarm), after D and I
+// The code's copy of the paragraph at snk_debug_raise_alarm in include/snk.h:
+//   D I A  snk_get_state  snk_set_state  snk_get_manifold  snk_set_manifold  snk_get_box  snk_set_box  snk_get_obs
+//          snk_mean_height  snk_link_positions  snk_joint3_reaction_fz  snk_set_ground_friction  snk_get_reset_pose
+//          snk_set_reset_pose  snk_debug_set_tickets  snk_render_host
+//   D . A  snk_reset  snk_step  snk_step_packed  snk_step_traced  snk_reset_host  snk_step_host  snk_step_traced_host
+//          snk_substep_host  snk_set_reset_pose_dev  snk_render
+//   . . A  snk_reset_pose_floats (returns 0)
+//   D I .  snk_get_ground_friction  snk_contact_overflow  snk_contact_histogram  snk_contact_histogram_enable
+//          snk_destroy (the two calls bare: errors ignored, snk_last_error untouched)
+//   D . .  snk_timing_enable  snk_timing_read
+//   . I .  snk_sched_stats (SNK_SCHED_DEBUG builds)
+//   . . .  snk_num_envs  snk_obs_dim  snk_act_dim  snk_state_dim  snk_record_floats  snk_trace_row_floats
+//          snk_manifold_floats  snk_model_describe  snk_debug_raise_alarm; and the calls without a handle
+enum : unsigned { kDev = 1, kIdle = 2, kAlive = 4, kState = kDev | kIdle | kAlive };
+int enter(const snk_handle* h, unsigned what) {
+    if (what & kDev) HIP_TRY(hipSetDevice(h->device));
+    if (what & kIdle) HIP_TRY(hipDeviceSynchronize());
+    return (what & kAlive) ? check_alarm(h) : 0;
+}
 
 int check_launch() {
     hipError_t e = hipGetLastError();
@@ -219,7 +259,6 @@ int check_launch() {
 // events while the pool has one left
 int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode, hipStream_t st,
                int packed_stride, float* trace = nullptr, int trace_rows = 0) {
-    HIP_TRY(hipSetDevice(h->device));
     const bool timed = 2 * h->ev_used + 1 < (int)h->ev.size();
     if (timed) HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used], st));
     const int rc = dispatch(h, [&](auto k) {
@@ -273,20 +312,86 @@ float manifold_from_host(const float* o, float* pts) {
     return o[0] >= 0.f ? (o[0] <= 4.f ? floorf(o[0]) : 4.f) : 0.f;
 }
 
+// A per-environment device table: `rows` rows of `stride` floats (the padding included).  The handle's tables:
+struct RowTable { float* d; size_t stride, rows; };
+// the state records: [base 13 | q n | qd n || motor torques n | joint-0 fz | previous x || joint-3 fz | padding]
+//                     `-- state_dim = 13 + 2n --'`------------- aux: n + 2 ------------'
+RowTable records(const snk_handle* h) { return {h->d_recs, (size_t)h->rec, (size_t)h->n_envs}; }
+size_t rec_joint3_fz(const snk_handle* h) { return (size_t)(15 + 3 * h->n); }
+RowTable friction(const snk_handle* h) { return {h->d_mu, 1, (size_t)h->n_envs}; }
+RowTable reset_poses(const snk_handle* h) { return {h->d_reset, (size_t)reset_row_floats(h->n), (size_t)h->n_envs}; }
+// one row per CYLINDER: [count, 3 pad, 4 x (a3, b.x, b.y, lambda)]
+RowTable link_manifolds(const snk_handle* h) { return {h->d_mf, (size_t)snk::kMfFloats, (size_t)h->n_envs * 2 * h->n}; }
+// the free box: [state 13 | count, 4 x (a3, b.x, b.y, lambda) | padding]
+RowTable boxes(const snk_handle* h) { return {h->d_box, (size_t)snk::kBoxFloats, (size_t)h->n_envs}; }
+constexpr size_t kBoxState = 13, kBoxMf = 25;
+
+// Column range [first, first + width) of a table and its dense host array [rows][width] (null: skipped; rows_get WRITES it)
+struct Cols { size_t first, width; const float* host; };
+// rows [r0, r1) of one range straight between the table and its host array (`set`: to the device)
+int direct(const RowTable& t, const Cols& c, size_t r0, size_t r1, bool set) {
+    const size_t f = sizeof(float), dp = t.stride * f, hp = c.width * f;
+    float *dev = t.d + r0 * t.stride + c.first, *hst = const_cast<float*>(c.host) + r0 * c.width;
+    const hipMemcpyKind kind = set ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    if (c.width == t.stride) HIP_TRY(hipMemcpy(set ? dev : hst, set ? hst : dev, (r1 - r0) * hp, kind));
+    else HIP_TRY(hipMemcpy2D(set ? dev : hst, set ? dp : hp, set ? hst : dev, set ? hp : dp, hp, r1 - r0, kind));
+    return 0;
+}
+// rows_get / rows_set: THE transfer between a table and dense host arrays (the device idle: enter(kIdle)), `mask` [rows]
+// (null: all) naming the rows rows_set writes.  Measured (profiles/r13_host_api_before_after.txt): a table of up to
+// kDirectBytes goes range by range, strided, unstaged (16 envs, every table <= 57 KB: this wins); a larger one crosses
+// whole, once, the ranges gathered / scattered on the host (4096 envs, >= 512 KB: wins by 25 %).  Whole rows go straight.
+constexpr size_t kDirectBytes = 64 << 10;
+int rows_move(const RowTable& t, std::initializer_list<Cols> cols, const uint8_t* mask, bool set) {
+    const size_t bytes = t.rows * t.stride * sizeof(float);
+    const bool staged = bytes > kDirectBytes && !(cols.size() == 1 && cols.begin()->width == t.stride && !mask);
+    std::vector<float> all(staged ? t.rows * t.stride : 0);
+    if (staged) HIP_TRY(hipMemcpy(all.data(), t.d, bytes, hipMemcpyDeviceToHost));
+    for (const Cols& c : cols)
+        for (size_t r0 = 0, r1; c.host && r0 < t.rows; r0 = r1 + 1) {      // every run [r0, r1) of rows the mask names
+            for (r1 = r0; r1 < t.rows && (!mask || mask[r1]); r1++) {}
+            if (!staged && r1 > r0 && direct(t, c, r0, r1, set)) return 1;
+            for (size_t r = r0; staged && r < r1; r++) {
+                float *a = &all[r * t.stride + c.first], *x = const_cast<float*>(c.host) + r * c.width;
+                memcpy(set ? a : x, set ? x : a, c.width * sizeof(float));
+            }
+        }
+    if (staged && set) HIP_TRY(hipMemcpy(t.d, all.data(), bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+int rows_get(const RowTable& t, std::initializer_list<Cols> cols) { return rows_move(t, cols, nullptr, false); }
+int rows_set(const RowTable& t, std::initializer_list<Cols> cols, const uint8_t* mask = nullptr) { return rows_move(t, cols, mask, true); }
+
+// h->D to the device: the handle's copy in global memory and, on a scheduled handle, its slot of snk::g_models
+int upload_model(snk_handle* h) {
+    HIP_TRY(hipMemcpy(h->d_model, &h->D, sizeof(snk::DevModel), hipMemcpyHostToDevice));
+    if (h->model_slot >= 0)
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(snk::g_models), &h->D, sizeof(snk::DevModel),
+                                  (size_t)h->model_slot * sizeof(snk::DevModel), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the host and device models of bare params (the models are large: on the heap)
+struct Models { snk::HostModel H; snk::DevModel D; };
+std::unique_ptr<Models> models_of(const snk_params& p) {
+    std::unique_ptr<Models> m(new Models);
+    snk::build_host_model(p, m->H);
+    snk::build_dev_model(p, m->H, m->D);
+    return m;
+}
+
 }  // namespace
 
 // the renderer's seam (snk_render_view.hpp): its translation unit sees this much of a handle, and reports through g_err
 namespace snk {
 int api_fail(const char* msg) { return fail(msg); }
 int render_view(snk_handle* h, bool sync, RenderView* v) {
-    HIP_TRY(hipSetDevice(h->device));
-    if (sync) HIP_TRY(hipDeviceSynchronize());
-    if (check_alarm(h)) return 1;
+    if (enter(h, sync ? kState : (kDev | kAlive))) return 1;
     v->device = h->device; v->n = h->n; v->n_envs = h->n_envs; v->v2 = h->v2;
     v->D = &h->D; v->d_model = h->d_model; v->d_recs = h->d_recs; v->d_box = h->d_box;
-    v->scratch = &h->d_render; v->scratch_bytes = &h->d_render_bytes;
     return 0;
 }
+float* render_scratch(snk_handle* h, size_t need) { return ensure(h, &h->d_render, need) ? nullptr : h->d_render; }
 }  // namespace snk
 
 extern "C" {
@@ -354,6 +459,33 @@ void snk_default_params(snk_params* p) {
 
 int snk_destroy(snk_handle* h);
 namespace {
+// scheduler state (snk_device.hpp: Sched): the model slot, the rings and counters, the host-mapped alarm word
+int init_sched(snk_handle* h) {
+    const char* q = getenv("SNK_QUANTUM");       // substeps per slice; 0 = whole env-steps in launch order
+    const int quantum = q ? atoi(q) : 1;
+    h->model_slot = quantum > 0 ? take_model_slot() : -1;
+    h->use_sched = h->model_slot >= 0;
+    snk::Sched& sc = h->sched;
+    sc.cap = 2u;                                  // power of two >= 2 n_envs: slot = ticket & (cap - 1) survives the
+    while (sc.cap < 2u * (uint32_t)h->n_envs) sc.cap <<= 1;      // wrap-around of the 32-bit tickets
+    sc.quantum = quantum;
+    const char* hy = getenv("SNK_HYST");          // experiments: see snk_device.hpp Sched::hyst
+    sc.hyst = hy ? atoi(hy) : 3;
+    if (sc.hyst < 1) sc.hyst = 1;
+    if (ensure(h, &sc.head, sizeof(uint32_t), 0) || ensure(h, &sc.tail, sizeof(uint32_t), 0) ||
+        ensure(h, &sc.waiting, snk::kBuckets * sizeof(int32_t), 0) ||
+        ensure(h, &sc.ent, (size_t)sc.cap * sizeof(unsigned long long), 0xFF) ||      // (all bits set: an empty slot)
+        ensure(h, &sc.counter, (size_t)h->n_envs * sizeof(int32_t)) || ensure(h, &sc.finished, sizeof(int32_t), 0))
+        return 1;
+    HIP_TRY(hipHostMalloc(&h->h_alarm, 64 * sizeof(int32_t), hipHostMallocMapped));
+    memset(h->h_alarm, 0, 64 * sizeof(int32_t));
+    HIP_TRY(hipHostGetDevicePointer((void**)&sc.alarm, h->h_alarm, 0));
+#ifdef SNK_SCHED_DEBUG
+    if (ensure(h, &sc.wstat, (size_t)h->grid_waves * 8 * sizeof(long long))) return 1;
+#endif
+    return 0;
+}
+
 // everything snk_create allocates; on failure the caller destroys the half-built handle
 int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t device) {
     h->P = *p;
@@ -365,6 +497,7 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     // SNK_POISON=1 (tests): the kernels' LDS images and every fresh device allocation start as NaNs instead of as
     // whatever was there, so that a read of something never written shows in the outputs
     const bool poison = getenv("SNK_POISON") != nullptr;
+    const int nans = poison ? 0xFF : kNoFill;
     h->D.poison = poison ? 1 : 0;
     h->D.hist = 0;
     h->rec = h->D.rec_floats;
@@ -382,129 +515,63 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
         return set_lds_attr(k, h->lds_bytes);
     });
     if (rc) return rc;
-    const size_t ne = (size_t)n_envs;
-    HIP_TRY(hipMalloc(&h->d_model, sizeof(snk::DevModel)));
-    HIP_TRY(hipMemcpy(h->d_model, &h->D, sizeof(snk::DevModel), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&h->d_recs, ne * h->rec * sizeof(float)));
-    HIP_TRY(hipMemset(h->d_recs, 0, ne * h->rec * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_mu, ne * sizeof(float)));
-    std::vector<float> ones(ne, 1.0f);   // plane.urdf lateral_friction = 1 [U]
-    HIP_TRY(hipMemcpy(h->d_mu, ones.data(), ne * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&h->d_act, ne * h->D.act_dim * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_obs, ne * h->D.obs_dim * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_rew, ne * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_done, ne));
-    HIP_TRY(hipMalloc(&h->d_sub, ne * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&h->d_mask, ne));
-    HIP_TRY(hipMalloc(&h->d_tgt, ne * h->n * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_info, ne * 2 * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&h->d_h, ne * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_order, ne * sizeof(int32_t)));
-    if (poison) {
-        const size_t na = ne * h->D.act_dim * sizeof(float), no = ne * h->D.obs_dim * sizeof(float);
-        HIP_TRY(hipMemset(h->d_act, 0xFF, na)); HIP_TRY(hipMemset(h->d_obs, 0xFF, no));
-        HIP_TRY(hipMemset(h->d_rew, 0xFF, ne * sizeof(float))); HIP_TRY(hipMemset(h->d_tgt, 0xFF, ne * h->n * sizeof(float)));
-        HIP_TRY(hipMemset(h->d_h, 0xFF, ne * sizeof(float)));
-    }
-    {
-        int waves = 0;
-        rc = resident_waves(h->lds_bytes, device, &waves);
-        if (rc) return rc;
-        h->grid_waves = waves > 0 && waves < n_envs ? waves : n_envs;
-    }
-    {
-        // (16-link handles on the register-resident solve need them too: a substep whose contacts outgrow its 64 slots
-        //  goes through the streamed-row solve in place, snk_device.hpp: substep())
-        // one block of streamed constraint rows per RESIDENT WAVE (every step / substep kernel is launched with that many
-        // workgroups and strides over the environments): 2048 x 112 KB = 230 MB for 32 links, whatever n_envs is
-        const size_t nb = (size_t)h->grid_waves;
-        const size_t bytes = nb * rf * sizeof(float);
-        HIP_TRY(hipMalloc(&h->d_rows, bytes));
-        HIP_TRY(hipMemset(h->d_rows, poison ? 0xFF : 0, bytes));
-        // what the kernels rely on being zero for good: the last three rows of every block (the refill of a skipped
-        // friction pair) and the pad columns of the M^-1 block behind the rows
-        if (poison)
-            for (size_t e = 0; e < nb; e++) {
-                HIP_TRY(hipMemsetAsync(h->d_rows + e * rf + z0, 0, zn * sizeof(float), nullptr));
-                HIP_TRY(hipMemsetAsync(h->d_rows + e * rf + m0, 0, (m1 - m0) * sizeof(float), nullptr));
-            }
-    }
-    if (p->obstacle == 2) {
-        // the free box where loadURDF puts it (snake.py:84, snake_gait_test.py:51): at rest, identity orientation,
-        // empty manifold
+    if (resident_waves(h->lds_bytes, device, &h->grid_waves)) return 1;
+    if (h->grid_waves <= 0 || h->grid_waves > n_envs) h->grid_waves = n_envs;
+    // Every buffer: slot, bytes, fill.  d_rows: one block of streamed constraint rows per RESIDENT WAVE (every
+    // step / substep kernel is launched with that many workgroups and strides over the environments): 2048 x 112 KB =
+    // 230 MB for 32 links, whatever n_envs is.  (16-link handles on the register-resident solve need them too: a substep
+    // whose contacts outgrow its 64 slots goes through the streamed-row solve in place, snk_device.hpp: substep())
+    const size_t ne = (size_t)n_envs, f = sizeof(float), nb = (size_t)h->grid_waves, R = (size_t)reset_row_floats(h->n);
+    if (ensure(h, &h->d_model, sizeof(snk::DevModel)) ||
+        ensure(h, &h->d_recs, ne * h->rec * f, 0) ||
+        ensure(h, &h->d_mu, ne * f) ||
+        ensure(h, &h->d_act, ne * h->D.act_dim * f, nans) ||
+        ensure(h, &h->d_obs, ne * h->D.obs_dim * f, nans) ||
+        ensure(h, &h->d_rew, ne * f, nans) ||
+        ensure(h, &h->d_tgt, ne * h->n * f, nans) ||
+        ensure(h, &h->d_h, ne * f, nans) ||
+        ensure(h, &h->d_done, ne) || ensure(h, &h->d_mask, ne) || ensure(h, &h->d_sub, ne * sizeof(int32_t)) ||
+        ensure(h, &h->d_info, ne * 2 * sizeof(int32_t)) || ensure(h, &h->d_order, ne * sizeof(int32_t)) ||
+        ensure(h, &h->d_rows, nb * rf * f, poison ? 0xFF : 0) ||
+        (p->obstacle == 2 && ensure(h, &h->d_box, ne * snk::kBoxFloats * f)) ||
+        ensure(h, &h->d_reset, ne * R * f) ||
+        ensure(h, &h->d_ovf, (snk::kOvfCounters + snk::kHistBins) * sizeof(unsigned long long), 0) ||
+        (p->contact_model == 1 && ensure(h, &h->d_mf, ne * 2 * h->n * snk::kMfFloats * f, 0)))      // hard reset: empty manifolds
+        return 1;
+    // what the kernels rely on being zero for good: the last three rows of every block of d_rows (the refill of a
+    // skipped friction pair) and the pad columns of the M^-1 block behind the rows
+    if (poison)
+        for (size_t e = 0; e < nb; e++) {
+            HIP_TRY(hipMemsetAsync(h->d_rows + e * rf + z0, 0, zn * f, nullptr));
+            HIP_TRY(hipMemsetAsync(h->d_rows + e * rf + m0, 0, (m1 - m0) * f, nullptr));
+        }
+    // the tables that start from values: ground friction 1 (plane.urdf lateral_friction [U]); the free box where loadURDF
+    // puts it (snake.py:84, snake_gait_test.py:51: at rest, identity orientation, empty manifold); the reset poses at the
+    // reference's defaults (snake.py:22-24: zeros, quaternion 0 0 0 1)
+    HIP_TRY(hipMemcpy(h->d_mu, std::vector<float>(ne, 1.0f).data(), ne * f, hipMemcpyHostToDevice));
+    if (h->d_box) {
         std::vector<float> b(ne * snk::kBoxFloats, 0.f);
         for (size_t e = 0; e < ne; e++) {
             float* x = &b[e * snk::kBoxFloats];
             for (int i = 0; i < 3; i++) x[i] = (float)p->obstacle_pos[i];
             x[6] = 1.0f;
         }
-        HIP_TRY(hipMalloc(&h->d_box, b.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(h->d_box, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->d_box, b.data(), b.size() * f, hipMemcpyHostToDevice));
     }
-    {
-        // the reset-pose table at the reference's defaults (snake.py:22-24): zeros, quaternion 0 0 0 1
-        const size_t R = (size_t)reset_row_floats(h->n);
-        std::vector<float> t(ne * R, 0.f);
-        for (size_t e = 0; e < ne; e++) t[e * R + 6] = 1.0f;
-        HIP_TRY(hipMalloc(&h->d_reset, t.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(h->d_reset, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&h->d_ovf, (snk::kOvfCounters + snk::kHistBins) * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(h->d_ovf, 0, (snk::kOvfCounters + snk::kHistBins) * sizeof(unsigned long long)));
-    if (p->contact_model == 1) {
-        const size_t bytes = ne * 2 * h->n * snk::kMfFloats * sizeof(float);
-        HIP_TRY(hipMalloc(&h->d_mf, bytes));
-        HIP_TRY(hipMemset(h->d_mf, 0, bytes));       // hard reset: empty manifolds
-    }
+    std::vector<float> t(ne * R, 0.f);
+    for (size_t e = 0; e < ne; e++) t[e * R + 6] = 1.0f;
+    HIP_TRY(hipMemcpy(h->d_reset, t.data(), t.size() * f, hipMemcpyHostToDevice));
     h->plan = getenv("SNK_NO_PLAN") == nullptr;
-    {
-        // scheduler state (snk_device.hpp: Sched)
-        const char* q = getenv("SNK_QUANTUM");       // substeps per slice; 0 = whole env-steps in launch order
-        int quantum = q ? atoi(q) : 1;
-        h->model_slot = quantum > 0 ? take_model_slot() : -1;
-        h->use_sched = h->model_slot >= 0;
-        if (h->use_sched)
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(snk::g_models), &h->D, sizeof(snk::DevModel),
-                                      (size_t)h->model_slot * sizeof(snk::DevModel), hipMemcpyHostToDevice));
-        snk::Sched& sc = h->sched;
-        sc.cap = 2u;                                  // power of two >= 2 n_envs: slot = ticket & (cap - 1) survives the
-        while (sc.cap < 2u * (uint32_t)n_envs) sc.cap <<= 1;      // wrap-around of the 32-bit tickets
-        sc.quantum = quantum;
-        {
-            const char* hy = getenv("SNK_HYST");      // experiments: see snk_device.hpp Sched::hyst
-            sc.hyst = hy ? atoi(hy) : 3;
-            if (sc.hyst < 1) sc.hyst = 1;
-        }
-        HIP_TRY(hipMalloc(&sc.head, sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&sc.tail, sizeof(uint32_t)));
-        HIP_TRY(hipMemset(sc.head, 0, sizeof(uint32_t)));
-        HIP_TRY(hipMemset(sc.tail, 0, sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&sc.waiting, snk::kBuckets * sizeof(int32_t)));
-        HIP_TRY(hipMemset(sc.waiting, 0, snk::kBuckets * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&sc.ent, (size_t)sc.cap * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(sc.ent, 0xFF, (size_t)sc.cap * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&sc.counter, ne * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&sc.finished, sizeof(int32_t)));
-        HIP_TRY(hipMemset(sc.finished, 0, sizeof(int32_t)));
-        HIP_TRY(hipHostMalloc(&h->h_alarm, 64 * sizeof(int32_t), hipHostMallocMapped));
-        memset(h->h_alarm, 0, 64 * sizeof(int32_t));
-        HIP_TRY(hipHostGetDevicePointer((void**)&sc.alarm, h->h_alarm, 0));
-#ifdef SNK_SCHED_DEBUG
-        HIP_TRY(hipMalloc(&sc.wstat, (size_t)h->grid_waves * 8 * sizeof(long long)));
-#endif
-    }
+    if (init_sched(h) || upload_model(h)) return 1;
     // hard reset (snake.py:88-95)
     rc = dispatch(h, [&](auto k) { return launch_reset(k, h, nullptr, nullptr, 1, nullptr); });
     if (rc || check_launch()) return 1;
     HIP_TRY(hipDeviceSynchronize());
     return 0;
 }
-}  // namespace
 
-int snk_create(const snk_params* p, int32_t n_envs, int32_t device, snk_handle** out) {
-    if (!p || !out) return fail("snk_create: null argument");
-    if (n_envs <= 0) return fail("snk_create: n_envs must be positive");
-    if (n_envs >= (1 << 24)) return fail("snk_create: n_envs must be below 2^24 (the step queue packs the env index into 24 bits)");
+// snk_create's refusals of a parameter set, before anything touches the device
+int validate_params(const snk_params* p) {
     if (p->struct_size != (uint32_t)sizeof(snk_params) || p->abi_version != SNK_ABI_VERSION) {
         static char msg[256];
         snprintf(msg, sizeof(msg), "snk_create: snk_params layout mismatch: the caller's struct is %u bytes, ABI version %u; this "
@@ -534,6 +601,15 @@ int snk_create(const snk_params* p, int32_t n_envs, int32_t device, snk_handle**
         return fail("snk_create: warm_start needs contact_model 1 (the impulses live in the persistent contact cache)");
     if (!(p->breaking_threshold > 0.0)) return fail("snk_create: breaking_threshold must be positive");
     if (p->term_index < 0 || p->term_index >= 3 * p->n_modules + 8) return fail("snk_create: term_index out of range");
+    return 0;
+}
+}  // namespace
+
+int snk_create(const snk_params* p, int32_t n_envs, int32_t device, snk_handle** out) {
+    if (!p || !out) return fail("snk_create: null argument");
+    if (n_envs <= 0) return fail("snk_create: n_envs must be positive");
+    if (n_envs >= (1 << 24)) return fail("snk_create: n_envs must be below 2^24 (the step queue packs the env index into 24 bits)");
+    if (validate_params(p)) return 1;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail("snk_create: no such HIP device");
@@ -553,11 +629,7 @@ int snk_destroy(snk_handle* h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    void* bufs[] = {h->d_model, h->d_recs, h->d_mu, h->d_act, h->d_obs, h->d_rew, h->d_done,
-                    h->d_sub, h->d_mask, h->d_tgt, h->d_info, h->d_h, h->d_order, h->d_rows, h->d_linkpos, h->d_trace, h->d_mf, h->d_ovf, h->d_box,
-                    h->d_reset, h->d_render,
-                    h->sched.head, h->sched.tail, h->sched.ent, h->sched.waiting, h->sched.counter, h->sched.finished};
-    for (void* b : bufs) (void)hipFree(b);
+    for (const snk_handle::Owned& o : h->owned) (void)hipFree(*o.slot);
     if (h->h_alarm) (void)hipHostFree(h->h_alarm);
     release_model_slot(h->model_slot);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -568,7 +640,7 @@ int snk_destroy(snk_handle* h) {
 #ifdef SNK_SCHED_DEBUG
 // per resident wave of the last step: ticks (100 MHz) waiting in the queue, ticks alive, slices, substeps
 int snk_sched_stats(snk_handle* h, long long* out, int32_t* n_waves) {
-    HIP_TRY(hipDeviceSynchronize());
+    if (enter(h, kIdle)) return 1;
     HIP_TRY(hipMemcpy(out, h->sched.wstat, (size_t)h->grid_waves * 8 * sizeof(long long), hipMemcpyDeviceToHost));
     *n_waves = h->grid_waves;
     return 0;
@@ -582,8 +654,7 @@ int32_t snk_record_floats(const snk_handle* h) { return h->rec; }
 
 int snk_reset(snk_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
     if (!h) return fail("snk_reset: null handle");
-    if (check_alarm(h)) return 1;
-    HIP_TRY(hipSetDevice(h->device));
+    if (enter(h, kDev | kAlive)) return 1;
     hipStream_t st = (hipStream_t)stream;
     if (dispatch(h, [&](auto k) { return launch_reset(k, h, mask_dev, obs_dev, 0, st); })) return 1;
     return check_launch();
@@ -593,7 +664,7 @@ int snk_step(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev, 
              int32_t* substeps_dev, int32_t vec_mode, void* stream) {
     if (!h) return fail("snk_step: null handle");
     if (!actions_dev || !obs_dev || !rew_dev || !done_dev) return fail("snk_step: null buffer");
-    if (check_alarm(h)) return 1;
+    if (enter(h, kDev | kAlive)) return 1;
     return timed_step(h, actions_dev, obs_dev, rew_dev, done_dev, substeps_dev, vec_mode, (hipStream_t)stream, 0);
 }
 
@@ -602,7 +673,7 @@ int snk_step_packed(snk_handle* h, float* actions_dev, float* packed_dev, int32_
     if (!h) return fail("snk_step_packed: null handle");
     if (!actions_dev || !packed_dev) return fail("snk_step_packed: null buffer");
     if (row_stride < h->D.obs_dim + 2) return fail("snk_step_packed: row_stride must be at least obs_dim + 2");
-    if (check_alarm(h)) return 1;
+    if (enter(h, kDev | kAlive)) return 1;
     return timed_step(h, actions_dev, packed_dev, nullptr, nullptr, substeps_dev, vec_mode, (hipStream_t)stream, row_stride);
 }
 
@@ -622,14 +693,14 @@ int snk_step_traced(snk_handle* h, float* actions_dev, float* obs_dev, float* re
     }
     if (reinterpret_cast<uintptr_t>(trace_dev) % 128 != 0)
         return fail("snk_step_traced: the trace buffer must be 128-byte aligned (a row is a whole number of 128-byte lines)");
-    if (check_alarm(h)) return 1;
+    if (enter(h, kDev | kAlive)) return 1;
     return timed_step(h, actions_dev, obs_dev, rew_dev, done_dev, substeps_dev, vec_mode, (hipStream_t)stream, 0, trace_dev,
                       trace_rows);
 }
 
 int snk_timing_enable(snk_handle* h, int32_t capacity) {
     if (!h) return fail("null handle");
-    HIP_TRY(hipSetDevice(h->device));
+    if (enter(h, kDev)) return 1;
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     h->ev.clear();
     h->ev_used = 0;
@@ -642,7 +713,7 @@ int snk_timing_enable(snk_handle* h, int32_t capacity) {
 }
 int snk_timing_read(snk_handle* h, double* mean_ms, int32_t* count) {
     if (!h) return fail("null handle");
-    HIP_TRY(hipSetDevice(h->device));
+    if (enter(h, kDev)) return 1;
     double sum = 0;
     for (int i = 0; i < h->ev_used; i++) {
         float ms = 0.f;
@@ -658,7 +729,7 @@ int snk_timing_read(snk_handle* h, double* mean_ms, int32_t* count) {
 
 int snk_reset_host(snk_handle* h, const uint8_t* mask, float* obs) {
     if (!h) return fail("snk_reset_host: null handle");
-    HIP_TRY(hipSetDevice(h->device));
+    if (enter(h, kDev | kAlive)) return 1;
     const size_t ne = (size_t)h->n_envs;
     if (mask) HIP_TRY(hipMemcpy(h->d_mask, mask, ne, hipMemcpyHostToDevice));
     if (obs) HIP_TRY(hipMemcpy(h->d_obs, obs, ne * h->D.obs_dim * sizeof(float), hipMemcpyHostToDevice));
@@ -669,23 +740,39 @@ int snk_reset_host(snk_handle* h, const uint8_t* mask, float* obs) {
     return 0;
 }
 
-int snk_step_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
-                  int32_t vec_mode) {
-    if (!h) return fail("snk_step_host: null handle");
-    if (!actions || !obs || !rew || !done) return fail("snk_step_host: null buffer");
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t ne = (size_t)h->n_envs;
-    HIP_TRY(hipMemcpy(h->d_act, actions, ne * h->D.act_dim * sizeof(float), hipMemcpyHostToDevice));
-    int rc = snk_step(h, h->d_act, h->d_obs, h->d_rew, h->d_done, h->d_sub, vec_mode, nullptr);
+// snk_step_host (trace null) and snk_step_traced_host: the alarm, the upload, the step, the device idle, the alarm again,
+// the downloads.  The callers have refused their null arguments.
+static int step_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps, float* trace,
+                     int32_t trace_rows, int32_t vec_mode) {
+    if (enter(h, kDev | kAlive)) return 1;
+    const size_t ne = (size_t)h->n_envs, na = ne * h->D.act_dim * sizeof(float);
+    const size_t tbytes = trace ? ne * (size_t)trace_rows * trace_row_floats(h->n) * sizeof(float) : 0;
+    if (trace) {
+        if (ensure(h, &h->d_trace, tbytes)) return 1;
+        // what the kernel does not write -- the padding of a row, the rows from an env's count on -- comes back as NaNs
+        // (all bits set), whatever the caller's buffer held
+        HIP_TRY(hipMemsetAsync(h->d_trace, 0xFF, tbytes, nullptr));
+    }
+    HIP_TRY(hipMemcpy(h->d_act, actions, na, hipMemcpyHostToDevice));
+    const int rc = trace ? snk_step_traced(h, h->d_act, h->d_obs, h->d_rew, h->d_done, h->d_sub, h->d_trace, trace_rows, vec_mode, nullptr)
+                         : snk_step(h, h->d_act, h->d_obs, h->d_rew, h->d_done, h->d_sub, vec_mode, nullptr);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (check_alarm(h)) return 1;
-    HIP_TRY(hipMemcpy(actions, h->d_act, ne * h->D.act_dim * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(actions, h->d_act, na, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(obs, h->d_obs, ne * h->D.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rew, h->d_rew, ne * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(done, h->d_done, ne, hipMemcpyDeviceToHost));
     if (substeps) HIP_TRY(hipMemcpy(substeps, h->d_sub, ne * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (trace) HIP_TRY(hipMemcpy(trace, h->d_trace, tbytes, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int snk_step_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
+                  int32_t vec_mode) {
+    if (!h) return fail("snk_step_host: null handle");
+    if (!actions || !obs || !rew || !done) return fail("snk_step_host: null buffer");
+    return step_host(h, actions, obs, rew, done, substeps, nullptr, 0, vec_mode);
 }
 
 int snk_step_traced_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
@@ -693,38 +780,13 @@ int snk_step_traced_host(snk_handle* h, float* actions, float* obs, float* rew, 
     if (!h) return fail("snk_step_traced_host: null handle");
     if (!actions || !obs || !rew || !done || !substeps || !trace) return fail("snk_step_traced_host: null buffer");
     if (trace_rows <= 0) return fail("snk_step_traced_host: trace_rows must be positive");
-    if (check_alarm(h)) return 1;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t ne = (size_t)h->n_envs;
-    const size_t tbytes = ne * (size_t)trace_rows * trace_row_floats(h->n) * sizeof(float);
-    if (!h->d_trace || h->d_trace_rows != trace_rows) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (h->d_trace) { (void)hipFree(h->d_trace); h->d_trace = nullptr; h->d_trace_rows = 0; }
-        HIP_TRY(hipMalloc(&h->d_trace, tbytes));
-        h->d_trace_rows = trace_rows;
-    }
-    // what the kernel does not write -- the padding of a row, the rows from an env's count on -- comes back as NaNs
-    // (all bits set), whatever the caller's buffer held
-    HIP_TRY(hipMemsetAsync(h->d_trace, 0xFF, tbytes, nullptr));
-    HIP_TRY(hipMemcpy(h->d_act, actions, ne * h->D.act_dim * sizeof(float), hipMemcpyHostToDevice));
-    int rc = snk_step_traced(h, h->d_act, h->d_obs, h->d_rew, h->d_done, h->d_sub, h->d_trace, trace_rows, vec_mode, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (check_alarm(h)) return 1;
-    HIP_TRY(hipMemcpy(actions, h->d_act, ne * h->D.act_dim * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(obs, h->d_obs, ne * h->D.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rew, h->d_rew, ne * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(done, h->d_done, ne, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(substeps, h->d_sub, ne * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(trace, h->d_trace, tbytes, hipMemcpyDeviceToHost));
-    return 0;
+    return step_host(h, actions, obs, rew, done, substeps, trace, trace_rows, vec_mode);
 }
 
 int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* info) {
     if (!h || !targets) return fail("snk_substep_host: null argument");
     if (k < 0) return fail("snk_substep_host: k < 0");
-    if (check_alarm(h)) return 1;
-    HIP_TRY(hipSetDevice(h->device));
+    if (enter(h, kDev | kAlive)) return 1;
     const size_t ne = (size_t)h->n_envs;
     HIP_TRY(hipMemcpy(h->d_tgt, targets, ne * h->n * sizeof(float), hipMemcpyHostToDevice));
     if (dispatch(h, [&](auto v) { return launch_substep(v, h, h->d_tgt, k, h->d_info, nullptr); }) || check_launch()) return 1;
@@ -735,52 +797,32 @@ int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* in
 
 int snk_get_state(snk_handle* h, float* state, float* aux) {
     if (!h) return fail("snk_get_state: null handle");
-    SNK_SYNC_ALIVE(h);
-    const size_t ne = (size_t)h->n_envs;
-    std::vector<float> recs(ne * h->rec);
-    HIP_TRY(hipMemcpy(recs.data(), h->d_recs, recs.size() * sizeof(float), hipMemcpyDeviceToHost));
-    const int sd = h->D.state_dim, n = h->n;
-    for (size_t e = 0; e < ne; e++) {
-        if (state) memcpy(state + e * sd, &recs[e * h->rec], sd * sizeof(float));
-        if (aux) memcpy(aux + e * (n + 2), &recs[e * h->rec + sd], (n + 2) * sizeof(float));
-    }
-    return 0;
+    if (enter(h, kState)) return 1;
+    const size_t sd = (size_t)h->D.state_dim;
+    return rows_get(records(h), {{0, sd, state}, {sd, (size_t)h->n + 2, aux}});
 }
-
 int snk_set_state(snk_handle* h, const float* state, const float* aux) {
     if (!h) return fail("snk_set_state: null handle");
-    SNK_SYNC_ALIVE(h);
-    const size_t ne = (size_t)h->n_envs;
-    std::vector<float> recs(ne * h->rec);
-    HIP_TRY(hipMemcpy(recs.data(), h->d_recs, recs.size() * sizeof(float), hipMemcpyDeviceToHost));
-    const int sd = h->D.state_dim, n = h->n;
-    for (size_t e = 0; e < ne; e++) {
-        if (state) memcpy(&recs[e * h->rec], state + e * sd, sd * sizeof(float));
-        if (aux) memcpy(&recs[e * h->rec + sd], aux + e * (n + 2), (n + 2) * sizeof(float));
-    }
-    HIP_TRY(hipMemcpy(h->d_recs, recs.data(), recs.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    if (enter(h, kState)) return 1;
+    const size_t sd = (size_t)h->D.state_dim;
+    return rows_set(records(h), {{0, sd, state}, {sd, (size_t)h->n + 2, aux}});
 }
 
 int32_t snk_reset_pose_floats(const snk_handle* h) {
     if (!h) { fail("snk_reset_pose_floats: null handle"); return 0; }
-    if (check_alarm(h)) return 0;
+    if (enter(h, kAlive)) return 0;
     return 7 + h->n;
 }
 
 int snk_get_reset_pose(snk_handle* h, float* pose) {
     if (!h || !pose) return fail("snk_get_reset_pose: null argument");
-    SNK_SYNC_ALIVE(h);
-    const size_t ne = (size_t)h->n_envs, R = (size_t)reset_row_floats(h->n), W = (size_t)(7 + h->n);
-    // (the padded rows to the caller's dense ones)
-    HIP_TRY(hipMemcpy2D(pose, W * sizeof(float), h->d_reset, R * sizeof(float), W * sizeof(float), ne, hipMemcpyDeviceToHost));
-    return 0;
+    if (enter(h, kState)) return 1;
+    return rows_get(reset_poses(h), {{0, (size_t)(7 + h->n), pose}});
 }
-
 int snk_set_reset_pose(snk_handle* h, const uint8_t* mask, const float* pose) {
     if (!h || !pose) return fail("snk_set_reset_pose: null argument");
-    SNK_SYNC_ALIVE(h);
-    const size_t ne = (size_t)h->n_envs, R = (size_t)reset_row_floats(h->n), W = (size_t)(7 + h->n);
+    if (enter(h, kState)) return 1;
+    const size_t ne = (size_t)h->n_envs, W = (size_t)(7 + h->n);
     // validated before anything is written: a refused call leaves the table as it was
     for (size_t e = 0; e < ne; e++) {
         if (mask && !mask[e]) continue;
@@ -800,89 +842,67 @@ int snk_set_reset_pose(snk_handle* h, const uint8_t* mask, const float* pose) {
             return fail(msg);
         }
     }
-    if (!mask) {
-        HIP_TRY(hipMemcpy2D(h->d_reset, R * sizeof(float), pose, W * sizeof(float), W * sizeof(float), ne, hipMemcpyHostToDevice));
-        return 0;
-    }
-    // masked: the table read back (the device is idle), the masked rows patched on the host, one copy back
-    std::vector<float> t(ne * R);
-    HIP_TRY(hipMemcpy(t.data(), h->d_reset, t.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < ne; e++)
-        if (mask[e]) memcpy(&t[e * R], pose + e * W, W * sizeof(float));
-    HIP_TRY(hipMemcpy(h->d_reset, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    return rows_set(reset_poses(h), {{0, W, pose}}, mask);
 }
 
 int snk_set_reset_pose_dev(snk_handle* h, const uint8_t* mask_dev, const float* pose_dev, void* stream) {
     if (!h || !pose_dev) return fail("snk_set_reset_pose_dev: null argument");
-    if (check_alarm(h)) return 1;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t total = (size_t)h->n_envs * (size_t)(7 + h->n);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (h->n == 16)
-        hipLaunchKernelGGL((snk::reset_pose_copy_kernel<16>), dim3(blocks), dim3(256), 0, st, h->d_reset, mask_dev, pose_dev, h->n_envs);
-    else
-        hipLaunchKernelGGL((snk::reset_pose_copy_kernel<32>), dim3(blocks), dim3(256), 0, st, h->d_reset, mask_dev, pose_dev, h->n_envs);
+    if (enter(h, kDev | kAlive)) return 1;
+    const unsigned blocks = (unsigned)(((size_t)h->n_envs * (size_t)(7 + h->n) + 255) / 256);
+    if (dispatch(h, [&](auto k) {
+            hipLaunchKernelGGL((snk::reset_pose_copy_kernel<decltype(k)::N>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                               h->d_reset, mask_dev, pose_dev, h->n_envs);
+            return 0;
+        })) return 1;
     return check_launch();
 }
 
 int32_t snk_manifold_floats(const snk_handle* h) { return (h && h->d_mf) ? 2 * h->n * 29 : 0; }
 
-// per cylinder: host layout manifold_to_host's; device layout [count, 3 pad, 4 x (a3, b.x, b.y, lambda)] = kMfFloats
+// per cylinder: host layout manifold_to_host's; device layout link_manifolds'
 int snk_get_manifold(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_get_manifold: null argument");
     if (!h->d_mf) return fail("snk_get_manifold: this handle has contact_model 0 (no contact cache)");
-    SNK_SYNC_ALIVE(h);
-    const size_t ncyl = (size_t)h->n_envs * 2 * h->n;
-    std::vector<float> dev(ncyl * snk::kMfFloats);
-    HIP_TRY(hipMemcpy(dev.data(), h->d_mf, dev.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < ncyl; c++) manifold_to_host(dev[snk::kMfFloats * c], &dev[snk::kMfFloats * c + 4], out + 29 * c);
+    if (enter(h, kState)) return 1;
+    const RowTable t = link_manifolds(h);
+    std::vector<float> dev(t.rows * t.stride);
+    if (rows_get(t, {{0, t.stride, dev.data()}})) return 1;
+    for (size_t c = 0; c < t.rows; c++) manifold_to_host(dev[t.stride * c], &dev[t.stride * c + 4], out + 29 * c);
     return 0;
 }
 int snk_set_manifold(snk_handle* h, const float* in) {
     if (!h || !in) return fail("snk_set_manifold: null argument");
     if (!h->d_mf) return fail("snk_set_manifold: this handle has contact_model 0 (no contact cache)");
-    SNK_SYNC_ALIVE(h);
-    const size_t ncyl = (size_t)h->n_envs * 2 * h->n;
-    std::vector<float> dev(ncyl * snk::kMfFloats, 0.f);
-    for (size_t c = 0; c < ncyl; c++) dev[snk::kMfFloats * c] = manifold_from_host(in + 29 * c, &dev[snk::kMfFloats * c + 4]);
-    HIP_TRY(hipMemcpy(h->d_mf, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    if (enter(h, kState)) return 1;
+    const RowTable t = link_manifolds(h);
+    std::vector<float> dev(t.rows * t.stride, 0.f);
+    for (size_t c = 0; c < t.rows; c++) dev[t.stride * c] = manifold_from_host(in + 29 * c, &dev[t.stride * c + 4]);
+    return rows_set(t, {{0, t.stride, dev.data()}});
 }
 
 int snk_get_box(snk_handle* h, float* state, float* manifold) {
     if (!h) return fail("snk_get_box: null handle");
     if (!h->d_box) return fail("snk_get_box: this handle has no free box (obstacle != 2)");
-    SNK_SYNC_ALIVE(h);
-    std::vector<float> b((size_t)h->n_envs * snk::kBoxFloats);
-    HIP_TRY(hipMemcpy(b.data(), h->d_box, b.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < (size_t)h->n_envs; e++) {
-        const float* x = &b[e * snk::kBoxFloats];
-        if (state) memcpy(state + 13 * e, x, 13 * sizeof(float));
-        if (manifold) manifold_to_host(x[13], x + 14, manifold + 29 * e);      // (state 13, count, points)
-    }
+    if (enter(h, kState)) return 1;
+    const size_t ne = (size_t)h->n_envs;
+    std::vector<float> m(manifold ? ne * kBoxMf : 0);      // (count, points) of every box
+    if (rows_get(boxes(h), {{0, kBoxState, state}, {kBoxState, kBoxMf, manifold ? m.data() : nullptr}})) return 1;
+    for (size_t e = 0; manifold && e < ne; e++) manifold_to_host(m[kBoxMf * e], &m[kBoxMf * e + 1], manifold + 29 * e);
     return 0;
 }
 int snk_set_box(snk_handle* h, const float* state, const float* manifold) {
     if (!h) return fail("snk_set_box: null handle");
     if (!h->d_box) return fail("snk_set_box: this handle has no free box (obstacle != 2)");
-    SNK_SYNC_ALIVE(h);
-    std::vector<float> b((size_t)h->n_envs * snk::kBoxFloats);
-    HIP_TRY(hipMemcpy(b.data(), h->d_box, b.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < (size_t)h->n_envs; e++) {
-        float* x = &b[e * snk::kBoxFloats];
-        if (state) memcpy(x, state + 13 * e, 13 * sizeof(float));
-        if (manifold) x[13] = manifold_from_host(manifold + 29 * e, x + 14);
-    }
-    HIP_TRY(hipMemcpy(h->d_box, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    if (enter(h, kState)) return 1;
+    const size_t ne = (size_t)h->n_envs;
+    std::vector<float> m(manifold ? ne * kBoxMf : 0);
+    for (size_t e = 0; manifold && e < ne; e++) m[kBoxMf * e] = manifold_from_host(manifold + 29 * e, &m[kBoxMf * e + 1]);
+    return rows_set(boxes(h), {{0, kBoxState, state}, {kBoxState, kBoxMf, manifold ? m.data() : nullptr}});
 }
 
 int snk_contact_overflow(snk_handle* h, uint64_t* out) {
     if (!h || !out) return fail("snk_contact_overflow: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
+    if (enter(h, kDev | kIdle)) return 1;
     unsigned long long v[3];
     HIP_TRY(hipMemcpy(v, h->d_ovf, sizeof(v), hipMemcpyDeviceToHost));
     for (int i = 0; i < 3; i++) out[i] = (uint64_t)v[i];
@@ -892,19 +912,13 @@ int snk_contact_overflow(snk_handle* h, uint64_t* out) {
 int32_t snk_contact_histogram_bins(void) { return snk::kHistBins; }
 int snk_contact_histogram_enable(snk_handle* h, int32_t on) {
     if (!h) return fail("snk_contact_histogram_enable: null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
+    if (enter(h, kDev | kIdle)) return 1;
     h->D.hist = on ? 1 : 0;
-    HIP_TRY(hipMemcpy(h->d_model, &h->D, sizeof(snk::DevModel), hipMemcpyHostToDevice));
-    if (h->model_slot >= 0)
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(snk::g_models), &h->D, sizeof(snk::DevModel),
-                                  (size_t)h->model_slot * sizeof(snk::DevModel), hipMemcpyHostToDevice));
-    return 0;
+    return upload_model(h);
 }
 int snk_contact_histogram(snk_handle* h, uint64_t* out, int32_t reset) {
     if (!h || !out) return fail("snk_contact_histogram: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
+    if (enter(h, kDev | kIdle)) return 1;
     std::vector<unsigned long long> v(snk::kHistBins);
     HIP_TRY(hipMemcpy(v.data(), h->d_ovf + snk::kOvfCounters, v.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int i = 0; i < snk::kHistBins; i++) out[i] = (uint64_t)v[i];
@@ -914,52 +928,43 @@ int snk_contact_histogram(snk_handle* h, uint64_t* out, int32_t reset) {
 
 int snk_get_obs(snk_handle* h, float* obs) {
     if (!h || !obs) return fail("snk_get_obs: null argument");
-    SNK_SYNC_ALIVE(h);
+    if (enter(h, kState)) return 1;
     return obs_pass(h, h->d_obs, nullptr, nullptr, obs, (size_t)h->n_envs * h->D.obs_dim * sizeof(float));
 }
-
 int snk_mean_height(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_mean_height: null argument");
-    SNK_SYNC_ALIVE(h);
+    if (enter(h, kState)) return 1;
     return obs_pass(h, nullptr, h->d_h, nullptr, out, (size_t)h->n_envs * sizeof(float));
 }
-
 int snk_link_positions(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_link_positions: null argument");
-    SNK_SYNC_ALIVE(h);
+    if (enter(h, kState)) return 1;
     const size_t bytes = (size_t)h->n_envs * 3 * (h->n + 1) * sizeof(float);
-    if (!h->d_linkpos) HIP_TRY(hipMalloc(&h->d_linkpos, bytes));
+    if (ensure(h, &h->d_linkpos, bytes)) return 1;
     return obs_pass(h, nullptr, nullptr, h->d_linkpos, out, bytes);
 }
 
 int snk_set_ground_friction(snk_handle* h, const float* mu) {
     if (!h || !mu) return fail("snk_set_ground_friction: null argument");
-    SNK_SYNC_ALIVE(h);
-    HIP_TRY(hipMemcpy(h->d_mu, mu, (size_t)h->n_envs * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    if (enter(h, kState)) return 1;
+    return rows_set(friction(h), {{0, 1, mu}});
 }
 
 int snk_joint3_reaction_fz(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_joint3_reaction_fz: null argument");
-    SNK_SYNC_ALIVE(h);
-    const size_t ne = (size_t)h->n_envs;
-    std::vector<float> recs(ne * h->rec);
-    HIP_TRY(hipMemcpy(recs.data(), h->d_recs, recs.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < ne; e++) out[e] = recs[e * h->rec + 15 + 3 * h->n];      // behind prev_x in the record
-    return 0;
+    if (enter(h, kState)) return 1;
+    return rows_get(records(h), {{rec_joint3_fz(h), 1, out}});
 }
 
 int snk_get_ground_friction(snk_handle* h, float* mu) {
     if (!h || !mu) return fail("snk_get_ground_friction: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(mu, h->d_mu, (size_t)h->n_envs * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    if (enter(h, kDev | kIdle)) return 1;
+    return rows_get(friction(h), {{0, 1, mu}});
 }
 
 int snk_debug_set_tickets(snk_handle* h, uint32_t base) {
     if (!h) return fail("snk_debug_set_tickets: null handle");
-    SNK_SYNC_ALIVE(h);
+    if (enter(h, kState)) return 1;
     HIP_TRY(hipMemcpy(h->sched.head, &base, sizeof(base), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->sched.tail, &base, sizeof(base), hipMemcpyHostToDevice));
     return 0;
@@ -992,12 +997,8 @@ int snk_debug_noncontact_order(int32_t n_modules, int32_t* out) {
 int snk_debug_reach_bound(const snk_params* p, float out[3]) {
     if (!p || !out) return fail("snk_debug_reach_bound: null argument");
     if (p->n_modules != 16 && p->n_modules != 32) return fail("snk_debug_reach_bound: n_modules must be 16 or 32");
-    // (the models are large: not on the stack)
-    std::vector<snk::HostModel> H(1);
-    std::vector<snk::DevModel> D(1);
-    snk::build_host_model(*p, H[0]);
-    snk::build_dev_model(*p, H[0], D[0]);
-    out[0] = D[0].reach_l; out[1] = D[0].reach_hb; out[2] = snk::kReachSlack;
+    const auto m = models_of(*p);
+    out[0] = m->D.reach_l; out[1] = m->D.reach_hb; out[2] = snk::kReachSlack;
     return 0;
 }
 
@@ -1042,10 +1043,8 @@ int snk_selftest(int32_t device) {
 int snk_params_derived(const snk_params* p, double* out) {
     if (!p || !out) return fail("snk_params_derived: null argument");
     if (p->n_modules != 16 && p->n_modules != 32) return fail("snk_params_derived: n_modules must be 16 or 32");
-    snk::HostModel H;
-    snk::DevModel D;
-    snk::build_host_model(*p, H);
-    snk::build_dev_model(*p, H, D);
+    const auto m = models_of(*p);
+    const snk::DevModel& D = m->D;
     out[0] = D.break_thr; out[1] = D.cyl_r; out[2] = D.cyl_hl; out[3] = D.cyl_zoff; out[4] = D.margin; out[5] = D.obs_thr;
     return 0;
 }

@@ -16,12 +16,6 @@
 namespace {
 
 int rfail(const std::string& msg) { return snk::api_fail(msg.c_str()); }
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return rfail(std::string(#expr) + ": " + hipGetErrorString(e__));                  \
-    } while (0)
 
 // what both forms refuse before they look at the handle's state; `who` = the entry point's name
 int check_shape(const char* who, const snk_handle* h, int32_t n_images, int32_t width, int32_t height, int32_t flags) {
@@ -59,13 +53,8 @@ int snk_render(snk_handle* h, const int32_t* env_ids_dev, int32_t n_images, cons
     snk::RenderView v;
     if (snk::render_view(h, false, &v)) return 1;
     const size_t pf = (size_t)snk::prim_stride(v.n), need = (size_t)n_images * (pf + snk::kCamFloats) * sizeof(float);
-    if (*v.scratch_bytes < need) {
-        // (hipFree waits for the device: a render still reading the old tables is complete before they go)
-        if (*v.scratch) { (void)hipFree(*v.scratch); *v.scratch = nullptr; *v.scratch_bytes = 0; }
-        HIP_TRY(hipMalloc(v.scratch, need));
-        *v.scratch_bytes = need;
-    }
-    float* prims = *v.scratch;
+    float* prims = snk::render_scratch(h, need);
+    if (!prims) return 1;
     float* cams = prims + (size_t)n_images * pf;
     hipStream_t st = (hipStream_t)stream;
     const int shared = shared_camera ? 1 : 0;

@@ -18,13 +18,13 @@ struct RenderView {
     const DevModel* d_model;      // the same on the device
     const float* d_recs;          // [n_envs][rec] state records
     const float* d_box;           // obstacle 2: [n_envs][kBoxFloats], else null
-    // scratch the handle owns for the renderer (snk_destroy frees it): the per-image primitive and camera tables
-    float** scratch;
-    size_t* scratch_bytes;
 };
 
 // Fills `v`; non-zero (snk_last_error set) for a poisoned handle.  `sync`: the device idle first, like the state accessors.
 __attribute__((visibility("hidden"))) int render_view(snk_handle* h, bool sync, RenderView* v);
+// The handle's scratch for the renderer -- the per-image primitive and camera tables -- of at least `need` bytes: the
+// handle owns, grows and frees it.  Null (snk_last_error set) when it cannot be had.
+__attribute__((visibility("hidden"))) float* render_scratch(snk_handle* h, size_t need);
 // snk_last_error's message, from the other object; returns 1
 __attribute__((visibility("hidden"))) int api_fail(const char* msg);
 
