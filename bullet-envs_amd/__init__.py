@@ -7,7 +7,7 @@ or through the top-level shim:  import bullet_envs_amd as pkg
 from ._lib import SnkParams, Snapshot, Stepper, default_params, load, LIB_PATH, trace_row_floats, trace_to_lists  # noqa: F401
 from .snake_env import (CloudpickleWrapper, Snake, SnakeGymEnv, SnakeVecEnv, SubprocVecEnv, VecEnv,  # noqa: F401
                         params_from_args)
-from .device_env import DeviceVecEnv, ShardedVecEnv  # noqa: F401
+from .device_env import DeviceVecEnv, DeviceWorld, ShardedVecEnv  # noqa: F401
 from .pybullet_client import BulletClient  # noqa: F401  (the reference's inner seam: Snake(pybullet_client, ...))
 from . import checkpoint  # noqa: F401  (simulator-state checkpoints)
 from .checkpoint import save_state, load_state  # noqa: F401

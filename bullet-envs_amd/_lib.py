@@ -74,6 +74,14 @@ SYMBOLS = {
     "snk_reset_host": (C.c_int, [_vp, _U8, _F]),
     "snk_step_host": (C.c_int, [_vp, _F, _F, _F, _U8, _I32, C.c_int32]),
     "snk_substep_host": (C.c_int, [_vp, _F, C.c_int32, _I32]),
+    "snk_substep": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "snk_observe": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "snk_link_state_rows": (C.c_int32, [_vp]),
+    "snk_link_states": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
+    "snk_link_states_host": (C.c_int, [_vp, _I32, C.c_int32, _F]),
+    "snk_link_inertial_offsets": (C.c_int, [C.POINTER(SnkParams), _D]),
+    "snk_copy_envs": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "snk_copy_envs_host": (C.c_int, [_vp, _I32, _I32, C.c_int32, C.c_int32]),
     "snk_get_state": (C.c_int, [_vp, _F, _F]),
     "snk_set_state": (C.c_int, [_vp, _F, _F]),
     "snk_manifold_floats": (C.c_int32, [_vp]),
@@ -107,6 +115,8 @@ SYMBOLS = {
     "snk_last_error": (C.c_char_p, []),
 }
 RENDER_SHADOW = 1      # SNK_RENDER_SHADOW
+COPY_RESET_POSE = 1    # SNK_COPY_RESET_POSE
+LINK_STATE_FLOATS = 16  # floats per row of snk_link_states: [COM 3 | quat xyzw 4 | link origin 3 | COM velocity 3 | omega 3]
 
 #: the camera behind render() / getCameraImage when the caller gives no matrices [U]: the reference calls
 #: resetDebugVisualizerCamera(1.5, -30, -90, [1.28, 0, 0]) right before its getCameraImage (snake.py:322-327) -- the reading
@@ -196,6 +206,15 @@ def reach_bound(params=None, **over):
 
 def fptr(a):
     return a.ctypes.data_as(_F)
+
+
+def link_inertial_offsets(n_modules=16, **params):
+    """snk_link_inertial_offsets: [3n + 2, 3] float64, every link's COM in its own link frame (PyBullet's
+    localInertialFramePosition; row r = Bullet link r - 1).  Host arithmetic only: no handle, no device."""
+    p = default_params(n_modules=int(n_modules), **params)
+    out = np.zeros((3 * int(n_modules) + 2, 3), np.float64)
+    check(load().snk_link_inertial_offsets(C.byref(p), out.ctypes.data_as(_D)), "snk_link_inertial_offsets")
+    return out
 
 
 def view_matrix_ypr(target, distance, yaw, pitch, roll=0.0, up_axis=2):
@@ -554,6 +573,60 @@ class Stepper:
 
     def reset_device(self, mask_ptr=0, obs_ptr=0, stream=0):
         check(self.lib.snk_reset(self.h, mask_ptr or None, obs_ptr or None, stream or None), "snk_reset")
+
+    # ---- the tensor seam: substeps, read-outs, link states and forks on device pointers (0: none) ----
+    def substep_device(self, targets_ptr, k=1, active_ptr=0, info_ptr=0, stream=0):
+        """snk_substep: k physics substeps towards targets [n_envs, n] f32 for the envs whose byte of active [n_envs] u8
+        is non-zero (0: all); info [n_envs, 2] i32.  Asynchronous on `stream`."""
+        check(self.lib.snk_substep(self.h, targets_ptr or None, int(k), active_ptr or None, info_ptr or None, stream or None),
+              "snk_substep")
+
+    def observe_device(self, obs_ptr=0, height_ptr=0, linkpos_ptr=0, stream=0):
+        """snk_observe: observation [n_envs, obs_dim], mean height [n_envs], link positions [n_envs, 3(n+1)], each f32
+        or 0.  Asynchronous on `stream`."""
+        check(self.lib.snk_observe(self.h, obs_ptr or None, height_ptr or None, linkpos_ptr or None, stream or None),
+              "snk_observe")
+
+    @property
+    def link_rows(self):
+        """3n + 2: rows per env of link_states (row r = Bullet link r - 1)."""
+        return int(self.lib.snk_link_state_rows(self.h))
+
+    def link_states_device(self, ids_ptr, n_rows, out_ptr, stream=0):
+        """snk_link_states: out [n_rows, 3n + 2, 16] f32 for the envs ids [n_rows] i32 (0: envs 0 .. n_rows - 1)."""
+        check(self.lib.snk_link_states(self.h, ids_ptr or None, int(n_rows), out_ptr or None, stream or None),
+              "snk_link_states")
+
+    def copy_envs_device(self, src_ptr, dst_ptr, n_pairs, reset_pose=False, stream=0):
+        """snk_copy_envs: env dst[i] becomes env src[i] (ids [n_pairs] i32 on the device; nothing validated)."""
+        check(self.lib.snk_copy_envs(self.h, src_ptr or None, dst_ptr or None, int(n_pairs),
+                                     COPY_RESET_POSE if reset_pose else 0, stream or None), "snk_copy_envs")
+
+    def link_states(self, env_ids=None):
+        """snk_link_states_host: [k, 3n + 2, 16] float32 of the envs `env_ids` (None: all; ids may repeat, any order):
+        per link [COM 3 | quaternion xyzw 4 | link-frame origin 3 | COM velocity 3 | angular velocity 3], world frame."""
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        k = self.n_envs if ids is None else len(ids)
+        out = np.zeros((max(k, 1), 3 * self.n + 2, LINK_STATE_FLOATS), np.float32)
+        check(self.lib.snk_link_states_host(self.h, ids.ctypes.data_as(_I32) if ids is not None else None, k, fptr(out)),
+              "snk_link_states_host")
+        return out
+
+    def copy_envs(self, src, dst, reset_pose=False):
+        """snk_copy_envs_host: env dst[i] becomes env src[i] in everything a Snapshot holds (the reset pose only with
+        reset_pose=True).  Refused with the index, nothing written: an id outside the handle, a repeated dst, a dst
+        that is also a src."""
+        s = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+        d = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1)
+        if len(s) != len(d):
+            raise ValueError("src and dst must name as many envs each, got %d and %d" % (len(s), len(d)))
+        check(self.lib.snk_copy_envs_host(self.h, s.ctypes.data_as(_I32), d.ctypes.data_as(_I32), len(s),
+                                          COPY_RESET_POSE if reset_pose else 0), "snk_copy_envs_host")
+
+    @staticmethod
+    def link_inertial_offsets(n_modules=16, **params):
+        """snk_link_inertial_offsets (module function link_inertial_offsets)."""
+        return link_inertial_offsets(n_modules, **params)
 
     # ---- the ray caster (snk_render / snk_render_host) ----
     def render(self, view, proj, width, height, env_ids=None, shadow=False, depth=True, seg=True):

@@ -14,6 +14,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "snk.h")
 
 
 RENDER_OBJ = os.path.join(HERE, "snk_render.o")
+WORLD_OBJ = os.path.join(HERE, "snk_world.o")
 
 
 def sources():
@@ -49,6 +50,13 @@ def _render_command(obj, defines=(), extra=()):
         ["-D" + d for d in defines] + list(extra)
 
 
+def _world_command(obj, defines=(), extra=()):
+    """The translation unit of the link states and the env fork (csrc/snk_world.hip): an object of its own, like the
+    renderer's, linked in by the library's command."""
+    return [_hipcc()] + FLAGS + ["-c", "-fPIC", os.path.join(CSRC, "snk_world.hip"), "-o", obj] + \
+        ["-D" + d for d in defines] + list(extra)
+
+
 def _stamp(out):
     return out + ".cmd"
 
@@ -57,6 +65,10 @@ def _render_stamp(out):
     """libsnk.so.cmd stays the command of the step kernels' translation unit alone, flags and source (the pinned bits of
     tests/test_gpu_bits.py are keyed by it and by the toolchain); the renderer's object has a stamp of its own."""
     return out + ".render.cmd"
+
+
+def _world_stamp(out):
+    return out + ".world.cmd"
 
 
 def toolchain_text():
@@ -90,7 +102,10 @@ def needs_build(cmd=None):
             if f.read() != _stamp_text(cmd if cmd is not None else _command(LIB)):
                 return True
         with open(_render_stamp(LIB)) as f:
-            return f.read() != _stamp_text(_render_command(RENDER_OBJ))
+            if f.read() != _stamp_text(_render_command(RENDER_OBJ)):
+                return True
+        with open(_world_stamp(LIB)) as f:
+            return f.read() != _stamp_text(_world_command(WORLD_OBJ))
     except OSError:
         return True
 
@@ -111,9 +126,11 @@ def build(force=False, verbose=False, defines=(), out=None):
                 f.write(toolchain_text())
         return LIB
     obj = RENDER_OBJ if out is None else os.path.splitext(target)[0] + "_render.o"
+    wobj = WORLD_OBJ if out is None else os.path.splitext(target)[0] + "_world.o"
     rcmd = _render_command(obj, defines, extra)
-    run = [cmd[0], obj] + list(cmd[1:])      # (the object first: hipcc reads every input behind a .hip file as HIP source)
-    for r in (rcmd, run):
+    wcmd = _world_command(wobj, defines, extra)
+    run = [cmd[0], obj, wobj] + list(cmd[1:])      # (the objects first: hipcc reads every input behind a .hip file as HIP source)
+    for r in (rcmd, wcmd, run):
         if verbose:
             r = [r[0], "-Rpass-analysis=kernel-resource-usage"] + r[1:]
             print(" ".join(r))
@@ -122,6 +139,8 @@ def build(force=False, verbose=False, defines=(), out=None):
         f.write(_stamp_text(cmd))
     with open(_render_stamp(target), "w") as f:
         f.write(_stamp_text(rcmd))
+    with open(_world_stamp(target), "w") as f:
+        f.write(_stamp_text(wcmd))
     with open(target + ".toolchain", "w") as f:
         f.write(toolchain_text())
     return target

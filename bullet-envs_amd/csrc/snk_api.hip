@@ -62,6 +62,7 @@ struct snk_handle {
     float* d_box = nullptr;       // obstacle 2: the free box of every env, [n_envs][kBoxFloats] (state 13, count, manifold 24)
     float* d_reset = nullptr;     // the reset-pose table, [n_envs][reset_row_floats(n)] = [pos 3 | quat xyzw 4 | q n | padding]
     int32_t* d_order = nullptr;
+    float* d_links = nullptr;     // the link table of the unmerged tree (snk_model.hpp: build_link_table), for snk_link_states
     float* d_render = nullptr;    // snk_render's per-image primitive and camera tables (snk::render_scratch), made on first use
     bool plan = true;
     // in-launch scheduler of env_step_sched_kernel (snk_device.hpp): rings, counters, the host-mapped alarm word
@@ -156,9 +157,9 @@ int launch_step(K, snk_handle* h, float* act, float* obs, float* rew, uint8_t* d
     return 0;
 }
 template <class K>
-int launch_substep(K, snk_handle* h, const float* tgt, int k, int32_t* info, hipStream_t st) {
+int launch_substep(K, snk_handle* h, const float* tgt, int k, int32_t* info, const uint8_t* active, hipStream_t st) {
     hipLaunchKernelGGL((snk::substep_kernel<K::N, K::V2, K::RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st,
-                       h->d_model, h->d_recs, h->d_mu, tgt, k, info, h->n_envs, h->d_rows, h->d_mf, h->d_ovf, h->d_box);
+                       h->d_model, h->d_recs, h->d_mu, tgt, k, info, h->n_envs, h->d_rows, h->d_mf, h->d_ovf, h->d_box, active);
     return 0;
 }
 template <class K>
@@ -232,16 +233,17 @@ int check_alarm(const snk_handle* h) {
 // The code's copy of the paragraph at snk_debug_raise_alarm in include/snk.h:
 //   D I A  snk_get_state  snk_set_state  snk_get_manifold  snk_set_manifold  snk_get_box  snk_set_box  snk_get_obs
 //          snk_mean_height  snk_link_positions  snk_joint3_reaction_fz  snk_set_ground_friction  snk_get_reset_pose
-//          snk_set_reset_pose  snk_debug_set_tickets  snk_render_host
+//          snk_set_reset_pose  snk_debug_set_tickets  snk_render_host  snk_link_states_host  snk_copy_envs_host
 //   D . A  snk_reset  snk_step  snk_step_packed  snk_step_traced  snk_reset_host  snk_step_host  snk_step_traced_host
-//          snk_substep_host  snk_set_reset_pose_dev  snk_render
+//          snk_substep_host  snk_set_reset_pose_dev  snk_render  snk_substep  snk_observe  snk_link_states  snk_copy_envs
 //   . . A  snk_reset_pose_floats (returns 0)
 //   D I .  snk_get_ground_friction  snk_contact_overflow  snk_contact_histogram  snk_contact_histogram_enable
 //          snk_destroy (the two calls bare: errors ignored, snk_last_error untouched)
 //   D . .  snk_timing_enable  snk_timing_read
 //   . I .  snk_sched_stats (SNK_SCHED_DEBUG builds)
 //   . . .  snk_num_envs  snk_obs_dim  snk_act_dim  snk_state_dim  snk_record_floats  snk_trace_row_floats
-//          snk_manifold_floats  snk_model_describe  snk_debug_raise_alarm; and the calls without a handle
+//          snk_manifold_floats  snk_model_describe  snk_debug_raise_alarm  snk_link_state_rows; and the calls without a
+//          handle
 enum : unsigned { kDev = 1, kIdle = 2, kAlive = 4, kState = kDev | kIdle | kAlive };
 int enter(const snk_handle* h, unsigned what) {
     if (what & kDev) HIP_TRY(hipSetDevice(h->device));
@@ -273,14 +275,18 @@ int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done,
     return check_launch();
 }
 
-// one obs_kernel pass over h's records (the device idle, the handle alive), and its one output copied to out
-int obs_pass(snk_handle* h, float* obs, float* height, float* linkpos, void* out, size_t bytes) {
+// one obs_kernel pass over h's records, enqueued on st (snk_observe; the host read-outs below)
+int launch_obs(snk_handle* h, float* obs, float* height, float* linkpos, hipStream_t st) {
     const int rc = dispatch(h, [&](auto k) {
         hipLaunchKernelGGL((snk::obs_kernel<decltype(k)::N, decltype(k)::V2>), dim3(h->n_envs), dim3(64), h->lds_bytes,
-                           nullptr, h->d_model, h->d_recs, obs, height, linkpos, h->n_envs);
+                           st, h->d_model, h->d_recs, obs, height, linkpos, h->n_envs);
         return 0;
     });
-    if (rc || check_launch()) return 1;
+    return (rc || check_launch()) ? 1 : 0;
+}
+// that pass (the device idle, the handle alive), and its one output copied to out
+int obs_pass(snk_handle* h, float* obs, float* height, float* linkpos, void* out, size_t bytes) {
+    if (launch_obs(h, obs, height, linkpos, nullptr)) return 1;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, obs ? obs : (height ? height : linkpos), bytes, hipMemcpyDeviceToHost));
     return 0;
@@ -382,13 +388,22 @@ std::unique_ptr<Models> models_of(const snk_params& p) {
 
 }  // namespace
 
-// the renderer's seam (snk_render_view.hpp): its translation unit sees this much of a handle, and reports through g_err
+// the seam of the other objects (snk_render_view.hpp): their translation units see this much of a handle, and report
+// through g_err
 namespace snk {
 int api_fail(const char* msg) { return fail(msg); }
 int render_view(snk_handle* h, bool sync, RenderView* v) {
     if (enter(h, sync ? kState : (kDev | kAlive))) return 1;
     v->device = h->device; v->n = h->n; v->n_envs = h->n_envs; v->v2 = h->v2;
     v->D = &h->D; v->d_model = h->d_model; v->d_recs = h->d_recs; v->d_box = h->d_box;
+    return 0;
+}
+int world_view(snk_handle* h, bool sync, WorldView* v) {
+    if (render_view(h, sync, v)) return 1;
+    v->d_links = h->d_links;
+    const size_t ne = (size_t)h->n_envs;
+    const RowTable t[WorldView::kTables] = {records(h), link_manifolds(h), boxes(h), friction(h), reset_poses(h)};
+    for (int i = 0; i < WorldView::kTables; i++) v->tables[i] = {t[i].d, t[i].stride * (t[i].rows / ne)};
     return 0;
 }
 float* render_scratch(snk_handle* h, size_t need) { return ensure(h, &h->d_render, need) ? nullptr : h->d_render; }
@@ -535,6 +550,7 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
         ensure(h, &h->d_rows, nb * rf * f, poison ? 0xFF : 0) ||
         (p->obstacle == 2 && ensure(h, &h->d_box, ne * snk::kBoxFloats * f)) ||
         ensure(h, &h->d_reset, ne * R * f) ||
+        ensure(h, &h->d_links, (size_t)snk::link_rows(h->n) * snk::kLinkFloats * f) ||
         ensure(h, &h->d_ovf, (snk::kOvfCounters + snk::kHistBins) * sizeof(unsigned long long), 0) ||
         (p->contact_model == 1 && ensure(h, &h->d_mf, ne * 2 * h->n * snk::kMfFloats * f, 0)))      // hard reset: empty manifolds
         return 1;
@@ -561,6 +577,9 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     std::vector<float> t(ne * R, 0.f);
     for (size_t e = 0; e < ne; e++) t[e * R + 6] = 1.0f;
     HIP_TRY(hipMemcpy(h->d_reset, t.data(), t.size() * f, hipMemcpyHostToDevice));
+    std::vector<float> lt((size_t)snk::link_rows(h->n) * snk::kLinkFloats);
+    snk::build_link_table(h->H, lt.data());
+    HIP_TRY(hipMemcpy(h->d_links, lt.data(), lt.size() * f, hipMemcpyHostToDevice));
     h->plan = getenv("SNK_NO_PLAN") == nullptr;
     if (init_sched(h) || upload_model(h)) return 1;
     // hard reset (snake.py:88-95)
@@ -789,10 +808,26 @@ int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* in
     if (enter(h, kDev | kAlive)) return 1;
     const size_t ne = (size_t)h->n_envs;
     HIP_TRY(hipMemcpy(h->d_tgt, targets, ne * h->n * sizeof(float), hipMemcpyHostToDevice));
-    if (dispatch(h, [&](auto v) { return launch_substep(v, h, h->d_tgt, k, h->d_info, nullptr); }) || check_launch()) return 1;
+    if (dispatch(h, [&](auto v) { return launch_substep(v, h, h->d_tgt, k, h->d_info, nullptr, nullptr); }) || check_launch()) return 1;
     HIP_TRY(hipDeviceSynchronize());
     if (info) HIP_TRY(hipMemcpy(info, h->d_info, ne * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return 0;
+}
+
+int snk_substep(snk_handle* h, const float* targets_dev, int32_t k, const uint8_t* active_dev, int32_t* info_dev, void* stream) {
+    if (!h || !targets_dev) return fail("snk_substep: null argument");
+    if (k < 0) return fail("snk_substep: k < 0");
+    if (enter(h, kDev | kAlive)) return 1;
+    if (dispatch(h, [&](auto v) { return launch_substep(v, h, targets_dev, k, info_dev, active_dev, (hipStream_t)stream); }))
+        return 1;
+    return check_launch();
+}
+
+int snk_observe(snk_handle* h, float* obs_dev, float* height_dev, float* linkpos_dev, void* stream) {
+    if (!h) return fail("snk_observe: null handle");
+    if (!obs_dev && !height_dev && !linkpos_dev) return fail("snk_observe: obs_dev, height_dev and linkpos_dev are all null");
+    if (enter(h, kDev | kAlive)) return 1;
+    return launch_obs(h, obs_dev, height_dev, linkpos_dev, (hipStream_t)stream);
 }
 
 int snk_get_state(snk_handle* h, float* state, float* aux) {

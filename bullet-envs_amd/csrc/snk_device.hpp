@@ -140,13 +140,17 @@ __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restri
                                                      const float* __restrict__ targets, int k,
                                                      int32_t* __restrict__ info, int n_envs, float* __restrict__ rows_all,
                                                      float* __restrict__ mf_all, unsigned long long* __restrict__ ovf,
-                                                     float* __restrict__ box_all) {
+                                                     float* __restrict__ box_all,
+                                                     const uint8_t* __restrict__ active) {
     extern __shared__ float4 smem_raw[];
     using LT = LdsFor<N, V2, RULES>;
     LT& L = *reinterpret_cast<LT*>(smem_raw);
     const DevModel& M = *Mp;
     const int lane = threadIdx.x;
     for (int env = blockIdx.x; env < n_envs; env += gridDim.x) {      // (the block of streamed rows belongs to the workgroup)
+    // snk_substep's mask (null: every env): an env whose byte is 0 is neither loaded nor stored -- record, contact cache,
+    // free box and info row keep their bits
+    if (active && !active[env]) continue;
     if (M.poison) { L.poison(lane); lds_sync(); }
     load_env(L, recs, mf_all, box_all, env, lane);
     if (lane < N) L.targets[lane] = targets[(size_t)env * N + lane];

@@ -24,6 +24,7 @@ constexpr int kMaxN = 32;
 constexpr int kMaxB = kMaxN + 1;
 constexpr int kMaxCyl = 2 * kMaxN;
 constexpr int kMaxSub = 4;
+constexpr int kMaxLinks = 3 * kMaxN + 2;   // the unmerged URDF tree: root, base, and per module INPUT_IF, COLLAR, OUTPUT_BODY
 
 // Flat, float, uniform data read by every wave (scalar loads).
 struct DevModel {
@@ -199,6 +200,12 @@ struct HostModel {
     int cyl_body[kMaxCyl];
     double cyl_c[kMaxCyl][3], cyl_R[kMaxCyl][9];
     double zbase[3], hbase[3], m_root;
+    // The links of the unmerged tree, in Bullet's order: row r = Bullet link r - 1 (row 0 = kdl_dummy_root, Bullet's base;
+    // row 1 = `base`; rows 3k - 1, 3k, 3k + 1 = INPUT_IF_k, COLLAR_k, OUTPUT_BODY_k).  Per link: its composite body, its
+    // frame in that body (rotation link -> body, origin), and its COM in its OWN frame (PyBullet's localInertialFramePosition),
+    // taken back out of the sub-link offsets merged above.
+    int link_body[kMaxLinks];
+    double link_R[kMaxLinks][9], link_o[kMaxLinks][3], link_c[kMaxLinks][3];
 };
 
 inline void build_host_model(const snk_params& P, HostModel& H) {
@@ -284,6 +291,31 @@ inline void build_host_model(const snk_params& P, HostModel& H) {
             memcpy(H.Rfix[b], Rz, sizeof(Rz));
         }
     }
+    // links of the unmerged tree: sub-link s of body b is link row r, with frame (R, o) in the body
+    {
+        auto link = [&](int r, int b, int s, const double* R, const double* o) {
+            H.link_body[r] = b;
+            memcpy(H.link_R[r], R, 9 * sizeof(double));
+            for (int i = 0; i < 3; i++) H.link_o[r][i] = o[i];
+            for (int i = 0; i < 3; i++) {      // R^T (COM in the body - origin)
+                double t = 0;
+                for (int k = 0; k < 3; k++) t += R[3 * k + i] * (H.sub[b][s].c[k] - o[k]);
+                H.link_c[r][i] = t;
+            }
+        };
+        const double o0[3] = {0, 0, 0}, ob[3] = {0, 0, 0.026}, oin[3] = {0, 0, z_out};
+        link(0, 0, 0, Rid, o0);                                         // kdl_dummy_root
+        link(1, 0, 1, Rbase, ob);                                       // base (urdf:11)
+        link(2, 0, 2, Rbase, ob);                                       // INPUT_IF_1: on the base link's frame
+        link(3, 0, 3, Rbase, ob);                                       // COLLAR_1: on INPUT_IF_1's frame
+        for (int b = 1; b <= n; b++) {
+            link(3 * b + 1, b, 0, Rid, o0);                             // OUTPUT_BODY_b
+            if (b < n) {
+                link(3 * b + 2, b, 1, Rz, oin);                         // INPUT_IF_{b+1} (urdf:877)
+                link(3 * b + 3, b, 2, Rz, oin);                         // COLLAR_{b+1}
+            }
+        }
+    }
     // cylinders
     for (int c = 0; c < 2 * n; c++) {
         int b = (c + 1) / 2;
@@ -300,6 +332,21 @@ inline void build_host_model(const snk_params& P, HostModel& H) {
             H.cyl_c[c][0] = 0; H.cyl_c[c][1] = 0; H.cyl_c[c][2] = z_out + z_cyl;
             memcpy(H.cyl_R[c], Rz, sizeof(Rz));
         }
+    }
+}
+
+// The link table of the device (snk_world.hpp: link_state_kernel), kept out of DevModel, whose layout the step kernels
+// are compiled against: one row of kLinkFloats per link of the unmerged tree,
+//   [rotation link -> body 9, row-major | origin in the body 3 | COM in the link's own frame 3 | composite body (int bits)].
+constexpr int kLinkFloats = 16;
+inline int link_rows(int n) { return 3 * n + 2; }
+inline void build_link_table(const HostModel& H, float* out /* [link_rows(n)][kLinkFloats] */) {
+    for (int r = 0; r < link_rows(H.n); r++) {
+        float* o = out + (size_t)r * kLinkFloats;
+        for (int i = 0; i < 9; i++) o[i] = (float)H.link_R[r][i];
+        for (int i = 0; i < 3; i++) { o[9 + i] = (float)H.link_o[r][i]; o[12 + i] = (float)H.link_c[r][i]; }
+        const int32_t b = H.link_body[r];
+        memcpy(o + 15, &b, sizeof(b));
     }
 }
 

@@ -1,0 +1,186 @@
+// snk_world.hip -- link states and the env fork behind snk_link_states / snk_copy_envs and their host forms, and the
+// host-only link read-outs (include/snk.h).  A translation unit and a code object of its own, like snk_render.hip:
+// build.py compiles it to an object and links it into libsnk.so next to snk_api.hip, whose kernels it does not touch.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/snk.h"
+#include "snk_render_view.hpp"
+#include "snk_world.hpp"
+
+namespace {
+
+int wfail(const std::string& msg) { return snk::api_fail(msg.c_str()); }
+
+int launched(const char* who) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return wfail(std::string(who) + ": kernel launch: " + hipGetErrorString(e));
+    return 0;
+}
+
+template <int N, bool V2>
+void launch_links(const snk::WorldView& v, const int32_t* ids, int n_rows, float* out, hipStream_t st) {
+    const int blocks = n_rows < 65536 ? n_rows : 65536;
+    hipLaunchKernelGGL((snk::link_state_kernel<N, V2>), dim3(blocks), dim3(64), 0, st, v.d_model, v.d_recs, v.d_links, ids, out,
+                       n_rows, v.n_envs);
+}
+
+// a host id list against the handle: the first index whose id is outside 0 .. n_envs - 1, or -1
+int bad_id(const int32_t* ids, int n, int n_envs) {
+    for (int k = 0; k < n; k++)
+        if (ids[k] < 0 || ids[k] >= n_envs) return k;
+    return -1;
+}
+
+// device copies of host arrays for the host forms, freed on every way out
+struct Staged {
+    std::vector<void*> p;
+    ~Staged() { for (void* q : p) (void)hipFree(q); }
+    void* up(const void* host, size_t bytes) {      // null when it cannot be had
+        void* d = nullptr;
+        if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
+        p.push_back(d);
+        if (host && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return d;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int32_t snk_link_state_rows(const snk_handle* h) {
+    if (!h) { wfail("snk_link_state_rows: null handle"); return 0; }
+    return snk_obs_dim(h) - 6;      // obs_dim = 3n + 8 (snake.py:163-164); the tree has 3n + 2 links
+}
+
+int snk_link_states(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float* out_dev, void* stream) {
+    if (!h) return wfail("snk_link_states: null handle (h)");
+    if (n_rows < 1) return wfail("snk_link_states: n_rows must be at least 1");
+    if (!out_dev) return wfail("snk_link_states: null out_dev");
+    if (reinterpret_cast<uintptr_t>(out_dev) % 16 != 0)
+        return wfail("snk_link_states: out_dev must be 16-byte aligned (the rows leave as 16-byte stores)");
+    snk::WorldView v;
+    if (snk::world_view(h, false, &v)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (v.n == 16 && v.v2) launch_links<16, true>(v, env_ids_dev, n_rows, out_dev, st);
+    else if (v.n == 16) launch_links<16, false>(v, env_ids_dev, n_rows, out_dev, st);
+    else if (v.n == 32) launch_links<32, false>(v, env_ids_dev, n_rows, out_dev, st);
+    else return wfail("snk_link_states: unsupported n_modules (16 or 32)");
+    return launched("snk_link_states");
+}
+
+int snk_link_states_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* out) {
+    if (!h) return wfail("snk_link_states_host: null handle (h)");
+    if (n_rows < 1) return wfail("snk_link_states_host: n_rows must be at least 1");
+    if (!out) return wfail("snk_link_states_host: null out");
+    snk::WorldView v;
+    if (snk::world_view(h, true, &v)) return 1;
+    char msg[160];
+    const int bad = env_ids ? bad_id(env_ids, n_rows, v.n_envs) : -1;
+    if (bad >= 0) {
+        snprintf(msg, sizeof(msg), "snk_link_states_host: env_ids[%d] = %d is outside 0 .. %d", bad, (int)env_ids[bad], v.n_envs - 1);
+        return wfail(msg);
+    }
+    if (!env_ids && n_rows > v.n_envs) {
+        snprintf(msg, sizeof(msg), "snk_link_states_host: n_rows %d without env_ids is more than the handle's %d envs", (int)n_rows,
+                 v.n_envs);
+        return wfail(msg);
+    }
+    const size_t bytes = (size_t)n_rows * snk::link_rows(v.n) * snk::kLinkStateFloats * sizeof(float);
+    Staged s;
+    int32_t* d_ids = env_ids ? static_cast<int32_t*>(s.up(env_ids, (size_t)n_rows * sizeof(int32_t))) : nullptr;
+    float* d_out = static_cast<float*>(s.up(nullptr, bytes));
+    if ((env_ids && !d_ids) || !d_out)
+        return wfail(std::string("snk_link_states_host: ") + hipGetErrorString(hipGetLastError()));
+    if (snk_link_states(h, d_ids, n_rows, d_out, nullptr)) return 1;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return wfail(std::string("snk_link_states_host: ") + hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+int snk_link_inertial_offsets(const snk_params* p, double* out) {
+    if (!p || !out) return wfail("snk_link_inertial_offsets: null argument");
+    if (p->n_modules != 16 && p->n_modules != 32) return wfail("snk_link_inertial_offsets: n_modules must be 16 or 32");
+    std::unique_ptr<snk::HostModel> H(new snk::HostModel);      // (the model is large: on the heap)
+    snk::build_host_model(*p, *H);
+    for (int r = 0; r < snk::link_rows(H->n); r++)
+        for (int i = 0; i < 3; i++) out[3 * r + i] = H->link_c[r][i];
+    return 0;
+}
+
+int snk_copy_envs(snk_handle* h, const int32_t* src_ids_dev, const int32_t* dst_ids_dev, int32_t n_pairs, int32_t flags,
+                  void* stream) {
+    if (!h) return wfail("snk_copy_envs: null handle (h)");
+    if (!src_ids_dev || !dst_ids_dev) return wfail("snk_copy_envs: null id list");
+    if (n_pairs < 1) return wfail("snk_copy_envs: n_pairs must be at least 1");
+    if (flags & ~SNK_COPY_RESET_POSE) return wfail("snk_copy_envs: unknown bits in flags (SNK_COPY_RESET_POSE is the only one)");
+    snk::WorldView v;
+    if (snk::world_view(h, false, &v)) return 1;
+    static_assert((int)snk::WorldView::kTables == snk::kCopyTables, "one slot of the copy per table of the view");
+    snk::CopyArgs a;
+    for (int t = 0; t < snk::kCopyTables; t++) {
+        const bool take = t != snk::WorldView::kResetPose || (flags & SNK_COPY_RESET_POSE);
+        a.d[t] = take ? v.tables[t].d : nullptr;
+        a.floats[t] = (int)v.tables[t].floats;
+    }
+    const int blocks = n_pairs < 65536 ? n_pairs : 65536;
+    hipLaunchKernelGGL(snk::copy_envs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, src_ids_dev, dst_ids_dev,
+                       n_pairs, v.n_envs);
+    return launched("snk_copy_envs");
+}
+
+int snk_copy_envs_host(snk_handle* h, const int32_t* src_ids, const int32_t* dst_ids, int32_t n_pairs, int32_t flags) {
+    if (!h) return wfail("snk_copy_envs_host: null handle (h)");
+    if (!src_ids || !dst_ids) return wfail("snk_copy_envs_host: null id list");
+    if (n_pairs < 1) return wfail("snk_copy_envs_host: n_pairs must be at least 1");
+    if (flags & ~SNK_COPY_RESET_POSE)
+        return wfail("snk_copy_envs_host: unknown bits in flags (SNK_COPY_RESET_POSE is the only one)");
+    snk::WorldView v;
+    if (snk::world_view(h, true, &v)) return 1;
+    // validated before anything is written: a refused call leaves every table as it was
+    char msg[200];
+    int bad = bad_id(src_ids, n_pairs, v.n_envs);
+    if (bad >= 0) {
+        snprintf(msg, sizeof(msg), "snk_copy_envs_host: src_ids[%d] = %d is outside 0 .. %d", bad, (int)src_ids[bad], v.n_envs - 1);
+        return wfail(msg);
+    }
+    bad = bad_id(dst_ids, n_pairs, v.n_envs);
+    if (bad >= 0) {
+        snprintf(msg, sizeof(msg), "snk_copy_envs_host: dst_ids[%d] = %d is outside 0 .. %d", bad, (int)dst_ids[bad], v.n_envs - 1);
+        return wfail(msg);
+    }
+    std::vector<int> as_dst(v.n_envs, -1), as_src(v.n_envs, -1);      // the first index at which an env is named
+    for (int k = 0; k < n_pairs; k++)
+        if (as_src[src_ids[k]] < 0) as_src[src_ids[k]] = k;
+    for (int k = 0; k < n_pairs; k++) {
+        const int d = dst_ids[k];
+        if (as_dst[d] >= 0) {
+            snprintf(msg, sizeof(msg), "snk_copy_envs_host: dst_ids[%d] = %d repeats dst_ids[%d] (the destinations must be distinct)",
+                     k, d, as_dst[d]);
+            return wfail(msg);
+        }
+        as_dst[d] = k;
+        if (as_src[d] >= 0) {
+            snprintf(msg, sizeof(msg), "snk_copy_envs_host: dst_ids[%d] = %d is also src_ids[%d] (no env may be both a source and a "
+                     "destination)", k, d, as_src[d]);
+            return wfail(msg);
+        }
+    }
+    Staged s;
+    const size_t bytes = (size_t)n_pairs * sizeof(int32_t);
+    int32_t* d_src = static_cast<int32_t*>(s.up(src_ids, bytes));
+    int32_t* d_dst = static_cast<int32_t*>(s.up(dst_ids, bytes));
+    if (!d_src || !d_dst) return wfail(std::string("snk_copy_envs_host: ") + hipGetErrorString(hipGetLastError()));
+    if (snk_copy_envs(h, d_src, d_dst, n_pairs, flags, nullptr)) return 1;
+    if (hipDeviceSynchronize() != hipSuccess)
+        return wfail(std::string("snk_copy_envs_host: ") + hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+}  // extern "C"

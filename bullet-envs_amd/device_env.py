@@ -2,6 +2,10 @@
 
 DeviceVecEnv   torch CUDA(=HIP) tensors in, tensors out; the step kernel is enqueued on
                torch's current stream, nothing touches the host.
+DeviceWorld    the physics BELOW the fused env-step on the same terms: masked substeps, observation / mean height /
+               link positions, the states of all 3n + 2 links, resets and env forks, each one launch on the current
+               stream.  An env with another reward, termination rule, gait or control rate -- or a sampling-based
+               controller forking states -- is torch code over these calls and never leaves the GPU.
 ShardedVecEnv  one process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI).
                Global env g lives on rank g // envs_per_rank for its whole life; the
                physics never communicates.  Per env-step there is exactly one exchange each
@@ -180,8 +184,198 @@ class DeviceVecEnv(object):
         """[E, 7 + n] float32 ndarray: the reset-pose table (synchronises the device)."""
         return self.stepper.get_reset_pose()
 
+    @property
+    def world(self):
+        """A DeviceWorld on THIS env's handle: the same environments, below the fused step."""
+        if getattr(self, "_world", None) is None:
+            self._world = DeviceWorld(stepper=self.stepper, device_index=self.device.index)
+        return self._world
+
     def close(self):
         self.stepper.close()
+
+
+class DeviceWorld(object):
+    """The simulator without a task, on torch CUDA tensors: what pybullet.stepSimulation, getLinkState and
+    saveState / restoreState are to a script (snake.py:219-221, 286, 138-156), for every env of a handle at once.  Every
+    call is one launch on torch's current stream, ordered with what is enqueued there (a DeviceVecEnv.step or render on
+    the same handle included); nothing synchronises, nothing is copied to the host.  Calls on one handle are serialised by
+    the caller, as everywhere.
+
+    DeviceWorld(num_envs, ...) owns a handle of its own; DeviceVecEnv.world shares that env's."""
+
+    def __init__(self, num_envs=None, device_index=0, args=None, n_modules=16, params=None, stepper=None, **over):
+        import torch
+        self.torch = torch
+        torch.cuda.set_device(device_index)
+        self.device = torch.device("cuda", device_index)
+        self._owns = stepper is None
+        if stepper is None:
+            if num_envs is None:
+                raise ValueError("DeviceWorld needs num_envs (or the stepper of an existing env)")
+            params = params if params is not None else params_from_args(args, n_modules=n_modules, **over)
+            stepper = _lib.Stepper(num_envs, device=device_index, params=params)
+        self.stepper = stepper
+        self.params = stepper.params
+        self.num_envs = stepper.n_envs
+        self.n = stepper.n
+        self.obs_dim = stepper.obs_dim
+        self.link_rows = 3 * self.n + 2
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _arg(self, x, what, dtypes, shape):
+        """a caller's tensor as the kernels read it: on this device, of one of `dtypes`, of `shape`, contiguous"""
+        t = self.torch
+        if not isinstance(x, t.Tensor) or not x.is_cuda or x.device != self.device:
+            raise ValueError("%s must be a CUDA tensor on %s" % (what, self.device))
+        if x.dtype not in dtypes:
+            raise ValueError("%s must be %s, got %s" % (what, " or ".join(str(d) for d in dtypes), x.dtype))
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError("%s must have shape %s, got %s" % (what, tuple(shape), tuple(x.shape)))
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % what)
+        return x
+
+    def _out(self, out, what, shape, dtype=None):
+        t = self.torch
+        dtype = t.float32 if dtype is None else dtype
+        if out is None:
+            return t.empty(shape, dtype=dtype, device=self.device)
+        return self._arg(out, what, (dtype,), shape)
+
+    def _keep(self, *tensors):
+        """the kernels read these when the stream gets there: they stay alive until then"""
+        cur = self.torch.cuda.current_stream(self.device)
+        for x in tensors:
+            if x is not None:
+                x.record_stream(cur)
+
+    def step_simulation(self, targets, k=1, active=None, info=None):
+        """k physics substeps towards the joint targets [E, n] float32 (radians): setJointMotorControlArray +
+        stepSimulation (snake.py:219-221, 286).  active: uint8 / bool [E] or None (all); an env whose byte is 0 keeps
+        every bit of its state.  info: int32 [E, 2] or None -- solver iterations and contact count of the last substep;
+        rows of inactive envs are left alone."""
+        t = self.torch
+        targets = self._arg(targets, "targets", (t.float32,), (self.num_envs, self.n))
+        if active is not None:
+            active = self._arg(active, "active", (t.uint8, t.bool), (self.num_envs,))     # (a bool is one byte, 0 / 1)
+        if info is not None:
+            info = self._arg(info, "info", (t.int32,), (self.num_envs, 2))
+        if int(k) < 0:
+            raise ValueError("k must not be negative, got %d" % int(k))
+        self.stepper.substep_device(targets.data_ptr(), int(k), active.data_ptr() if active is not None else 0,
+                                    info.data_ptr() if info is not None else 0, self._stream())
+        self._keep(targets, active)
+
+    def observation(self, out=None):
+        """getObservation (snake.py:209-217) of every env: [E, 3n + 8] float32."""
+        out = self._out(out, "out", (self.num_envs, self.obs_dim))
+        self.stepper.observe_device(obs_ptr=out.data_ptr(), stream=self._stream())
+        return out
+
+    def mean_height(self, out=None):
+        """checkSnakeHeight's mean z (snake.py:237-245) of every env: [E] float32."""
+        out = self._out(out, "out", (self.num_envs,))
+        self.stepper.observe_device(height_ptr=out.data_ptr(), stream=self._stream())
+        return out
+
+    def link_positions(self, out=None):
+        """getLinkPositions (snake.py:138-146) of every env: [E, 3(n + 1)] float32, [x.., y.., z..] of links 0, 3, .., 3n."""
+        out = self._out(out, "out", (self.num_envs, 3 * (self.n + 1)))
+        self.stepper.observe_device(linkpos_ptr=out.data_ptr(), stream=self._stream())
+        return out
+
+    def link_states(self, env_ids=None, out=None):
+        """[k, 3n + 2, 16] float32: getLinkState(computeLinkVelocity=1) of every link of the envs `env_ids` (None: all;
+        an int32 CUDA tensor or a sequence; ids may repeat, any order; an id outside the handle gives zero rows).  Row r
+        is Bullet link r - 1 (row 0: the root); a row is [COM 3 | quaternion xyzw 4 | link-frame origin 3 | COM velocity
+        3 | angular velocity 3], world frame."""
+        t = self.torch
+        if env_ids is None:
+            ids, k = None, self.num_envs
+        else:
+            ids = t.as_tensor(env_ids, dtype=t.int32, device=self.device).reshape(-1).contiguous()
+            k = int(ids.numel())
+        if k < 1:
+            raise ValueError("env_ids must name at least one env")
+        out = self._out(out, "out", (k, self.link_rows, _lib.LINK_STATE_FLOATS))
+        self.stepper.link_states_device(ids.data_ptr() if ids is not None else 0, k, out.data_ptr(), self._stream())
+        self._keep(ids)
+        return out
+
+    def reset(self, mask=None, out=None):
+        """The soft reset (snake.py:96-99, 119-127) of the envs of `mask` (uint8 / bool [E]; None: all) onto their rows
+        of the reset-pose table.  Returns the observations [E, 3n + 8]; rows of unmasked envs are left as `out` had them
+        (zeros for a fresh tensor)."""
+        t = self.torch
+        if mask is not None:
+            mask = self._arg(mask, "mask", (t.uint8, t.bool), (self.num_envs,))
+        if out is None:
+            out = t.zeros((self.num_envs, self.obs_dim), dtype=t.float32, device=self.device)
+        else:
+            out = self._arg(out, "out", (t.float32,), (self.num_envs, self.obs_dim))
+        self.stepper.reset_device(mask.data_ptr() if mask is not None else 0, out.data_ptr(), self._stream())
+        self._keep(mask)
+        return out
+
+    def set_reset_pose(self, pose, mask=None):
+        """Rows [position 3 | quaternion xyzw 4 | joint angles n] of the reset-pose table from CUDA tensors (pose [E, 7 +
+        n] float32, mask uint8 / bool [E] or None): snk_set_reset_pose_dev on the current stream, nothing validated."""
+        t = self.torch
+        pose = self._arg(pose, "pose", (t.float32,), (self.num_envs, 7 + self.n))
+        if mask is not None:
+            mask = self._arg(mask, "mask", (t.uint8, t.bool), (self.num_envs,))
+        self.stepper.set_reset_pose_device(pose.data_ptr(), mask.data_ptr() if mask is not None else 0, self._stream())
+        self._keep(pose, mask)
+
+    def fork(self, src, dst, reset_pose=False):
+        """Env dst[i] becomes env src[i] in everything a Snapshot holds: state record, contact cache, free box, ground
+        friction -- and with reset_pose=True its row of the reset-pose table.
+        Host lists / arrays are VALIDATED (ids inside the handle, the dst ids distinct, no env on both sides; a ValueError
+        names the index) and then uploaded.  int32 CUDA tensors go to the kernel as they are, UNVALIDATED, without a
+        host round trip: the caller keeps that contract; broken, which copy wins is undefined and an id outside the
+        handle makes its pair a no-op."""
+        t = self.torch
+        if isinstance(src, t.Tensor) and src.is_cuda and isinstance(dst, t.Tensor) and dst.is_cuda:
+            k = int(src.numel())
+            s = self._arg(src.reshape(-1), "src", (t.int32,), (k,))
+            d = self._arg(dst.reshape(-1), "dst", (t.int32,), (k,))
+        else:
+            hs = np.asarray(src.cpu() if isinstance(src, t.Tensor) else src).reshape(-1)
+            hd = np.asarray(dst.cpu() if isinstance(dst, t.Tensor) else dst).reshape(-1)
+            check_fork_ids(hs, hd, self.num_envs)
+            s = t.as_tensor(hs.astype(np.int32), device=self.device)
+            d = t.as_tensor(hd.astype(np.int32), device=self.device)
+        if s.numel() < 1:
+            raise ValueError("fork needs at least one (src, dst) pair")
+        self.stepper.copy_envs_device(s.data_ptr(), d.data_ptr(), int(s.numel()), reset_pose, self._stream())
+        self._keep(s, d)
+
+    def close(self):
+        if self._owns:
+            self.stepper.close()
+
+
+def check_fork_ids(src, dst, num_envs):
+    """snk_copy_envs' contract on host id lists (what snk_copy_envs_host refuses): raises ValueError naming the index."""
+    if len(src) != len(dst):
+        raise ValueError("src and dst must name as many envs each, got %d and %d" % (len(src), len(dst)))
+    for name, ids in (("src", src), ("dst", dst)):
+        for i, e in enumerate(ids):
+            if int(e) != e or not 0 <= int(e) < num_envs:
+                raise ValueError("%s[%d] = %s is outside 0 .. %d" % (name, i, e, num_envs - 1))
+    first = {}
+    for i, e in enumerate(dst):
+        if int(e) in first:
+            raise ValueError("dst[%d] = %d repeats dst[%d] (the destinations must be distinct)" % (i, int(e), first[int(e)]))
+        first[int(e)] = i
+    sources = {int(e): i for i, e in reversed(list(enumerate(src)))}
+    for i, e in enumerate(dst):
+        if int(e) in sources:
+            raise ValueError("dst[%d] = %d is also src[%d] (no env may be both a source and a destination)"
+                             % (i, int(e), sources[int(e)]))
 
 
 class ShardedVecEnv(object):

@@ -16,6 +16,11 @@ line, which is also how tests check that the fused env-step kernel IS that logic
 
 Only what the path calls is implemented; anything else raises AttributeError (no silent stubs).  The world is created
 lazily, at the first call that needs it, from what loadURDF / changeDynamics / setGravity / setTimeStep said before.
+
+getLinkStates stays what the path reads: the COM positions of links 0, 3, ..., 3n, a placeholder in the orientation's
+place, any other link refused (tests/test_pybullet_client.py pins both, and its CPU stand-in answers link_positions
+only).  The orientations, origins and velocities of ALL 3n + 2 links are one level down: Stepper.link_states /
+DeviceWorld.link_states (snk_link_states), and Snake.getLinkOrientations / getBaseVelocity of snake_env.py.
 """
 import math
 import os

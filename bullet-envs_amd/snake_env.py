@@ -238,6 +238,15 @@ class Snake(object):
     def getLinkPositions(self):                          # snake.py:138-146: [x.., y.., z..] of links 0, 3, ..., 3n
         return self._need_env()._stepper.link_positions()[0].astype(np.float64)
 
+    def getLinkOrientations(self):                       # snake.py:148-156: [x.., y.., z.., w..] of links 0, 3, ..., 3n
+        rows = self._need_env()._stepper.link_states([0])[0, 1::3]      # Bullet link l is row l + 1 (snk_link_states)
+        return rows[:, 3:7].T.reshape(-1).astype(np.float64)
+
+    def getBaseVelocity(self):
+        """pybullet.getBaseVelocity of the snake: (linear velocity of the root link, angular velocity), world frame."""
+        root = self._need_env()._stepper.link_states([0])[0, 0]
+        return tuple(float(x) for x in root[10:13]), tuple(float(x) for x in root[13:16])
+
     def convertActionToJointCommand(self, action):       # snake.py:223-225
         return [a * self.SCALING_FACTOR for a in action]
 

@@ -270,6 +270,77 @@ int snk_step_traced_host(snk_handle* h, float* actions, float* obs, float* rew, 
  * For single-substep parity tests. */
 int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* info);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The tensor seam: the physics below the fused env-step, driven from device memory.  With these calls the loop of
+ * Snake.step (snake.py:283-304) -- or any other reward, termination, gait or control rate -- can be written by the
+ * caller on device tensors, one launch per call, nothing touching the host.  Every device-pointer form is asynchronous
+ * on `stream` (hipStream_t or NULL) and ordered with the steps, resets and renders enqueued there; none synchronises,
+ * copies or validates what lies in device memory.
+ *
+ * snk_substep (replaces pybullet.stepSimulation, snake.py:286, behind setJointMotorControlArray, snake.py:219-221): k
+ * physics substeps towards targets_dev [n_envs x n] f32 (radians).  It is snk_substep_host without the copies and the
+ * synchronisation, plus a mask: active_dev [n_envs] u8 or NULL (all).  An env whose byte is 0 is neither loaded nor
+ * stored: its record, contact cache, free box and info row keep their bits.  info_dev [n_envs x 2] i32 or NULL: solver
+ * iterations and contact count of the last substep.  The sensor pass runs on every substep, as in snk_substep_host.
+ *
+ * snk_observe (replaces Snake.getObservation snake.py:209-217, checkSnakeHeight's mean z snake.py:237-245 and
+ * Snake.getLinkPositions snake.py:138-146 in one pass): obs_dev [n_envs x obs_dim], height_dev [n_envs], linkpos_dev
+ * [n_envs x 3(n+1)] laid out as snk_link_positions; each may be NULL, all three NULL is refused. */
+int snk_substep(snk_handle* h, const float* targets_dev, int32_t k, const uint8_t* active_dev, int32_t* info_dev, void* stream);
+int snk_observe(snk_handle* h, float* obs_dev, float* height_dev, float* linkpos_dev, void* stream);
+
+/* snk_link_states (replaces pybullet.getLinkState(computeLinkVelocity=1) over every link, and getBasePositionAndOrientation
+ * / getBaseVelocity for the root: what Snake.getLinkPositions and Snake.getLinkOrientations, snake.py:138-156, read link
+ * by link) for any subset of the handle's envs at once, from their CURRENT device state.
+ *   snk_link_state_rows  3n + 2: the links of the unmerged URDF tree.  Row r is Bullet link r - 1: row 0 the root
+ *                (kdl_dummy_root, Bullet's base, link -1), row 1 `base`, rows 3k - 1, 3k, 3k + 1 INPUT_IF_k, COLLAR_k and
+ *                OUTPUT_BODY_k -- row i + 1 is the link of joint i.  0 (snk_last_error set) for a null handle.
+ *   env_ids_dev  [n_rows] i32, device; NULL: envs 0 .. n_rows - 1.  snk_render's rule: ids may repeat and come in any
+ *                order; they cannot be validated on this path, an id outside 0 .. n_envs - 1 reads nothing and its rows
+ *                are written as zeros.
+ *   out_dev      [n_rows][3n + 2][16] f32, 16-byte aligned.  A row:
+ *                  0-2 COM world position | 3-6 world orientation, quaternion xyzw | 7-9 world origin of the URDF link
+ *                  frame | 10-12 world linear velocity of the COM | 13-15 world angular velocity
+ *                -- PyBullet's getLinkState tuple without its two constant entries (snk_link_inertial_offsets has the
+ *                first; the second is the identity: the model's inertias are diagonal in link axes, so the inertial frame
+ *                is axis-parallel to the link frame and the one quaternion serves both orientations).
+ * Row 0 carries the record's own position, quaternion, omega and velocity verbatim: bitwise what snk_get_state returns.
+ * The other rows take their quaternion from the link's rotation matrix by the branch of the largest of (trace, m00,
+ * m11, m22) (Shepperd), normalised and signed so that w >= 0.  The COM velocity is v(body origin) + omega x (COM - body
+ * origin), the joint's own rate being part of the body's twist.  Bytes beyond [n_rows][3n + 2][16] are left alone;
+ * nothing of the handle's state is written.  Refused, naming the argument: a null or poisoned handle; n_rows < 1; a null
+ * or misaligned out_dev.
+ *
+ * snk_link_states_host: the same with HOST buffers (replaces the same getLinkState loop for a caller on the host); it
+ * synchronises the device first, like the state accessors, and also refuses an env id outside 0 .. n_envs - 1 and n_rows
+ * above n_envs without ids, each with its index.
+ *
+ * snk_link_inertial_offsets (replaces getLinkState(...)[2] and getDynamicsInfo(...)[3], localInertialFramePosition):
+ * host only, no handle and no device.  out [(3n+2) x 3]: every link's COM in its own link frame, from the same sub-link
+ * offsets the model compiler merges into the composite bodies. */
+int32_t snk_link_state_rows(const snk_handle* h);
+int snk_link_states(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float* out_dev, void* stream);
+int snk_link_states_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* out);
+int snk_link_inertial_offsets(const snk_params* p, double* out);
+
+/* snk_copy_envs (replaces pybullet.saveState in one world + restoreState in another, which the reference never needs --
+ * snake.py:96-99 resets instead -- and a sampling-based controller does: forking env states): env dst[i] becomes env
+ * src[i] in everything that is simulator state -- the whole state record (state, aux, joint-3 force, previous x), the
+ * link manifolds (contact_model 1), the free box and its manifold (obstacle 2), the ground friction; with
+ * SNK_COPY_RESET_POSE in flags the env's row of the reset-pose table as well.  src_ids_dev, dst_ids_dev [n_pairs] i32,
+ * device.  One workgroup per pair copies whole table rows, padding included.
+ * THE CONTRACT, which cannot be validated on this path (the limit snk_set_reset_pose_dev has): the dst ids are distinct,
+ * and no id is both a source and a destination -- otherwise which copy wins is undefined, and nothing worse happens.  A
+ * pair with an id outside 0 .. n_envs - 1 is a no-op.  Refused: a null or poisoned handle, a null id list, n_pairs < 1,
+ * unknown bits in flags.
+ * snk_copy_envs_host: the same with HOST id lists (synchronises first); it does validate: an id outside the handle, a
+ * repeated dst, or a dst that is also a src is refused, naming the index, with nothing written.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SNK_COPY_RESET_POSE 1   /* flags bit: copy the reset-pose row too */
+int snk_copy_envs(snk_handle* h, const int32_t* src_ids_dev, const int32_t* dst_ids_dev, int32_t n_pairs, int32_t flags,
+                  void* stream);
+int snk_copy_envs_host(snk_handle* h, const int32_t* src_ids, const int32_t* dst_ids, int32_t n_pairs, int32_t flags);
+
 /* State access (host buffers), for parity tests and checkpointing.  These calls (and snk_get_obs,
  * snk_mean_height, snk_link_positions, snk_set/get_ground_friction) synchronise the device first, so a step
  * still running on any stream is complete before the records are read or overwritten.
@@ -433,7 +504,8 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
  * kernel sets when one of its bounded waits runs out (nothing waits, nothing hangs).  Afterwards the handle behaves as
  * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
  * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction,
- * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) and snk_render / snk_render_host return
+ * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) and snk_render / snk_render_host and the tensor seam
+ * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host)) return
  * non-zero -- and snk_reset_pose_floats 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */
