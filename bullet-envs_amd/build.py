@@ -146,11 +146,36 @@ def build(force=False, verbose=False, defines=(), out=None):
     return target
 
 
+SCALAR_LIB = os.path.join(HERE, "libsnk_scalar.so")
+
+
+def build_scalar(force=False):
+    """libsnk_scalar.so: the same sources with -DSNK_SCALAR_DYNAMICS, the wave-uniform form of fk_vel and of the velocity
+    refresh (csrc/snk_dynamics.hpp) that the shipped kernels' lane form is compared with, byte for byte
+    (tests/test_gpu_lane_dynamics.py), and timed against.  Unlike the other variants it belongs to the test suite, so it
+    is rebuilt only when stale: a source newer than it, or another command line."""
+    cmd = _command(SCALAR_LIB, ("SNK_SCALAR_DYNAMICS",))
+    if not force and os.path.exists(SCALAR_LIB):
+        t = os.path.getmtime(SCALAR_LIB)
+        try:
+            with open(_stamp(SCALAR_LIB)) as f:
+                same = f.read() == _stamp_text(cmd)
+        except OSError:
+            same = False
+        if same and not any(os.path.getmtime(d) > t for d in sources() + [HEADER, os.path.abspath(__file__)]):
+            return SCALAR_LIB
+    return build(force=True, defines=("SNK_SCALAR_DYNAMICS",), out=SCALAR_LIB)
+
+
 if __name__ == "__main__":
     if "--print-flags" in sys.argv:
         print(" ".join(FLAGS))
     elif "--profile" in sys.argv:
         print(build(force=True, defines=("SNK_PROFILE",), out=os.path.join(HERE, "libsnk_prof.so")))
+    elif "--profile-fine" in sys.argv:     # the dynamics' own pieces instead of the phases (tools/profile_phases.py fine)
+        print(build(force=True, defines=("SNK_PROFILE", "SNK_PROFILE_FINE"), out=os.path.join(HERE, "libsnk_prof_fine.so")))
+    elif "--scalar-dynamics" in sys.argv:  # the wave-uniform form of fk_vel and the sweeps (tests/test_gpu_lane_dynamics.py, A/B timing)
+        print(build_scalar(force=True))
     elif "--sched-debug" in sys.argv:      # per-wave accounting of the step kernel's scheduler (tools/sched_stats.py)
         print(build(force=True, defines=("SNK_SCHED_DEBUG",), out=os.path.join(HERE, "libsnk_dbg.so")))
     else:

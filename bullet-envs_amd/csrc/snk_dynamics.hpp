@@ -9,9 +9,47 @@
 namespace snk {
 
 // ----------------------------------------------------------------------------------
-// S1: forward kinematics + link velocities of the chain (serial recurrence, evaluated
-// uniformly by the wave; lane 0 stores)
+// S1: forward kinematics + link velocities of the chain.  The chain over the bodies is a serial recurrence; within a
+// body step one lane owns one component (lane c < 3 of every quad: row c of R in three registers, component c of every
+// 3-vector), so that a vector operation is one instruction, R_parent Rfix nine, and a cross product two: its (y,z,x) and
+// (z,x,y) operands are quad_perm DPP reads.  Nothing crosses quads, and nothing goes through LDS on the way.  The quad's
+// fourth lane shadows the third's inputs and stores nothing; lanes 0..2 store what they hold.
+//
+// The arithmetic is that of the wave-uniform form (-DSNK_SCALAR_DYNAMICS: every lane evaluates every component, lane 0
+// stores; kept for tests/test_gpu_lane_dynamics.py and for A/B timing, in no shipped kernel), tree by tree as the compiler
+// contracts that form:  a b + c d + e f = fma(e, f, fma(a, b, c d)),  a b - c d = fma(a, b, -(c d)),  p + a s = fma(a, s, p),
+// spelled out here with contraction off.
 // ----------------------------------------------------------------------------------
+#ifndef SNK_SCALAR_DYNAMICS
+// x of lane (c + 1) % 3 / (c + 2) % 3 of the quad, for c < 3
+__device__ __forceinline__ float quad_yzx(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xC9, 0xf, 0xf, true));   // quad_perm [1,2,0,3]
+}
+__device__ __forceinline__ float quad_zxy(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xD2, 0xf, 0xf, true));   // quad_perm [2,0,1,3]
+}
+// component c of a x b, from a's two rotations (a body step crosses the parent's angular velocity three times)
+__device__ __forceinline__ float lane_cross(float a_yzx, float a_zxy, float b) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(a_yzx, quad_zxy(b), -(a_zxy * quad_yzx(b)));
+}
+// component c of the velocity part of a body step: w = wp + ax qd, v = vp + wp x r, zeta = [wp x ax qd ; wp x (wp x r)]
+struct LaneVel {
+    float w, v, za, zl;
+};
+__device__ __forceinline__ LaneVel lane_vel_step(float wp, float vp, float ax, float rb, float qdb) {
+#pragma clang fp contract(off)
+    const float wy = quad_yzx(wp), wz = quad_zxy(wp);
+    const float cr = lane_cross(wy, wz, rb);
+    LaneVel o;
+    o.w = __builtin_fmaf(ax, qdb, wp);
+    o.v = vp + cr;
+    o.za = lane_cross(wy, wz, ax) * qdb;
+    o.zl = lane_cross(wy, wz, cr);
+    return o;
+}
+#endif
+
 template <class LT>
 __device__ void fk_vel(LT& L, const DevModel& M, int lane) {
     constexpr int N = LT::kN;
@@ -36,6 +74,38 @@ __device__ void fk_vel(LT& L, const DevModel& M, int lane) {
     // with v_readlane instead of evaluating sincosf sixteen times one after the other
     float snv = 0.f, csv = 1.f;
     if (lane < N) sincosf(L.q()[lane], &snv, &csv);
+#ifndef SNK_SCALAR_DYNAMICS
+    const int ln = launder_lane(lane);
+    const int c = ln & 3, cc = c < 3 ? c : 2;
+    float C0 = c == 0 ? Rp[0] : (c == 1 ? Rp[3] : Rp[6]);      // row c of the parent's R
+    float C1 = c == 0 ? Rp[1] : (c == 1 ? Rp[4] : Rp[7]);
+    float C2 = c == 0 ? Rp[2] : (c == 1 ? Rp[5] : Rp[8]);
+    float opv = bs[cc], wpv = bs[7 + cc], vpv = bs[10 + cc];   // component c of the parent's origin and velocities
+#pragma unroll 4
+    for (int b = 1; b <= N; b++) {
+#pragma clang fp contract(off)
+        const float* Rf = M.Rfix[b];
+        const float* pf = M.pfix[b];
+        const float qdb = L.qd()[b - 1];
+        const float sn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(snv), b - 1));
+        const float cs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(csv), b - 1));
+        const float T0 = __builtin_fmaf(C2, Rf[6], __builtin_fmaf(C0, Rf[0], C1 * Rf[3]));   // row c of R_parent Rfix
+        const float T1 = __builtin_fmaf(C2, Rf[7], __builtin_fmaf(C0, Rf[1], C1 * Rf[4]));   // (its column 1: the joint axis)
+        const float T2 = __builtin_fmaf(C2, Rf[8], __builtin_fmaf(C0, Rf[2], C1 * Rf[5]));
+        const float N0 = __builtin_fmaf(T0, cs, -(sn * T2));
+        const float N2 = __builtin_fmaf(sn, T0, cs * T2);
+        const float rb = __builtin_fmaf(C2, pf[2], __builtin_fmaf(C0, pf[0], C1 * pf[1]));
+        const float o = opv + rb;
+        const LaneVel k = lane_vel_step(wpv, vpv, T1, rb, qdb);
+        if (ln < 3) {
+            L.R[b][3 * c] = N0; L.R[b][3 * c + 1] = T1; L.R[b][3 * c + 2] = N2;
+            L.o[b][c] = o; L.r[b][c] = rb; L.ax[b][c] = T1; L.w[b][c] = k.w; L.v[b][c] = k.v;
+            L.zeta[b][c] = k.za; L.zeta[b][3 + c] = k.zl;
+        }
+        C0 = N0; C1 = T1; C2 = N2;
+        opv = o; wpv = k.w; vpv = k.v;
+    }
+#else
 #pragma unroll 4
     for (int b = 1; b <= N; b++) {
         const float* Rf = M.Rfix[b];
@@ -72,7 +142,37 @@ __device__ void fk_vel(LT& L, const DevModel& M, int lane) {
         for (int i = 0; i < 9; i++) Rp[i] = Rn[i];
         op = o; wp = w; vp = v;
     }
+#endif
     lds_sync();
+}
+
+// The velocities changed and the pose did not (the sensor passes, after v += a dt): w, v, zeta of every body again, from
+// the axes and lever arms fk_vel left.  The same recurrence and the same lane map as fk_vel's velocity part.
+template <class LT>
+__device__ __forceinline__ void vel_refresh(LT& L, int lane) {
+    constexpr int N = LT::kN;
+#ifdef SNK_SCALAR_DYNAMICS
+    f3 wp = ld3(L.base() + 7), vp = ld3(L.base() + 10);
+    if (lane == 0) { st3(L.w[0], wp); st3(L.v[0], vp); }
+    for (int b = 1; b <= N; b++) {
+        f3 ax = ld3(L.ax[b]), rb = ld3(L.r[b]);
+        float qdb = L.qd()[b - 1];
+        f3 w = wp + ax * qdb, v = vp + cross(wp, rb);
+        f3 za = cross(wp, ax) * qdb, zl = cross(wp, cross(wp, rb));
+        if (lane == 0) { st3(L.w[b], w); st3(L.v[b], v); st3(&L.zeta[b][0], za); st3(&L.zeta[b][3], zl); }
+        wp = w; vp = v;
+    }
+#else
+    const int ln = launder_lane(lane);
+    const int c = ln & 3, cc = c < 3 ? c : 2;
+    float wpv = L.base()[7 + cc], vpv = L.base()[10 + cc];
+    if (ln < 3) { L.w[0][c] = wpv; L.v[0][c] = vpv; }
+    for (int b = 1; b <= N; b++) {
+        const LaneVel k = lane_vel_step(wpv, vpv, L.ax[b][cc], L.r[b][cc], L.qd()[b - 1]);
+        if (ln < 3) { L.w[b][c] = k.w; L.v[b][c] = k.v; L.zeta[b][c] = k.za; L.zeta[b][3 + c] = k.zl; }
+        wpv = k.w; vpv = k.v;
+    }
+#endif
 }
 
 // checkSnakeHeight's mean z over {`base` link COM, OUTPUT_BODY origins} (snake.py:237-245)
@@ -143,7 +243,11 @@ __device__ void body_bias(LT& L, const DevModel& M, int lane) {
 // FACTOR: also builds the articulated inertias IA, U = IA S, D = S^T U and the base inverse.
 // ----------------------------------------------------------------------------------
 template <class LT, bool FACTOR>
-__device__ void aba_main(LT& L, const DevModel& M, int lane) {
+__device__ void aba_main(LT& L, const DevModel& M, int lane
+#ifdef SNK_PROFILE_FINE
+                         , unsigned long long* prof_f = nullptr
+#endif
+) {
     constexpr int N = LT::kN;
     float cA[6], cB[9], cC[6];   // child contribution to the parent's articulated inertia
 #pragma unroll
@@ -235,6 +339,7 @@ __device__ void aba_main(LT& L, const DevModel& M, int lane) {
             for (int i = 0; i < 6; i++) cC[i] = Cp[i];
         }
     }
+    SNK_FSTAMP(2)
     // base: [alpha0; a0] = -IA0^-1 p0
     f3 pN = ld3(&L.p[0][0]) + cN, pF = ld3(&L.p[0][3]) + cF;
     float p0[6] = {pN.x, pN.y, pN.z, pF.x, pF.y, pF.z};
@@ -307,6 +412,7 @@ __device__ void aba_main(LT& L, const DevModel& M, int lane) {
         }
     }
     lds_sync();
+    SNK_FSTAMP(3)
     if (!FACTOR) return;   // the sensor pass only needs the base acceleration (acc0)
     // forward sweep: joint accelerations
     f3 al = ld3(&L.acc0[0]), a = ld3(&L.acc0[3]);
@@ -320,6 +426,7 @@ __device__ void aba_main(LT& L, const DevModel& M, int lane) {
         if (lane == 0) L.qdd[b - 1] = qdd;
     }
     lds_sync();
+    SNK_FSTAMP(4)
 }
 
 // True when the substep whose solve just produced `dv` (this lane's component of the velocity

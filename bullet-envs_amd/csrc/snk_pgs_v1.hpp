@@ -1036,18 +1036,7 @@ __device__ __forceinline__ void substep_v1(LT& L, const DevModel& M, int lane, f
         }
         lds_sync();
         // velocities changed in (3): refresh w, v, zeta of every body (pose unchanged)
-        {
-            f3 wp = ld3(L.base() + 7), vp = ld3(L.base() + 10);
-            if (lane == 0) { st3(L.w[0], wp); st3(L.v[0], vp); }
-            for (int b = 1; b <= N; b++) {
-                f3 ax = ld3(L.ax[b]), rb = ld3(L.r[b]);
-                float qdb = L.qd()[b - 1];
-                f3 w = wp + ax * qdb, v = vp + cross(wp, rb);
-                f3 za = cross(wp, ax) * qdb, zl = cross(wp, cross(wp, rb));
-                if (lane == 0) { st3(L.w[b], w); st3(L.v[b], v); st3(&L.zeta[b][0], za); st3(&L.zeta[b][3], zl); }
-                wp = w; vp = v;
-            }
-        }
+        vel_refresh(L, lane);
         lds_sync();
         body_bias<LT, false>(L, M, lane);
         lds_sync();

@@ -1067,18 +1067,7 @@ __device__ __noinline__ void sensor_pass_v2(LT& L, const DevModel& M, const int 
         for (int i = 0; i < nlim; i++) L.tauj[L.nc_joint[i]] += L.nc_sign[i] * L.nc_app[i] * M.inv_dt;
     }
     lds_sync();
-    {
-        f3 wp = ld3(L.base() + 7), vp = ld3(L.base() + 10);
-        if (lane == 0) { st3(L.w[0], wp); st3(L.v[0], vp); }
-        for (int b = 1; b <= N; b++) {
-            f3 ax = ld3(L.ax[b]), rb = ld3(L.r[b]);
-            float qdb = L.qd()[b - 1];
-            f3 w = wp + ax * qdb, v = vp + cross(wp, rb);
-            f3 za = cross(wp, ax) * qdb, zl = cross(wp, cross(wp, rb));
-            if (lane == 0) { st3(L.w[b], w); st3(L.v[b], v); st3(&L.zeta[b][0], za); st3(&L.zeta[b][3], zl); }
-            wp = w; vp = v;
-        }
-    }
+    vel_refresh(L, lane);
     lds_sync();
     SNK_STAMP(14)
     body_bias<LT, false>(L, M, lane);
@@ -1110,6 +1099,10 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
 #ifdef SNK_PROFILE
     unsigned long long prof_t[17];
 #endif
+#ifdef SNK_PROFILE_FINE
+    unsigned long long prof_fine[8];
+    unsigned long long* const prof_f = prof_fine;
+#endif
     SNK_STAMP(0)
     // (1) contacts of the current pose, (2) bias forces with gravity, joint damping torque
     const int nc = __builtin_amdgcn_readfirstlane(find_contacts_v2(L, M, lane, ovf));
@@ -1121,9 +1114,15 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
         L.qd_old[lane] = qd;
         L.tauj[lane] = -M.joint_damp * qd;   // PyBullet adds URDF joint damping as a torque [U]
     }
+    SNK_FSTAMP(0)
     body_bias<LT, true>(L, M, lane);
     lds_sync();
+    SNK_FSTAMP(1)
+#ifdef SNK_PROFILE_FINE
+    aba_main<LT, true>(L, M, lane, prof_f);
+#else
     aba_main<LT, true>(L, M, lane);
+#endif
     SNK_STAMP(2)
     // joint-0 force sensor, first pass [U] (parked in LDS: nothing but rows may live across the solve)
     {
@@ -1487,6 +1486,7 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     }
     // (7) apply the solver's delta-v (lower half's copy), motor torques, integrate positions
     lds_sync();
+    SNK_FSTAMP(5)
     dv = L.stM[lane][20];
     if (lane < 6) {
         float x = L.base()[7 + lane] + dv;
@@ -1522,11 +1522,18 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
         }
     }
     lds_sync();
+    SNK_FSTAMP(6)
     fk_vel(L, M, lane);
 #ifdef SNK_PROFILE
     SNK_STAMP(16)
+    SNK_FSTAMP(7)
     lds_sync();
+#ifdef SNK_PROFILE_FINE
+    // slots 0..6: body_bias, inward sweep, base inverse, outward sweep, (everything between), integrate, fk_vel
+    if (lane < 16) L.taum()[lane] = lane < 7 ? (float)(prof_fine[lane + 1] - prof_fine[lane]) : 0.f;
+#else
     if (lane < 16) L.taum()[lane] = (float)(prof_t[lane + 1] - prof_t[lane]);
+#endif
     lds_sync();
 #endif
 }

@@ -1,17 +1,23 @@
 """Phase durations inside one physics substep (s_memtime ticks, wave 0 of each env), from the
 -DSNK_PROFILE build:  python bullet-envs_amd/build.py --profile  (here), then on the GPU box
 SNK_LIB=bullet-envs_amd/libsnk_prof.so python tools/profile_phases.py [16|32]
-(16: the register-resident solve's substep; 32: the streamed-row solve's)"""
+(16: the register-resident solve's substep; 32: the streamed-row solve's)
+The dynamics' own pieces instead of the phases (16 links):  python bullet-envs_amd/build.py --profile-fine, then
+SNK_LIB=bullet-envs_amd/libsnk_prof_fine.so python tools/profile_phases.py fine"""
 import importlib, os, sys
 import numpy as np
 sys.path.insert(0, '.')
-assert os.environ.get("SNK_LIB", "").endswith("libsnk_prof.so"), "run with SNK_LIB=bullet-envs_amd/libsnk_prof.so"
+FINE = "fine" in sys.argv[1:]
+want = "libsnk_prof_fine.so" if FINE else "libsnk_prof.so"
+assert os.environ.get("SNK_LIB", "").endswith(want), "run with SNK_LIB=bullet-envs_amd/" + want
 pkg = importlib.import_module("bullet-envs_amd")
 names = ["contacts", "bias + ABA (factor, solve)", "sensor pass 1, v += a dt", "rows: motors (ABA deltas)",
          "rows: friction A (ABA deltas)", "  load 64 slots (A)", "rows: friction B (ABA deltas)", "  load 64 slots (B)",
          "rows: normals (ABA deltas)", "  load 32 slots + motor registers", "coupling scalars", "limit rows",
          "PGS, 50 iterations", "sensor pass 2: contact wrenches, FK", "sensor pass 2: bias + ABA", "integrate + FK"]
-NL = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+NL = int(sys.argv[1]) if len(sys.argv) > 1 and not FINE else 16
+if FINE:     # the stamps are not contiguous: slot 4 is everything between the outward sweep and the integration
+    names = ["body_bias", "ABA inward sweep", "ABA base inverse", "ABA outward sweep", None, "integrate", "fk_vel"]
 if NL == 32:
     names = ["ground contacts", "link-link contacts (GJK)", "bias + ABA (factor, solve)", "sensor pass 1, v += a dt",
              "rows: M^-1 columns (38 delta sweeps) + assembly, lane = dof", "PGS, 50 iterations", "sensor pass 2", "integrate", "FK of the new pose"]
@@ -23,7 +29,9 @@ for B in (1024, 2048):
     _, aux = st.get_state()
     t = aux[:, :len(names)].astype(np.float64)
     m = t.mean(axis=0)
+    if FINE:
+        m = np.array([v for n_, v in zip(names, m) if n_])
     print("B=%d (%d wave(s)/SIMD): ticks per phase, mean over envs; total %.0f" % (B, B // 1024, m.sum()))
-    for n_, v in zip(names, m):
+    for n_, v in zip([n_ for n_ in names if n_], m):
         print("   %-36s %9.0f  %5.1f %%" % (n_, v, 100 * v / m.sum()))
     st.close()
