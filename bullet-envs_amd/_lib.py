@@ -102,6 +102,8 @@ SYMBOLS = {
     "snk_debug_set_tickets": (C.c_int, [_vp, C.c_uint32]),
     "snk_debug_raise_alarm": (C.c_int, [_vp]),
     "snk_debug_noncontact_order": (C.c_int, [C.c_int32, _I32]),
+    "snk_debug_rows_layout": (C.c_int, [C.c_int32, _I32]),
+    "snk_debug_rows": (C.c_int, [_vp, C.c_int32, _F]),
     "snk_debug_reach_bound": (C.c_int, [C.POINTER(SnkParams), _F]),
     "snk_selftest": (C.c_int, [C.c_int32]),
     "snk_timing_enable": (C.c_int, [_vp, C.c_int32]),
@@ -193,6 +195,19 @@ def noncontact_order(n_modules):
     out = np.zeros(2 * int(n_modules), np.int32)
     check(load().snk_debug_noncontact_order(int(n_modules), out.ctypes.data_as(_I32)), "snk_debug_noncontact_order")
     return out
+
+
+#: the names of snk_debug_rows_layout's 14 numbers, in its order
+ROWS_LAYOUT = ("ND", "NC", "NCT", "kRows", "kFric", "kRS", "kMO", "kSpec", "kGeo", "kGeoOff", "kMmOff", "kYOff", "kRowFloats",
+               "kBoxBody")
+
+
+def rows_layout(n_modules):
+    """The layout of the streamed-row solve's block of rows (snk_debug_rows_layout; snk_lds.hpp: Lds<N, false>) as a dict
+    of ROWS_LAYOUT's names.  Host arithmetic only: no handle, no device."""
+    out = np.zeros(len(ROWS_LAYOUT), np.int32)
+    check(load().snk_debug_rows_layout(int(n_modules), out.ctypes.data_as(_I32)), "snk_debug_rows_layout")
+    return dict(zip(ROWS_LAYOUT, (int(x) for x in out)))
 
 
 def reach_bound(params=None, **over):
@@ -382,6 +397,18 @@ class Stepper:
         info = np.zeros((self.n_envs, 2), dtype=np.int32)
         check(self.lib.snk_substep_host(self.h, fptr(t), int(k), info.ctypes.data_as(_I32)), "snk_substep_host")
         return info
+
+    def debug_rows_layout(self):
+        """rows_layout of this handle's chain length."""
+        return rows_layout(self.n)
+
+    def debug_rows(self):
+        """[n_envs, kRowFloats] float32: every env's block of streamed rows as its last substep left it (snk_debug_rows:
+        streamed-row handles of at most as many envs as resident waves, right after substep())."""
+        out = np.zeros((self.n_envs, self.debug_rows_layout()["kRowFloats"]), dtype=np.float32)
+        for e in range(self.n_envs):
+            check(self.lib.snk_debug_rows(self.h, e, fptr(out[e])), "snk_debug_rows")
+        return out
 
     def get_state(self):
         s = np.zeros((self.n_envs, self.state_dim), dtype=np.float32)

@@ -69,6 +69,9 @@ struct snk_handle {
     snk::Sched sched = {};
     int32_t* h_alarm = nullptr;
     int grid_waves = 0;           // resident waves of the step kernel
+    // snk_debug_rows: the last launch on this handle was substep_kernel over every env (launch_substep sets it, every other launch of this
+    // file and every entry of the other objects, which come through render_view, clears it)
+    bool rows_of_substep = false;
     int model_slot = -1;          // index into snk::g_models (constant memory); -1: none free, unscheduled kernel
     bool use_sched = true;
     size_t lds_bytes = 0;
@@ -143,6 +146,7 @@ int launch_step(K, snk_handle* h, float* act, float* obs, float* rew, uint8_t* d
     a.model = h->d_model; a.order = h->plan ? h->d_order : nullptr;
     a.trace = trace; a.trace_rows = trace_rows; a.trace_stride = trace_row_floats(h->n);
     a.reset_all = h->d_reset;
+    h->rows_of_substep = false;
     if (h->use_sched) {
         hipLaunchKernelGGL((snk::plan_sched_kernel<K::N>), dim3(1), dim3(1024), 0, st, h->d_model, h->d_recs, act, h->sched,
                            h->n_envs);
@@ -160,12 +164,14 @@ template <class K>
 int launch_substep(K, snk_handle* h, const float* tgt, int k, int32_t* info, const uint8_t* active, hipStream_t st) {
     hipLaunchKernelGGL((snk::substep_kernel<K::N, K::V2, K::RULES>), dim3(h->grid_waves), dim3(64), h->lds_bytes, st,
                        h->d_model, h->d_recs, h->d_mu, tgt, k, info, h->n_envs, h->d_rows, h->d_mf, h->d_ovf, h->d_box, active);
+    h->rows_of_substep = active == nullptr;      // (a masked launch leaves the blocks of the envs it skips as they were)
     return 0;
 }
 template <class K>
 int launch_reset(K, snk_handle* h, const uint8_t* mask, float* obs, int hard, hipStream_t st) {
     hipLaunchKernelGGL((snk::reset_kernel<K::N, K::V2>), dim3(h->n_envs), dim3(64), h->lds_bytes, st, h->d_recs, mask, obs,
                        h->d_reset, hard, h->n_envs);
+    h->rows_of_substep = false;
     return 0;
 }
 // Waves of the step kernel a CU holds: __launch_bounds__(64, 2) = 2 per SIMD, 4 SIMDs, and the CU's LDS (160 KB on
@@ -234,6 +240,7 @@ int check_alarm(const snk_handle* h) {
 //   D I A  snk_get_state  snk_set_state  snk_get_manifold  snk_set_manifold  snk_get_box  snk_set_box  snk_get_obs
 //          snk_mean_height  snk_link_positions  snk_joint3_reaction_fz  snk_set_ground_friction  snk_get_reset_pose
 //          snk_set_reset_pose  snk_debug_set_tickets  snk_render_host  snk_link_states_host  snk_copy_envs_host
+//          snk_debug_rows
 //   D . A  snk_reset  snk_step  snk_step_packed  snk_step_traced  snk_reset_host  snk_step_host  snk_step_traced_host
 //          snk_substep_host  snk_set_reset_pose_dev  snk_render  snk_substep  snk_observe  snk_link_states  snk_copy_envs
 //   . . A  snk_reset_pose_floats (returns 0)
@@ -277,6 +284,7 @@ int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done,
 
 // one obs_kernel pass over h's records, enqueued on st (snk_observe; the host read-outs below)
 int launch_obs(snk_handle* h, float* obs, float* height, float* linkpos, hipStream_t st) {
+    h->rows_of_substep = false;
     const int rc = dispatch(h, [&](auto k) {
         hipLaunchKernelGGL((snk::obs_kernel<decltype(k)::N, decltype(k)::V2>), dim3(h->n_envs), dim3(64), h->lds_bytes,
                            st, h->d_model, h->d_recs, obs, height, linkpos, h->n_envs);
@@ -394,6 +402,7 @@ namespace snk {
 int api_fail(const char* msg) { return fail(msg); }
 int render_view(snk_handle* h, bool sync, RenderView* v) {
     if (enter(h, sync ? kState : (kDev | kAlive))) return 1;
+    h->rows_of_substep = false;
     v->device = h->device; v->n = h->n; v->n_envs = h->n_envs; v->v2 = h->v2;
     v->D = &h->D; v->d_model = h->d_model; v->d_recs = h->d_recs; v->d_box = h->d_box;
     return 0;
@@ -887,6 +896,7 @@ int snk_set_reset_pose_dev(snk_handle* h, const uint8_t* mask_dev, const float* 
     if (dispatch(h, [&](auto k) {
             hipLaunchKernelGGL((snk::reset_pose_copy_kernel<decltype(k)::N>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                                h->d_reset, mask_dev, pose_dev, h->n_envs);
+            h->rows_of_substep = false;
             return 0;
         })) return 1;
     return check_launch();
@@ -1027,6 +1037,40 @@ int snk_debug_noncontact_order(int32_t n_modules, int32_t* out) {
     if (n_modules == 16) return write(snk::NoncontactOrder<16>::tab);
     if (n_modules == 32) return write(snk::NoncontactOrder<32>::tab);
     return fail("snk_debug_noncontact_order: n_modules must be 16 or 32");
+}
+
+int snk_debug_rows_layout(int32_t n_modules, int32_t* out) {
+    if (!out) return fail("snk_debug_rows_layout: null output");
+    auto write = [out](auto n) {
+        using LR = snk::Lds<decltype(n)::value, false>;
+        const int32_t v[14] = {LR::ND, LR::NC, LR::NCT, LR::kRows, LR::kFric, LR::kRS, LR::kMO, LR::kSpec, LR::kGeo,
+                               (int32_t)LR::kGeoOff, (int32_t)LR::kMmOff, (int32_t)LR::kYOff, (int32_t)LR::kRowFloats,
+                               LR::kBoxBody};
+        for (int i = 0; i < 14; i++) out[i] = v[i];
+        return 0;
+    };
+    if (n_modules == 16) return write(std::integral_constant<int, 16>{});
+    if (n_modules == 32) return write(std::integral_constant<int, 32>{});
+    return fail("snk_debug_rows_layout: n_modules must be 16 or 32");
+}
+
+int snk_debug_rows(snk_handle* h, int32_t env, float* out) {
+    if (!h || !out) return fail("snk_debug_rows: null argument");
+    if (enter(h, kState)) return 1;
+    if (env < 0 || env >= h->n_envs) return fail("snk_debug_rows: no such environment");
+    if (h->v2)
+        return fail("snk_debug_rows: this handle runs the register-resident solve, whose rows never leave registers (the "
+                    "streamed-row kernels: 32 links, obstacle 2, SNK_FORCE_STREAMED)");
+    if (h->n_envs > h->grid_waves)
+        return fail("snk_debug_rows: more environments than resident waves: a workgroup's block of rows is shared by "
+                    "several environments");
+    if (!h->rows_of_substep)
+        return fail("snk_debug_rows: the last launch on this handle was not a substep of every environment (snk_substep_host, "
+                    "or snk_substep without a mask): only then has workgroup b run environment b and nothing else");
+    size_t rf = 0;
+    if (dispatch(h, [&](auto k) { rf = snk::Lds<decltype(k)::N, false>::kRowFloats; return 0; })) return 1;
+    HIP_TRY(hipMemcpy(out, h->d_rows + (size_t)env * rf, rf * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int snk_debug_reach_bound(const snk_params* p, float out[3]) {

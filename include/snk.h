@@ -517,6 +517,20 @@ int snk_debug_raise_alarm(snk_handle* h);
  * the kernels unroll their sweeps over. */
 int snk_debug_noncontact_order(int32_t n_modules, int32_t* out);
 
+/* Test hooks: the streamed-row solve's intermediate results ("stage by stage").  That solve keeps its
+ * constraint rows in a block of global memory per resident workgroup (snk_lds.hpp: Lds<N, false>): every normal and
+ * friction record, the 20-float geometry of every contact slot, M^-1 and the Y block behind it.
+ * snk_debug_rows_layout (host only, no handle): the 14 constants of that layout for n_modules 16 or 32, out[14] =
+ * [ND, NC, NCT, kRows, kFric, kRS, kMO, kSpec, kGeo, kGeoOff, kMmOff, kYOff, kRowFloats, kBoxBody].
+ * snk_debug_rows: waits for the device and copies block `env`, kRowFloats floats, as the last substep of that environment
+ * left it.  It refuses, with a message that says which, unless the handle runs the streamed-row kernels (32 links,
+ * obstacle 2, SNK_FORCE_STREAMED), holds no more environments than resident waves, and the last launch on it was
+ * snk_substep_host, or snk_substep with a null mask: only then has workgroup b run environment b and nothing else (a
+ * masked snk_substep skips environments, whose blocks keep what an earlier launch left: it counts as another launch).
+ * Device code is not involved. */
+int snk_debug_rows_layout(int32_t n_modules, int32_t* out);
+int snk_debug_rows(snk_handle* h, int32_t env, float* out /* host, kRowFloats */);
+
 /* Test hook (host only, no handle): what the kernels' bound on one substep's change of the mean height is made of for
  * this parameter set ("when the sensor pass runs"): out[0] = the longest joint-to-joint offset of the chain
  * and out[1] = the distance of the base link's COM from the root origin, both in metres and rounded up by 1.001 as the

@@ -100,6 +100,8 @@ def _load(f32=False):
         "orc_debug_gjk": (C.c_double, [vp, D, D, D]),
         "orc_contacts_full": (C.c_int32, [vp, D, C.c_int32]),
         "orc_last_contacts_full": (C.c_int32, [vp, D, C.c_int32]),
+        "orc_last_rows": (C.c_int32, [vp, C.c_int32, D, C.c_int32]),
+        "orc_last_rows_nd": (C.c_int32, [vp]),
         "orc_bench_gait": (C.c_double, [C.POINTER(OrcParams), C.c_int32, D, D, C.c_int32, C.c_int32, C.c_int32,
                                         C.POINTER(C.c_int64), D]),
         "orc_quicksort_equal_keys": (None, [C.c_int32, I]),
@@ -348,6 +350,25 @@ class OracleEnv:
         out = np.zeros((maxc, 12))
         nc = self.lib.orc_last_contacts_full(self.h, _dp(out), maxc)
         return out[:nc]
+
+    ROW_KINDS = {"noncontact": 0, "normals": 1, "frictions": 2}
+
+    def last_rows(self, kind, max_rows=1024):
+        """The constraint rows of the last substep (orc_last_rows), kind "noncontact" | "normals" | "frictions" (two per
+        contact): a dict of arrays J [k, nd], M (M^-1 J^T) [k, nd], dinv, rhs, lo, hi, applied, start [k] and the integer
+        arrays kind (0 limit, 1 motor, 2 normal, 3 friction), joint [k]; dir [k, 3], a contact row's world direction; nd = 6 + n, + 6 with the free box."""
+        nd = self.lib.orc_last_rows_nd(self.h)
+        out = np.zeros((max_rows, 2 * nd + 11))
+        k = self.lib.orc_last_rows(self.h, self.ROW_KINDS[kind], _dp(out), max_rows)
+        assert 0 <= k <= max_rows, (kind, k)
+        out = out[:k]
+        r = dict(J=out[:, :nd].copy(), M=out[:, nd:2 * nd].copy())
+        for i, name in enumerate(("dinv", "rhs", "lo", "hi", "applied", "start")):
+            r[name] = out[:, 2 * nd + i].copy()
+        r["kind"] = out[:, 2 * nd + 6].astype(int)
+        r["joint"] = out[:, 2 * nd + 7].astype(int)
+        r["dir"] = out[:, 2 * nd + 8:2 * nd + 11].copy()
+        return r
 
     def last_normal_impulses(self, maxc=256):
         out = np.zeros(maxc)

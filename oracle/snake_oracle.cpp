@@ -242,6 +242,10 @@ struct orc_env {
     std::vector<Contact> contacts;
     std::vector<Real> last_normal_impulse;
     std::vector<Real> last_friction_impulse;   /* 2 per contact: the two tangent rows' accumulated impulses */
+    /* the rows of the last substep (orc_last_rows): non-contact in creation order, normals, frictions (2 per contact),
+     * and the impulse every normal row started from (warm_start) */
+    std::vector<Row> last_rows[3];
+    std::vector<Real> last_start;
     std::vector<Manifold> manifolds;   /* contact_model 1: one per link (used by the links that carry a cylinder) */
     /* obstacle 2: the free box (a btMultiBody without links [U]) */
     Real bpos[3], bquat[4], bomega[3], bvel[3];
@@ -1573,6 +1577,7 @@ void substep(orc_env* e, const Real* targets) {
         for (int r = 0; r < 3; r++) { g[nds + r] = e->bomega[r]; g[nds + 3 + r] = e->bvel[r]; }
 
     std::vector<Row> noncontact, normals, frictions;
+    e->last_start.clear();
     auto finish_row = [&](Row& row, Real vel_target_minus_relvel_plus_pos) {
         Real d = 0;
         for (int i = 0; i < nd; i++) d += row.J[i] * row.M[i];
@@ -1694,6 +1699,7 @@ void substep(orc_env* e, const Real* targets) {
         if (P.warm_start && c.mpoint >= 0)
             row.applied = (c.kind == 3 ? e->bman.p[c.mpoint].lambda : e->manifolds[c.link].p[c.mpoint].lambda) *
                           (Real)P.warmstarting_factor;
+        e->last_start.push_back(row.applied);
         normals.push_back(row);
         /* two friction directions from btPlaneSpace1(n) ((0,-1,0), (1,0,0) for the ground's n = (0,0,1)),
          * each scaled by the link's anisotropic friction in link axes:
@@ -1883,6 +1889,9 @@ void substep(orc_env* e, const Real* targets) {
     }
     for (size_t k2 = 0; k2 < noncontact.size(); k2++)
         if (noncontact[k2].kind == 1) e->tau_motor[noncontact[k2].joint] = noncontact[k2].applied / dt;
+    e->last_rows[0].swap(noncontact);
+    e->last_rows[1].swap(normals);
+    e->last_rows[2].swap(frictions);
     integrate_positions(e);
 }
 
@@ -2056,6 +2065,8 @@ void orc_hard_reset(orc_env* e) {
     e->contacts.clear();
     e->last_normal_impulse.clear();
     e->last_friction_impulse.clear();
+    for (int k = 0; k < 3; k++) e->last_rows[k].clear();
+    e->last_start.clear();
     e->manifolds.clear();    /* resetSimulation + loadURDF: a new world (a soft reset keeps the contact cache [U]) */
     e->pairs.clear();
     box_reset(e);
@@ -2347,6 +2358,24 @@ int32_t orc_last_friction_impulses(const orc_env* e, double* out, int32_t maxc) 
     for (int i = 0; i < 2 * nc && i < 2 * maxc; i++) out[i] = e->last_friction_impulse[i];
     return nc;
 }
+int32_t orc_last_rows(const orc_env* e, int32_t kind, double* out, int32_t max_rows) {
+    if (kind < 0 || kind > 2) return -1;
+    const std::vector<Row>& rows = e->last_rows[kind];
+    const int nd = rows.empty() ? 0 : (int)rows[0].J.size(), w = 2 * nd + 11;
+    for (int k = 0; k < (int)rows.size() && k < max_rows; k++) {
+        const Row& r = rows[k];
+        double* o = out + (size_t)k * w;
+        for (int i = 0; i < nd; i++) { o[i] = (double)r.J[i]; o[nd + i] = (double)r.M[i]; }
+        o[2 * nd] = (double)r.dinv; o[2 * nd + 1] = (double)r.rhs;
+        o[2 * nd + 2] = (double)r.lo; o[2 * nd + 3] = (double)r.hi;
+        o[2 * nd + 4] = (double)r.applied;
+        o[2 * nd + 5] = kind == 1 && k < (int)e->last_start.size() ? (double)e->last_start[k] : 0.0;
+        o[2 * nd + 6] = (double)r.kind; o[2 * nd + 7] = (double)r.joint;
+        for (int i = 0; i < 3; i++) o[2 * nd + 8 + i] = kind == 0 ? 0.0 : (double)r.dir[i];
+    }
+    return (int32_t)rows.size();
+}
+int32_t orc_last_rows_nd(const orc_env* e) { return e->nd + (e->P.obstacle == 2 ? 6 : 0); }
 int32_t orc_last_normal_impulses(const orc_env* e, double* out, int32_t maxc) {
     int nc = (int)e->last_normal_impulse.size();
     for (int i = 0; i < nc && i < maxc; i++) out[i] = e->last_normal_impulse[i];

@@ -220,6 +220,15 @@ int32_t  orc_last_normal_impulses(const orc_env* e, double* out, int32_t max_con
 /* ... and the two friction rows' impulses per contact (out [max_contacts x 2]; friction_directions 1: the second 0);
  * returns the contact count */
 int32_t  orc_last_friction_impulses(const orc_env* e, double* out, int32_t max_contacts);
+/* the constraint rows of the last substep.  kind 0: the non-contact rows in the order they were created (the forward
+ * sweep's), 1: the normal rows, 2: the friction rows, two per contact.  Per row 2 nd + 11 doubles, nd = orc_last_rows_nd
+ * (6 + n, + the free box's six components under obstacle 2): [J nd | M^-1 J^T nd | dinv, rhs | lo, hi (friction: as the last
+ * sweep set them), accumulated impulse, impulse the row started from (normals under warm_start; else 0), row kind
+ * (0 limit, 1 motor, 2 normal, 3 friction), joint (-1: a contact row) | the row's world direction 3 (a contact's normal; a
+ * friction row's anisotropically scaled tangent; zeros for a non-contact row)].  Writes at most max_rows rows, returns how many the
+ * substep had (-1: no such kind) */
+int32_t  orc_last_rows(const orc_env* e, int32_t kind, double* out, int32_t max_rows);
+int32_t  orc_last_rows_nd(const orc_env* e);
 
 /* CPU-baseline driver for bench.py: n_envs envs x (warmup + steps) batched env-steps of the
  * serpenoid-gait stream on n_threads threads, timed inside (no Python in the loop).  Returns seconds for the

@@ -32,6 +32,18 @@ def test_library_exports_every_declared_symbol(pkg):
     assert sorted(_lib.SYMBOLS) == declared
 
 
+def test_debug_rows_symbols_without_a_device(pkg):
+    """snk_debug_rows_layout is host arithmetic (tests/test_np_rows.py holds its numbers to snk_lds.hpp); snk_debug_rows
+    refuses its null arguments before it touches anything."""
+    import ctypes as C
+    lib = pkg.load()
+    out = (C.c_int32 * 14)()
+    assert lib.snk_debug_rows_layout(16, out) == 0 and out[0] == 22 and out[5] == 80
+    assert lib.snk_debug_rows_layout(32, out) == 0 and out[0] == 38 and out[12] == 85040
+    assert lib.snk_debug_rows_layout(24, out) != 0 and b"16 or 32" in lib.snk_last_error()
+    assert lib.snk_debug_rows(None, 0, None) != 0 and b"snk_debug_rows: null argument" in lib.snk_last_error()
+
+
 def test_default_params_mirror_reference(pkg):
     p = pkg.default_params()
     assert p.n_modules == 16 and p.gait == 1                       # snake.py:16,62
