@@ -80,6 +80,10 @@ SYMBOLS = {
     "snk_link_states": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
     "snk_link_states_host": (C.c_int, [_vp, _I32, C.c_int32, _F]),
     "snk_link_inertial_offsets": (C.c_int, [C.POINTER(SnkParams), _D]),
+    "snk_contact_slots": (C.c_int32, [_vp]),
+    "snk_contacts": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "snk_contacts_host": (C.c_int, [_vp, _I32, C.c_int32, _F, _F, _I32]),
+    "snk_contact_links": (C.c_int, [C.POINTER(SnkParams), _I32]),
     "snk_copy_envs": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "snk_copy_envs_host": (C.c_int, [_vp, _I32, _I32, C.c_int32, C.c_int32]),
     "snk_get_state": (C.c_int, [_vp, _F, _F]),
@@ -118,6 +122,8 @@ SYMBOLS = {
 }
 RENDER_SHADOW = 1      # SNK_RENDER_SHADOW
 COPY_RESET_POSE = 1    # SNK_COPY_RESET_POSE
+CONTACT_FLOATS = 16     # SNK_CONTACT_FLOATS, floats per contact slot of snk_contacts: [point on the body 3 | point on the ground 3 |
+#                         normal 3 | distance | normal force N | impulse | cylinder (2n: the box) | j | live | 0]
 LINK_STATE_FLOATS = 16  # floats per row of snk_link_states: [COM 3 | quat xyzw 4 | link origin 3 | COM velocity 3 | omega 3]
 
 #: the camera behind render() / getCameraImage when the caller gives no matrices [U]: the reference calls
@@ -229,6 +235,15 @@ def link_inertial_offsets(n_modules=16, **params):
     p = default_params(n_modules=int(n_modules), **params)
     out = np.zeros((3 * int(n_modules) + 2, 3), np.float64)
     check(load().snk_link_inertial_offsets(C.byref(p), out.ctypes.data_as(_D)), "snk_link_inertial_offsets")
+    return out
+
+
+def contact_links(n_modules=16, **params):
+    """snk_contact_links: [2n] int32, the Bullet link index of every collision cylinder's link (PyBullet's linkIndexA of a
+    contact of that cylinder; row link + 1 of link_states).  Host arithmetic only: no handle, no device."""
+    p = default_params(n_modules=int(n_modules), **params)
+    out = np.zeros(2 * int(n_modules), np.int32)
+    check(load().snk_contact_links(C.byref(p), out.ctypes.data_as(_I32)), "snk_contact_links")
     return out
 
 
@@ -637,6 +652,42 @@ class Stepper:
         out = np.zeros((max(k, 1), 3 * self.n + 2, LINK_STATE_FLOATS), np.float32)
         check(self.lib.snk_link_states_host(self.h, ids.ctypes.data_as(_I32) if ids is not None else None, k, fptr(out)),
               "snk_link_states_host")
+        return out
+
+    @property
+    def contact_slots(self):
+        """snk_contact_slots: contact slots per env, 8n (+ 4 with the free box); raises on a contact_model 0 handle."""
+        k = int(self.lib.snk_contact_slots(self.h))
+        if k == 0:
+            raise RuntimeError("snk_contact_slots failed: %s" % last_error())
+        return k
+
+    def contacts_device(self, ids_ptr, n_rows, points_ptr=0, force_ptr=0, count_ptr=0, stream=0):
+        """snk_contacts: points [n_rows, slots, 16] f32, force [n_rows, 2n + 1] f32, count [n_rows] i32 (each a device
+        pointer or 0) for the envs ids [n_rows] i32 (0: envs 0 .. n_rows - 1).  Asynchronous on `stream`."""
+        check(self.lib.snk_contacts(self.h, ids_ptr or None, int(n_rows), points_ptr or None, force_ptr or None,
+                                    count_ptr or None, stream or None), "snk_contacts")
+
+    def contacts(self, env_ids=None):
+        """snk_contacts_host: (points [k, slots, 16] float32, force [k, 2n + 1] float32, count [k] int32) of the envs
+        `env_ids` (None: all; ids may repeat, any order), from the contact cache at the current pose.  A slot (4 c + j:
+        cached point j of cylinder c; the last four of an obstacle 2 handle: the free box) is [point on the body 3 | point
+        on the ground 3 | normal 3 | distance | normal force N | impulse | c (2n: the box) | j | live | 0], sixteen zeros
+        when not live; force sums a cylinder's live slots, entry 2n the box's."""
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        k = self.n_envs if ids is None else len(ids)
+        slots = self.contact_slots
+        points = np.zeros((max(k, 1), slots, CONTACT_FLOATS), np.float32)
+        force = np.zeros((max(k, 1), 2 * self.n + 1), np.float32)
+        count = np.zeros(max(k, 1), np.int32)
+        check(self.lib.snk_contacts_host(self.h, ids.ctypes.data_as(_I32) if ids is not None else None, k, fptr(points),
+                                         fptr(force), count.ctypes.data_as(_I32)), "snk_contacts_host")
+        return points, force, count
+
+    def contact_links(self):
+        """snk_contact_links of this handle's parameters (module function contact_links)."""
+        out = np.zeros(2 * self.n, np.int32)
+        check(self.lib.snk_contact_links(C.byref(self.params), out.ctypes.data_as(_I32)), "snk_contact_links")
         return out
 
     def copy_envs(self, src, dst, reset_pose=False):

@@ -1,5 +1,5 @@
-// snk_world.hip -- link states and the env fork behind snk_link_states / snk_copy_envs and their host forms, and the
-// host-only link read-outs (include/snk.h).  A translation unit and a code object of its own, like snk_render.hip:
+// snk_world.hip -- link states, reported contacts and the env fork behind snk_link_states / snk_contacts / snk_copy_envs and
+// their host forms, and the host-only link read-outs (include/snk.h).  A translation unit and a code object of its own, like snk_render.hip:
 // build.py compiles it to an object and links it into libsnk.so next to snk_api.hip, whose kernels it does not touch.
 #include <hip/hip_runtime.h>
 
@@ -28,6 +28,21 @@ void launch_links(const snk::WorldView& v, const int32_t* ids, int n_rows, float
     const int blocks = n_rows < 65536 ? n_rows : 65536;
     hipLaunchKernelGGL((snk::link_state_kernel<N, V2>), dim3(blocks), dim3(64), 0, st, v.d_model, v.d_recs, v.d_links, ids, out,
                        n_rows, v.n_envs);
+}
+
+template <int N, bool V2>
+void launch_contacts(const snk::WorldView& v, const int32_t* ids, int n_rows, float* points, float* force, int32_t* count,
+                     hipStream_t st) {
+    const int blocks = n_rows < 65536 ? n_rows : 65536;
+    hipLaunchKernelGGL((snk::contacts_kernel<N, V2>), dim3(blocks), dim3(64), 0, st, v.d_model, v.d_recs,
+                       v.tables[snk::WorldView::kManifolds].d, v.tables[snk::WorldView::kBox].d, ids, points, force, count,
+                       n_rows, v.n_envs);
+}
+
+// contact slots of a viewed handle (snk_contact_slots); 0: no contact cache
+int contact_slots(const snk::WorldView& v) {
+    if (!v.tables[snk::WorldView::kManifolds].d) return 0;
+    return 4 * 2 * v.n + (v.tables[snk::WorldView::kBox].d ? 4 : 0);
 }
 
 // a host id list against the handle: the first index whose id is outside 0 .. n_envs - 1, or -1
@@ -111,6 +126,78 @@ int snk_link_inertial_offsets(const snk_params* p, double* out) {
     snk::build_host_model(*p, *H);
     for (int r = 0; r < snk::link_rows(H->n); r++)
         for (int i = 0; i < 3; i++) out[3 * r + i] = H->link_c[r][i];
+    return 0;
+}
+
+int32_t snk_contact_slots(const snk_handle* h) {
+    if (!h) { wfail("snk_contact_slots: null handle"); return 0; }
+    snk::WorldView v;
+    if (snk::world_view(const_cast<snk_handle*>(h), false, &v)) return 0;
+    const int slots = contact_slots(v);
+    if (!slots) wfail("snk_contact_slots: this handle has contact_model 0 (no contact cache)");
+    return slots;
+}
+
+int snk_contacts(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float* points_dev, float* force_dev,
+                 int32_t* count_dev, void* stream) {
+    if (!h) return wfail("snk_contacts: null handle (h)");
+    if (n_rows < 1) return wfail("snk_contacts: n_rows must be at least 1");
+    if (!points_dev && !force_dev && !count_dev) return wfail("snk_contacts: points_dev, force_dev and count_dev are all null");
+    if (reinterpret_cast<uintptr_t>(points_dev) % 16 != 0)
+        return wfail("snk_contacts: points_dev must be 16-byte aligned (the records leave as 16-byte stores)");
+    snk::WorldView v;
+    if (snk::world_view(h, false, &v)) return 1;
+    if (!contact_slots(v)) return wfail("snk_contacts: this handle has contact_model 0 (no contact cache)");
+    hipStream_t st = (hipStream_t)stream;
+    if (v.n == 16 && v.v2) launch_contacts<16, true>(v, env_ids_dev, n_rows, points_dev, force_dev, count_dev, st);
+    else if (v.n == 16) launch_contacts<16, false>(v, env_ids_dev, n_rows, points_dev, force_dev, count_dev, st);
+    else if (v.n == 32) launch_contacts<32, false>(v, env_ids_dev, n_rows, points_dev, force_dev, count_dev, st);
+    else return wfail("snk_contacts: unsupported n_modules (16 or 32)");
+    return launched("snk_contacts");
+}
+
+int snk_contacts_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* points, float* force, int32_t* count) {
+    if (!h) return wfail("snk_contacts_host: null handle (h)");
+    if (n_rows < 1) return wfail("snk_contacts_host: n_rows must be at least 1");
+    if (!points && !force && !count) return wfail("snk_contacts_host: points, force and count are all null");
+    snk::WorldView v;
+    if (snk::world_view(h, true, &v)) return 1;
+    const int slots = contact_slots(v);
+    if (!slots) return wfail("snk_contacts_host: this handle has contact_model 0 (no contact cache)");
+    char msg[160];
+    const int bad = env_ids ? bad_id(env_ids, n_rows, v.n_envs) : -1;
+    if (bad >= 0) {
+        snprintf(msg, sizeof(msg), "snk_contacts_host: env_ids[%d] = %d is outside 0 .. %d", bad, (int)env_ids[bad], v.n_envs - 1);
+        return wfail(msg);
+    }
+    if (!env_ids && n_rows > v.n_envs) {
+        snprintf(msg, sizeof(msg), "snk_contacts_host: n_rows %d without env_ids is more than the handle's %d envs", (int)n_rows,
+                 v.n_envs);
+        return wfail(msg);
+    }
+    const size_t pb = (size_t)n_rows * slots * snk::kContactFloats * sizeof(float);
+    const size_t fb = (size_t)n_rows * (2 * v.n + 1) * sizeof(float), cb = (size_t)n_rows * sizeof(int32_t);
+    Staged s;
+    int32_t* d_ids = env_ids ? static_cast<int32_t*>(s.up(env_ids, (size_t)n_rows * sizeof(int32_t))) : nullptr;
+    float* d_pts = points ? static_cast<float*>(s.up(nullptr, pb)) : nullptr;
+    float* d_force = force ? static_cast<float*>(s.up(nullptr, fb)) : nullptr;
+    int32_t* d_count = count ? static_cast<int32_t*>(s.up(nullptr, cb)) : nullptr;
+    if ((env_ids && !d_ids) || (points && !d_pts) || (force && !d_force) || (count && !d_count))
+        return wfail(std::string("snk_contacts_host: ") + hipGetErrorString(hipGetLastError()));
+    if (snk_contacts(h, d_ids, n_rows, d_pts, d_force, d_count, nullptr)) return 1;
+    if (hipDeviceSynchronize() != hipSuccess || (points && hipMemcpy(points, d_pts, pb, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (force && hipMemcpy(force, d_force, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (count && hipMemcpy(count, d_count, cb, hipMemcpyDeviceToHost) != hipSuccess))
+        return wfail(std::string("snk_contacts_host: ") + hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+int snk_contact_links(const snk_params* p, int32_t* out) {
+    if (!p || !out) return wfail("snk_contact_links: null argument");
+    if (p->n_modules != 16 && p->n_modules != 32) return wfail("snk_contact_links: n_modules must be 16 or 32");
+    // cylinder c is the collider of INPUT_INTERFACE_k (even c = 2k - 2: Bullet link 3k - 2) or of OUTPUT_BODY_k (odd c =
+    // 2k - 1: link 3k) -- build_host_model's cylinder loop, in the link numbering of its link table (row = link + 1)
+    for (int c = 0; c < 2 * p->n_modules; c++) out[c] = (c & 1) ? 3 * ((c + 1) / 2) : 3 * (c / 2) + 1;
     return 0;
 }
 

@@ -305,6 +305,37 @@ class DeviceWorld(object):
         self._keep(ids)
         return out
 
+    def contacts(self, env_ids=None, out=None):
+        """(points [k, slots, 16] float32, force [k, 2n + 1] float32, count [k] int32): the ground contacts of the envs
+        `env_ids` (None: all; an int32 CUDA tensor or a sequence; ids may repeat, any order; an id outside the handle gives
+        zeros), read from the contact cache at the current pose by one launch (snk_contacts; include/snk.h has the
+        contract).  Slot 4 c + j is cached point j of cylinder c, the last four of an obstacle 2 world the free box's; a
+        slot is [point on the body 3 | point on the ground 3 | normal 3 | distance | normal force N | impulse | c (2n: the
+        box) | j | live | 0], zeros when not live.  out: a (points, force, count) tuple of tensors to write into."""
+        t = self.torch
+        if env_ids is None:
+            ids, k = None, self.num_envs
+        else:
+            ids = t.as_tensor(env_ids, dtype=t.int32, device=self.device).reshape(-1).contiguous()
+            k = int(ids.numel())
+        if k < 1:
+            raise ValueError("env_ids must name at least one env")
+        po, fo, co = (None, None, None) if out is None else out
+        points = self._out(po, "out[0]", (k, self.stepper.contact_slots, _lib.CONTACT_FLOATS))
+        force = self._out(fo, "out[1]", (k, 2 * self.n + 1))
+        count = self._out(co, "out[2]", (k,), t.int32)
+        self.stepper.contacts_device(ids.data_ptr() if ids is not None else 0, k, points.data_ptr(), force.data_ptr(),
+                                     count.data_ptr(), self._stream())
+        self._keep(ids)
+        return points, force, count
+
+    def contact_forces(self, out=None):
+        """[E, 2n + 1] float32: the normal force of the ground on every cylinder of every env, in newtons (entry 2n: on
+        the free box, 0 without one) -- the touch / ground-reaction term of a reward written over step_simulation."""
+        out = self._out(out, "out", (self.num_envs, 2 * self.n + 1))
+        self.stepper.contacts_device(0, self.num_envs, force_ptr=out.data_ptr(), stream=self._stream())
+        return out
+
     def reset(self, mask=None, out=None):
         """The soft reset (snake.py:96-99, 119-127) of the envs of `mask` (uint8 / bool [E]; None: all) onto their rows
         of the reset-pose table.  Returns the observations [E, 3n + 8]; rows of unmasked envs are left as `out` had them

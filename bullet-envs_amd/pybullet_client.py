@@ -21,6 +21,9 @@ getLinkStates stays what the path reads: the COM positions of links 0, 3, ..., 3
 place, any other link refused (tests/test_pybullet_client.py pins both, and its CPU stand-in answers link_positions
 only).  The orientations, origins and velocities of ALL 3n + 2 links are one level down: Stepper.link_states /
 DeviceWorld.link_states (snk_link_states), and Snake.getLinkOrientations / getBaseVelocity of snake_env.py.
+
+getContactPoints answers what the handle holds: the ground contacts of the snake and of the free block, from the contact
+cache (snk_contacts).  Link-link and link-block contacts are stateless in the kernels: a query for them is refused.
 """
 import math
 import os
@@ -311,3 +314,40 @@ class BulletClient(object):
         # 4-vectors; snake.py:143 builds an array from the tuples, which numpy >= 1.24 only accepts when they have one
         # length -- hence a 3-vector placeholder in the orientation's place)
         return [((float(lp[0, i // 3]), float(lp[1, i // 3]), float(lp[2, i // 3])), (0.0, 0.0, 0.0)) for i in idx]
+
+    def getContactPoints(self, bodyA=-1, bodyB=-1, linkIndexA=-2, linkIndexB=-2, **kw):
+        """PyBullet's list of 14-tuples (contactFlag, bodyA, bodyB, linkIndexA, linkIndexB, positionOnA, positionOnB,
+        contactNormalOnB, distance, normalForce, lateralFriction1, lateralFrictionDir1, lateralFriction2,
+        lateralFrictionDir2) for the pair (snake, plane) or (block, plane), given in either order and never swapped -- A is
+        the snake (or the block), B the plane, the ids those loadURDF returned: the live slots of snk_contacts, in slot
+        order (include/snk.h, "The reported contacts").  The positions are those of the CURRENT pose (PyBullet: of the
+        last collision pass), the normal force that of the last substep.  [U] The four lateral-friction entries are zeros: the kernels store no friction impulse per point.
+        linkIndexA / linkIndexB (-2: any) filter by the link on their side; the plane's and the block's link is -1.
+        Refused (NotImplementedError): a query that leaves the pair open, and snake-snake or snake-block pairs -- those
+        contacts are stateless in the kernels, the handle does not hold them."""
+        if kw:
+            raise NotImplementedError("BulletClient.getContactPoints: %s" % sorted(kw))
+        pair = (bodyA, bodyB)
+        if self._PLANE not in pair or bodyA == bodyB or not all(b in self._bodies for b in pair):
+            raise NotImplementedError(
+                "BulletClient.getContactPoints: only (snake, plane) and (block, plane) are held by the handle (the contact "
+                "cache); got bodyA=%r, bodyB=%r -- link-link and link-block contacts are stateless in the kernels and not "
+                "stored, and a query that leaves a body open would have to list them" % (bodyA, bodyB))
+        mover = bodyA if bodyB == self._PLANE else bodyB
+        st = self._stepper()
+        points = st.contacts()[0][0].astype(np.float64)
+        n = self._n
+        if mover == self._SNAKE:
+            rows = points[:8 * n]
+            links = np.repeat(np.asarray(st.contact_links(), dtype=np.int64), 4)
+        else:
+            rows = points[8 * n:]
+            links = np.full(len(rows), -1, dtype=np.int64)
+        # the filters belong to the bodies as the query names them; the tuples are never swapped: A is the moving body
+        want_mover, want_plane = (linkIndexB, linkIndexA) if bodyA == self._PLANE else (linkIndexA, linkIndexB)
+        if want_plane not in (-2, -1):
+            return []
+        zero3 = (0.0, 0.0, 0.0)
+        return [(0, mover, self._PLANE, int(link), -1, tuple(float(v) for v in r[0:3]), tuple(float(v) for v in r[3:6]),
+                 tuple(float(v) for v in r[6:9]), float(r[9]), float(r[10]), 0.0, zero3, 0.0, zero3)
+                for r, link in zip(rows, links) if r[14] != 0.0 and want_mover in (-2, link)]

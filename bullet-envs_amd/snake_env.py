@@ -600,6 +600,14 @@ class SnakeVecEnv(VecEnv):
             view, proj = (dv if view is None else view), (dp if proj is None else proj)
         return self._stepper.render(view, proj, width, height, env_ids=env_ids, shadow=shadow)
 
+    def contact_points(self, env_ids=None):
+        """Ground contacts of the envs `env_ids` (None: all; ids may repeat, any order) as numpy arrays: (points [k, slots,
+        16] float32, force [k, 2n + 1] float32, count [k] int32) -- what getContactPoints(snake, plane) would list, as a
+        fixed table per env (Stepper.contacts has the layout; snk_contacts in include/snk.h the contract): slot 4 c + j
+        is cached point j of cylinder c, force[:, c] the normal force on cylinder c in newtons (entry 2n: the free box's),
+        count the live slots.  Link-link and link-box contacts are not reported, friction forces neither."""
+        return self._stepper.contacts(env_ids)
+
     def set_reset_pose(self, pose, mask=None):
         """Where the envs of `mask` (None: all) start their next episodes -- at reset() and at the auto-reset inside
         step(): pose [num_envs, 7 + n] (or one row for all) = [initPosition 3 | initOrientation xyzw 4 | initState n],

@@ -341,6 +341,71 @@ int snk_copy_envs(snk_handle* h, const int32_t* src_ids_dev, const int32_t* dst_
                   void* stream);
 int snk_copy_envs_host(snk_handle* h, const int32_t* src_ids, const int32_t* dst_ids, int32_t n_pairs, int32_t flags);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reported contacts: the contract of snk_contacts (replaces pybullet.getContactPoints(snake, plane) and
+ * getContactPoints(block, plane), which the reference never calls and a reward written over the tensor seam does: touch
+ * flags, ground-reaction terms).  The kernel (bullet-envs_amd/csrc/snk_world.hpp: contacts_kernel) and the independent
+ * numpy model of the tests (tests/np_contacts.py) are both written from this text.  contact_model 1 only: what is
+ * reported is the contact CACHE the handle holds (snk_get_manifold, snk_get_box), read where it lies.
+ *
+ * Contact slots.  One env's contacts are a fixed table of slots.  snk_contact_slots(h) = 4 * 2n, and 4 * 2n + 4 on an
+ * obstacle 2 handle; 0, with snk_last_error set, for a contact_model 0 handle, a null handle or a poisoned one (the calls
+ * below then refuse).  Slot 4 c + j is cached point j of cylinder c, the cylinders in link order: the order of
+ * snk_get_manifold.  The last four slots of an obstacle 2 handle are the free box's points with the plane.
+ *
+ * The record.  A slot is 16 floats:
+ *   0-2    the point on the moving body in world coordinates at the CURRENT pose.  Cylinder c, cached point a (in its
+ *          link's coordinates): centre_c + Rw_c (a - (0, 0, cyl_zoff)), centre_c and Rw_c the cylinder's world frame as the
+ *          contact finder's refresh forms it -- Rw_c = R_b cyl_R[c], centre_c = o_b + R_b cyl_c[c] on the frame (R_b, o_b)
+ *          of composite body b = (c + 1) / 2 from the forward kinematics; cyl_zoff as snk_params_derived reports it.
+ *          The box: pos + R(quat) a, pos and quat as snk_get_box reports them.
+ *   3-5    the point on the ground as cached: (b.x, b.y, 0).
+ *   6-8    the contact normal on the ground, towards the body: (0, 0, 1).
+ *   9      the distance at the current pose: float 2 - float 5.  (The cached point already contains the collision margin.)
+ *   10     the normal force in newtons: the cached impulse / dt, dt the handle's time step as the kernels hold it (float32).
+ *   11     the cached impulse itself.
+ *   12     the cylinder index c; 2n for the box.  (Small integers: exact as floats.)
+ *   13     j.
+ *   14     1.0 if the slot is live (j < the cylinder's count, the count taken as 0 .. 4), else 0.0.
+ *   15     0.
+ * A slot that is not live is sixteen zeros, whatever stale point the cache keeps there.
+ *
+ * What the numbers mean.
+ *   - The positions are those of the pose the state holds NOW.  PyBullet's getContactPoints reports them as of the last
+ *     collision pass, one dt of motion earlier; the cache does not keep that pass's distances: a documented deviation
+ *     (DESIGN.md 3).
+ *   - The force is that of the last substep in which the point had a row.  An env-step of 0 substeps leaves it stale.
+ *   - A cached point that the next refresh would drop (beyond the breaking threshold at the current pose) is reported
+ *     as the cache holds it.  The cache is the state.
+ *   - Link-link and link-box contacts are stateless in the kernels and carry no stored impulse: they are NOT reported.
+ *     Friction impulses are not stored either.
+ *
+ * Outputs, per requested env (row):
+ *   points_dev  [n_rows][slots][16] f32, 16-byte aligned;
+ *   force_dev   [n_rows][2n + 1] f32: per cylinder the sum of float 10 over its live slots, j ascending; entry 2n is the
+ *               box's, 0 without obstacle 2;
+ *   count_dev   [n_rows] i32: the number of live slots.
+ * Each may be NULL; all three NULL is refused.
+ *
+ * snk_contacts follows snk_link_states' shape and rules: env_ids_dev [n_rows] i32 or NULL (envs 0 .. n_rows - 1), ids may
+ * repeat and come in any order; an id outside 0 .. n_envs - 1 reads nothing and its outputs are zeros.  Asynchronous on
+ * `stream`, one launch (one wave per row), no atomics and no waits; it does not synchronise, copy or validate.  Bytes
+ * beyond the outputs are left alone; nothing of the handle's state is written, nothing is allocated.  Refused, naming the
+ * argument: a null or poisoned handle; a contact_model 0 handle; n_rows < 1; all three outputs null; a misaligned
+ * points_dev.
+ * snk_contacts_host: the same with HOST buffers; it synchronises the device first, like the state accessors, and also
+ * refuses an env id outside 0 .. n_envs - 1 and n_rows above n_envs without ids, each with its index.
+ * snk_contact_links: host only, no handle and no device.  out [2n] i32: the Bullet link index of every cylinder's link
+ * (INPUT_INTERFACE_k = 3k - 2 for even c = 2k - 2, OUTPUT_BODY_k = 3k for odd c = 2k - 1) -- PyBullet's linkIndexA, and
+ * row link + 1 of snk_link_states.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SNK_CONTACT_FLOATS 16   /* floats per contact slot */
+int32_t snk_contact_slots(const snk_handle* h);
+int snk_contacts(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float* points_dev, float* force_dev,
+                 int32_t* count_dev, void* stream);
+int snk_contacts_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* points, float* force, int32_t* count);
+int snk_contact_links(const snk_params* p, int32_t* out /* [2n] */);
+
 /* State access (host buffers), for parity tests and checkpointing.  These calls (and snk_get_obs,
  * snk_mean_height, snk_link_positions, snk_set/get_ground_friction) synchronise the device first, so a step
  * still running on any stream is complete before the records are read or overwritten.
@@ -505,8 +570,8 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
  * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
  * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction,
  * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) and snk_render / snk_render_host and the tensor seam
- * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host)) return
- * non-zero -- and snk_reset_pose_floats 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
+ * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host), snk_contacts(_host)) return
+ * non-zero -- and snk_reset_pose_floats and snk_contact_slots 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */
 int snk_debug_raise_alarm(snk_handle* h);
