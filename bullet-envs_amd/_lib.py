@@ -644,14 +644,19 @@ class Stepper:
         check(self.lib.snk_copy_envs(self.h, src_ptr or None, dst_ptr or None, int(n_pairs),
                                      COPY_RESET_POSE if reset_pose else 0, stream or None), "snk_copy_envs")
 
+    def _ids(self, env_ids):
+        """(int32 array or None, how many envs it names, its pointer or None) of an `env_ids` argument (None: all envs)"""
+        if env_ids is None:
+            return None, self.n_envs, None
+        ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        return ids, len(ids), ids.ctypes.data_as(_I32)
+
     def link_states(self, env_ids=None):
         """snk_link_states_host: [k, 3n + 2, 16] float32 of the envs `env_ids` (None: all; ids may repeat, any order):
         per link [COM 3 | quaternion xyzw 4 | link-frame origin 3 | COM velocity 3 | angular velocity 3], world frame."""
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-        k = self.n_envs if ids is None else len(ids)
+        ids, k, idp = self._ids(env_ids)
         out = np.zeros((max(k, 1), 3 * self.n + 2, LINK_STATE_FLOATS), np.float32)
-        check(self.lib.snk_link_states_host(self.h, ids.ctypes.data_as(_I32) if ids is not None else None, k, fptr(out)),
-              "snk_link_states_host")
+        check(self.lib.snk_link_states_host(self.h, idp, k, fptr(out)), "snk_link_states_host")
         return out
 
     @property
@@ -674,14 +679,13 @@ class Stepper:
         cached point j of cylinder c; the last four of an obstacle 2 handle: the free box) is [point on the body 3 | point
         on the ground 3 | normal 3 | distance | normal force N | impulse | c (2n: the box) | j | live | 0], sixteen zeros
         when not live; force sums a cylinder's live slots, entry 2n the box's."""
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-        k = self.n_envs if ids is None else len(ids)
+        ids, k, idp = self._ids(env_ids)
         slots = self.contact_slots
         points = np.zeros((max(k, 1), slots, CONTACT_FLOATS), np.float32)
         force = np.zeros((max(k, 1), 2 * self.n + 1), np.float32)
         count = np.zeros(max(k, 1), np.int32)
-        check(self.lib.snk_contacts_host(self.h, ids.ctypes.data_as(_I32) if ids is not None else None, k, fptr(points),
-                                         fptr(force), count.ctypes.data_as(_I32)), "snk_contacts_host")
+        check(self.lib.snk_contacts_host(self.h, idp, k, fptr(points), fptr(force), count.ctypes.data_as(_I32)),
+              "snk_contacts_host")
         return points, force, count
 
     def contact_links(self):
@@ -711,16 +715,14 @@ class Stepper:
         """snk_render_host: images of the envs `env_ids` (None: all; ids may repeat, any order) from their current state.
         view / proj: column-major 16-vectors, one pair shared by every image or [n_images, 16] each.  Returns
         (rgba [k, height, width, 4] uint8, depth [k, height, width] float32 or None, seg int32 primitive ids or None)."""
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-        k = self.n_envs if ids is None else len(ids)
+        ids, k, idp = self._ids(env_ids)
         cams, shared = camera_block(view, proj, k)
         W, H = int(width), int(height)
         ok = 1 <= W <= 4096 and 1 <= H <= 4096 and k >= 1        # (the library refuses the rest by name; no huge buffers first)
         rgba = np.zeros((k, H, W, 4) if ok else (1,), np.uint8)
         dep = np.zeros((k, H, W), np.float32) if depth and ok else None
         sg = np.zeros((k, H, W), np.int32) if seg and ok else None
-        check(self.lib.snk_render_host(self.h, ids.ctypes.data_as(_I32) if ids is not None else None, k, fptr(cams),
-                                       1 if shared else 0, W, H, RENDER_SHADOW if shadow else 0,
+        check(self.lib.snk_render_host(self.h, idp, k, fptr(cams), 1 if shared else 0, W, H, RENDER_SHADOW if shadow else 0,
                                        rgba.ctypes.data_as(_U8), fptr(dep) if dep is not None else None,
                                        sg.ctypes.data_as(_I32) if sg is not None else None), "snk_render_host")
         return rgba, dep, sg

@@ -16,7 +16,7 @@
 
 #include "../../include/snk.h"
 #include "snk_device.hpp"
-#include "snk_render_view.hpp"
+#include "snk_seam.hpp"
 
 namespace {
 
@@ -104,9 +104,10 @@ int with_rules(int rules, F& fn) {
 template <class F>
 int dispatch(const snk_handle* h, F&& fn) {
     const int rules = snk::rules_variant(h->D);
-    if (h->n == 16) return h->v2 ? with_rules<16, true>(rules, fn) : with_rules<16, false>(rules, fn);
-    if (h->n == 32) return with_rules<32, false>(rules, fn);
-    return fail("unsupported n_modules (16 or 32)");
+    const int rc = snk::for_variant(h->n, h->v2, [&](auto n, auto v2) {
+        return with_rules<decltype(n)::value, decltype(v2)::value>(rules, fn);
+    });
+    return rc == snk::kUnsupported ? fail("unsupported n_modules (16 or 32)") : rc;
 }
 
 // floats per row of the trace buffer (snk_trace_row_floats): the payload [obs | link positions] in whole 128-byte lines
@@ -259,12 +260,6 @@ int enter(const snk_handle* h, unsigned what) {
     return (what & kAlive) ? check_alarm(h) : 0;
 }
 
-int check_launch() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
-    return 0;
-}
-
 // the launch of snk_step / snk_step_packed / snk_step_traced (trace != null), between a pair of snk_timing_enable's
 // events while the pool has one left
 int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done, int32_t* sub, int vec_mode, hipStream_t st,
@@ -280,7 +275,7 @@ int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done,
         HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used + 1], st));
         h->ev_used++;
     }
-    return check_launch();
+    return snk::launch_ok(nullptr);
 }
 
 // one obs_kernel pass over h's records, enqueued on st (snk_observe; the host read-outs below)
@@ -291,7 +286,7 @@ int launch_obs(snk_handle* h, float* obs, float* height, float* linkpos, hipStre
                            st, h->d_model, h->d_recs, obs, height, linkpos, h->n_envs);
         return 0;
     });
-    return (rc || check_launch()) ? 1 : 0;
+    return (rc || snk::launch_ok(nullptr)) ? 1 : 0;
 }
 // that pass (the device idle, the handle alive), and its one output copied to out
 int obs_pass(snk_handle* h, float* obs, float* height, float* linkpos, void* out, size_t bytes) {
@@ -397,7 +392,7 @@ std::unique_ptr<Models> models_of(const snk_params& p) {
 
 }  // namespace
 
-// the seam of the other objects (snk_render_view.hpp): their translation units see this much of a handle, and report
+// the seam of the other objects (snk_seam.hpp): their translation units see this much of a handle, and report
 // through g_err
 namespace snk {
 int api_fail(const char* msg) { return fail(msg); }
@@ -594,7 +589,7 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     if (init_sched(h) || upload_model(h)) return 1;
     // hard reset (snake.py:88-95)
     rc = dispatch(h, [&](auto k) { return launch_reset(k, h, nullptr, nullptr, 1, nullptr); });
-    if (rc || check_launch()) return 1;
+    if (rc || snk::launch_ok(nullptr)) return 1;
     HIP_TRY(hipDeviceSynchronize());
     return 0;
 }
@@ -686,7 +681,7 @@ int snk_reset(snk_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stre
     if (enter(h, kDev | kAlive)) return 1;
     hipStream_t st = (hipStream_t)stream;
     if (dispatch(h, [&](auto k) { return launch_reset(k, h, mask_dev, obs_dev, 0, st); })) return 1;
-    return check_launch();
+    return snk::launch_ok(nullptr);
 }
 
 int snk_step(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev,
@@ -818,7 +813,7 @@ int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* in
     if (enter(h, kDev | kAlive)) return 1;
     const size_t ne = (size_t)h->n_envs;
     HIP_TRY(hipMemcpy(h->d_tgt, targets, ne * h->n * sizeof(float), hipMemcpyHostToDevice));
-    if (dispatch(h, [&](auto v) { return launch_substep(v, h, h->d_tgt, k, h->d_info, nullptr, nullptr); }) || check_launch()) return 1;
+    if (dispatch(h, [&](auto v) { return launch_substep(v, h, h->d_tgt, k, h->d_info, nullptr, nullptr); }) || snk::launch_ok(nullptr)) return 1;
     HIP_TRY(hipDeviceSynchronize());
     if (info) HIP_TRY(hipMemcpy(info, h->d_info, ne * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return 0;
@@ -830,7 +825,7 @@ int snk_substep(snk_handle* h, const float* targets_dev, int32_t k, const uint8_
     if (enter(h, kDev | kAlive)) return 1;
     if (dispatch(h, [&](auto v) { return launch_substep(v, h, targets_dev, k, info_dev, active_dev, (hipStream_t)stream); }))
         return 1;
-    return check_launch();
+    return snk::launch_ok(nullptr);
 }
 
 int snk_observe(snk_handle* h, float* obs_dev, float* height_dev, float* linkpos_dev, void* stream) {
@@ -900,7 +895,7 @@ int snk_set_reset_pose_dev(snk_handle* h, const uint8_t* mask_dev, const float* 
             h->rows_of_substep = false;
             return 0;
         })) return 1;
-    return check_launch();
+    return snk::launch_ok(nullptr);
 }
 
 int32_t snk_manifold_floats(const snk_handle* h) { return (h && h->d_mf) ? 2 * h->n * 29 : 0; }
@@ -1090,7 +1085,7 @@ int snk_selftest(int32_t device) {
     float* d = nullptr;
     HIP_TRY(hipMalloc(&d, 136 * sizeof(float)));
     hipLaunchKernelGGL(snk::selftest_kernel, dim3(1), dim3(64), 0, nullptr, d);
-    if (check_launch()) return 1;
+    if (snk::launch_ok(nullptr)) return 1;
     float o[136];
     HIP_TRY(hipMemcpy(o, d, sizeof(o), hipMemcpyDeviceToHost));
     (void)hipFree(d);

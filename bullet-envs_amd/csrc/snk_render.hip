@@ -11,31 +11,23 @@
 
 #include "../../include/snk.h"
 #include "snk_render.hpp"
-#include "snk_render_view.hpp"
+#include "snk_seam.hpp"
 
 namespace {
 
-int rfail(const std::string& msg) { return snk::api_fail(msg.c_str()); }
+using snk::api_fail;
 
 // what both forms refuse before they look at the handle's state; `who` = the entry point's name
 int check_shape(const char* who, const snk_handle* h, int32_t n_images, int32_t width, int32_t height, int32_t flags) {
     const std::string w(who);
-    if (!h) return rfail(w + ": null handle (h)");
-    if (n_images < 1) return rfail(w + ": n_images must be at least 1");
-    if (width < 1 || width > 4096) return rfail(w + ": width must be in 1 .. 4096");
-    if (height < 1 || height > 4096) return rfail(w + ": height must be in 1 .. 4096");
+    if (!h) return api_fail(w + ": null handle (h)");
+    if (n_images < 1) return api_fail(w + ": n_images must be at least 1");
+    if (width < 1 || width > 4096) return api_fail(w + ": width must be in 1 .. 4096");
+    if (height < 1 || height > 4096) return api_fail(w + ": height must be in 1 .. 4096");
     if ((long long)n_images * width * height > 2147483647LL)
-        return rfail(w + ": n_images x width x height is more than 2^31 - 1 pixels");
-    if (flags & ~SNK_RENDER_SHADOW) return rfail(w + ": unknown bits in flags (SNK_RENDER_SHADOW is the only one)");
+        return api_fail(w + ": n_images x width x height is more than 2^31 - 1 pixels");
+    if (flags & ~SNK_RENDER_SHADOW) return api_fail(w + ": unknown bits in flags (SNK_RENDER_SHADOW is the only one)");
     return 0;
-}
-
-template <int N, bool V2>
-void launch_scene(const snk::RenderView& v, const int32_t* ids, const float* cams_in, int shared, float* prims, float* cams,
-                  int n_images, hipStream_t st) {
-    const int blocks = n_images < 65536 ? n_images : 65536;
-    hipLaunchKernelGGL((snk::render_scene_kernel<N, V2>), dim3(blocks), dim3(64), 0, st, v.d_model, v.d_recs, v.d_box, ids,
-                       cams_in, shared, prims, cams, n_images, v.n_envs);
 }
 
 }  // namespace
@@ -46,10 +38,10 @@ int snk_render(snk_handle* h, const int32_t* env_ids_dev, int32_t n_images, cons
                int32_t width, int32_t height, int32_t flags, uint8_t* rgba_dev, float* depth_dev, int32_t* seg_dev,
                void* stream) {
     if (check_shape("snk_render", h, n_images, width, height, flags)) return 1;
-    if (!rgba_dev) return rfail("snk_render: null rgba_dev");
-    if (!cameras_dev) return rfail("snk_render: null cameras_dev");
+    if (!rgba_dev) return api_fail("snk_render: null rgba_dev");
+    if (!cameras_dev) return api_fail("snk_render: null cameras_dev");
     if (reinterpret_cast<uintptr_t>(rgba_dev) % 4 != 0)
-        return rfail("snk_render: rgba_dev must be 4-byte aligned (a pixel is one 32-bit store)");
+        return api_fail("snk_render: rgba_dev must be 4-byte aligned (a pixel is one 32-bit store)");
     snk::RenderView v;
     if (snk::render_view(h, false, &v)) return 1;
     const size_t pf = (size_t)snk::prim_stride(v.n), need = (size_t)n_images * (pf + snk::kCamFloats) * sizeof(float);
@@ -58,77 +50,53 @@ int snk_render(snk_handle* h, const int32_t* env_ids_dev, int32_t n_images, cons
     float* cams = prims + (size_t)n_images * pf;
     hipStream_t st = (hipStream_t)stream;
     const int shared = shared_camera ? 1 : 0;
-    if (v.n == 16 && v.v2) launch_scene<16, true>(v, env_ids_dev, cameras_dev, shared, prims, cams, n_images, st);
-    else if (v.n == 16) launch_scene<16, false>(v, env_ids_dev, cameras_dev, shared, prims, cams, n_images, st);
-    else if (v.n == 32) launch_scene<32, false>(v, env_ids_dev, cameras_dev, shared, prims, cams, n_images, st);
-    else return rfail("snk_render: unsupported n_modules (16 or 32)");
+    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+        hipLaunchKernelGGL((snk::render_scene_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_images)),
+                           dim3(64), 0, st, v.d_model, v.d_recs, v.d_box, env_ids_dev, cameras_dev, shared, prims, cams, n_images,
+                           v.n_envs);
+        return 0;
+    });
+    if (rc == snk::kUnsupported) return api_fail("snk_render: unsupported n_modules (16 or 32)");
     const int tx = (width + snk::kRenderTile - 1) / snk::kRenderTile, ty = (height + snk::kRenderTile - 1) / snk::kRenderTile;
     const long long work = (long long)n_images * tx * ty;
     const unsigned blocks = (unsigned)(work < (1LL << 20) ? work : (1LL << 20));
     hipLaunchKernelGGL(snk::render_rays_kernel, dim3(blocks), dim3(256), 0, st, prims, cams, 2 * v.n, width, height, tx, ty, work,
                        flags, reinterpret_cast<uint32_t*>(rgba_dev), depth_dev, seg_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rfail(std::string("snk_render: kernel launch: ") + hipGetErrorString(e));
-    return 0;
+    return snk::launch_ok("snk_render");
 }
 
 int snk_render_host(snk_handle* h, const int32_t* env_ids, int32_t n_images, const float* cameras, int32_t shared_camera,
                     int32_t width, int32_t height, int32_t flags, uint8_t* rgba, float* depth, int32_t* seg) {
     if (check_shape("snk_render_host", h, n_images, width, height, flags)) return 1;
-    if (!rgba) return rfail("snk_render_host: null rgba");
-    if (!cameras) return rfail("snk_render_host: null cameras");
+    if (!rgba) return api_fail("snk_render_host: null rgba");
+    if (!cameras) return api_fail("snk_render_host: null cameras");
     snk::RenderView v;
     if (snk::render_view(h, true, &v)) return 1;
-    char msg[160];
-    if (env_ids)
-        for (int k = 0; k < n_images; k++)
-            if (env_ids[k] < 0 || env_ids[k] >= v.n_envs) {
-                snprintf(msg, sizeof(msg), "snk_render_host: env_ids[%d] = %d is outside 0 .. %d", k, (int)env_ids[k], v.n_envs - 1);
-                return rfail(msg);
-            }
-    if (!env_ids && n_images > v.n_envs) {
-        snprintf(msg, sizeof(msg), "snk_render_host: n_images %d without env_ids is more than the handle's %d envs", (int)n_images, v.n_envs);
-        return rfail(msg);
-    }
+    if (env_ids ? snk::check_env_ids("snk_render_host", "env_ids", env_ids, n_images, v.n_envs)
+                : snk::check_count_without_ids("snk_render_host", "n_images", n_images, v.n_envs)) return 1;
     const size_t ncam = shared_camera ? 1 : (size_t)n_images;
     for (size_t k = 0; k < ncam * 32; k++)
         if (!std::isfinite(cameras[k])) {
+            char msg[160];
             snprintf(msg, sizeof(msg), "snk_render_host: cameras[%zu][%zu] is not finite", k / 32, k % 32);
-            return rfail(msg);
+            return api_fail(msg);
         }
     const size_t px = (size_t)n_images * width * height;
-    int32_t* d_ids = nullptr;
-    float* d_cam = nullptr;
-    uint8_t* d_rgba = nullptr;
-    float* d_depth = nullptr;
-    int32_t* d_seg = nullptr;
-    int rc = 1;
-    do {
-        if (env_ids && (hipMalloc(&d_ids, (size_t)n_images * 4) != hipSuccess ||
-                        hipMemcpy(d_ids, env_ids, (size_t)n_images * 4, hipMemcpyHostToDevice) != hipSuccess)) break;
-        if (hipMalloc(&d_cam, ncam * 32 * 4) != hipSuccess ||
-            hipMemcpy(d_cam, cameras, ncam * 32 * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMalloc(&d_rgba, px * 4) != hipSuccess) break;
-        if (depth && hipMalloc(&d_depth, px * 4) != hipSuccess) break;
-        if (seg && hipMalloc(&d_seg, px * 4) != hipSuccess) break;
-        rc = 2;
-        if (snk_render(h, d_ids, n_images, d_cam, shared_camera, width, height, flags, d_rgba, d_depth, d_seg, nullptr)) break;
-        rc = 1;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(rgba, d_rgba, px * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (depth && hipMemcpy(depth, d_depth, px * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (seg && hipMemcpy(seg, d_seg, px * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    (void)hipFree(d_ids); (void)hipFree(d_cam); (void)hipFree(d_rgba); (void)hipFree(d_depth); (void)hipFree(d_seg);
-    if (rc == 1) return rfail(std::string("snk_render_host: ") + hipGetErrorString(hipGetLastError()));
-    return rc ? 1 : 0;
+    snk::HostCall c;
+    const int32_t* d_ids = c.in(env_ids, (size_t)n_images * 4);
+    const float* d_cam = c.in(cameras, ncam * 32 * 4);
+    uint8_t* d_rgba = c.out(rgba, px * 4);
+    float* d_depth = c.out(depth, px * 4);
+    int32_t* d_seg = c.out(seg, px * 4);
+    if (c.ok() && snk_render(h, d_ids, n_images, d_cam, shared_camera, width, height, flags, d_rgba, d_depth, d_seg, nullptr))
+        return 1;
+    return c.finish("snk_render_host");
 }
 
 int snk_view_matrix_ypr(const float target[3], float distance, float yaw_deg, float pitch_deg, float roll_deg, int32_t up_axis,
                         float out[16]) {
-    if (!target || !out) return rfail("snk_view_matrix_ypr: null argument");
-    if (up_axis != 1 && up_axis != 2) return rfail("snk_view_matrix_ypr: up_axis must be 1 (y) or 2 (z)");
+    if (!target || !out) return api_fail("snk_view_matrix_ypr: null argument");
+    if (up_axis != 1 && up_axis != 2) return api_fail("snk_view_matrix_ypr: up_axis must be 1 (y) or 2 (z)");
     (void)roll_deg;      // [U] b3ComputeViewMatrixFromYawPitchRoll sets its rollRad to 0: the argument is not used
     const double rad = 0.01745329251994329547;
     const double yaw = yaw_deg * rad, pitch = pitch_deg * rad;
@@ -166,7 +134,7 @@ int snk_view_matrix_ypr(const float target[3], float distance, float yaw_deg, fl
 }
 
 int snk_projection_fov(float fov_deg, float aspect, float near_val, float far_val, float out[16]) {
-    if (!out) return rfail("snk_projection_fov: null argument");
+    if (!out) return api_fail("snk_projection_fov: null argument");
     // [U] b3ComputeProjectionMatrixFOV.  far == near (the reference's own call, snake.py:317-320) divides by zero: the
     // entries come out infinite, as the formula gives them; nothing is refused here
     const double ys = 1.0 / tan((3.141592538 / 180.0) * (double)fov_deg / 2.0), xs = ys / (double)aspect;

@@ -10,34 +10,13 @@
 #include <vector>
 
 #include "../../include/snk.h"
-#include "snk_render_view.hpp"
+#include "snk_seam.hpp"
 #include "snk_world.hpp"
 
 namespace {
 
-int wfail(const std::string& msg) { return snk::api_fail(msg.c_str()); }
-
-int launched(const char* who) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return wfail(std::string(who) + ": kernel launch: " + hipGetErrorString(e));
-    return 0;
-}
-
-template <int N, bool V2>
-void launch_links(const snk::WorldView& v, const int32_t* ids, int n_rows, float* out, hipStream_t st) {
-    const int blocks = n_rows < 65536 ? n_rows : 65536;
-    hipLaunchKernelGGL((snk::link_state_kernel<N, V2>), dim3(blocks), dim3(64), 0, st, v.d_model, v.d_recs, v.d_links, ids, out,
-                       n_rows, v.n_envs);
-}
-
-template <int N, bool V2>
-void launch_contacts(const snk::WorldView& v, const int32_t* ids, int n_rows, float* points, float* force, int32_t* count,
-                     hipStream_t st) {
-    const int blocks = n_rows < 65536 ? n_rows : 65536;
-    hipLaunchKernelGGL((snk::contacts_kernel<N, V2>), dim3(blocks), dim3(64), 0, st, v.d_model, v.d_recs,
-                       v.tables[snk::WorldView::kManifolds].d, v.tables[snk::WorldView::kBox].d, ids, points, force, count,
-                       n_rows, v.n_envs);
-}
+using snk::api_fail;
+using snk::launch_ok;
 
 // contact slots of a viewed handle (snk_contact_slots); 0: no contact cache
 int contact_slots(const snk::WorldView& v) {
@@ -45,83 +24,50 @@ int contact_slots(const snk::WorldView& v) {
     return 4 * 2 * v.n + (v.tables[snk::WorldView::kBox].d ? 4 : 0);
 }
 
-// a host id list against the handle: the first index whose id is outside 0 .. n_envs - 1, or -1
-int bad_id(const int32_t* ids, int n, int n_envs) {
-    for (int k = 0; k < n; k++)
-        if (ids[k] < 0 || ids[k] >= n_envs) return k;
-    return -1;
-}
-
-// device copies of host arrays for the host forms, freed on every way out
-struct Staged {
-    std::vector<void*> p;
-    ~Staged() { for (void* q : p) (void)hipFree(q); }
-    void* up(const void* host, size_t bytes) {      // null when it cannot be had
-        void* d = nullptr;
-        if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-        p.push_back(d);
-        if (host && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return d;
-    }
-};
-
 }  // namespace
 
 extern "C" {
 
 int32_t snk_link_state_rows(const snk_handle* h) {
-    if (!h) { wfail("snk_link_state_rows: null handle"); return 0; }
+    if (!h) { api_fail("snk_link_state_rows: null handle"); return 0; }
     return snk_obs_dim(h) - 6;      // obs_dim = 3n + 8 (snake.py:163-164); the tree has 3n + 2 links
 }
 
 int snk_link_states(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float* out_dev, void* stream) {
-    if (!h) return wfail("snk_link_states: null handle (h)");
-    if (n_rows < 1) return wfail("snk_link_states: n_rows must be at least 1");
-    if (!out_dev) return wfail("snk_link_states: null out_dev");
+    if (!h) return api_fail("snk_link_states: null handle (h)");
+    if (n_rows < 1) return api_fail("snk_link_states: n_rows must be at least 1");
+    if (!out_dev) return api_fail("snk_link_states: null out_dev");
     if (reinterpret_cast<uintptr_t>(out_dev) % 16 != 0)
-        return wfail("snk_link_states: out_dev must be 16-byte aligned (the rows leave as 16-byte stores)");
+        return api_fail("snk_link_states: out_dev must be 16-byte aligned (the rows leave as 16-byte stores)");
     snk::WorldView v;
     if (snk::world_view(h, false, &v)) return 1;
-    hipStream_t st = (hipStream_t)stream;
-    if (v.n == 16 && v.v2) launch_links<16, true>(v, env_ids_dev, n_rows, out_dev, st);
-    else if (v.n == 16) launch_links<16, false>(v, env_ids_dev, n_rows, out_dev, st);
-    else if (v.n == 32) launch_links<32, false>(v, env_ids_dev, n_rows, out_dev, st);
-    else return wfail("snk_link_states: unsupported n_modules (16 or 32)");
-    return launched("snk_link_states");
+    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+        hipLaunchKernelGGL((snk::link_state_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64),
+                           0, (hipStream_t)stream, v.d_model, v.d_recs, v.d_links, env_ids_dev, out_dev, n_rows, v.n_envs);
+        return 0;
+    });
+    if (rc == snk::kUnsupported) return api_fail("snk_link_states: unsupported n_modules (16 or 32)");
+    return launch_ok("snk_link_states");
 }
 
 int snk_link_states_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* out) {
-    if (!h) return wfail("snk_link_states_host: null handle (h)");
-    if (n_rows < 1) return wfail("snk_link_states_host: n_rows must be at least 1");
-    if (!out) return wfail("snk_link_states_host: null out");
+    if (!h) return api_fail("snk_link_states_host: null handle (h)");
+    if (n_rows < 1) return api_fail("snk_link_states_host: n_rows must be at least 1");
+    if (!out) return api_fail("snk_link_states_host: null out");
     snk::WorldView v;
     if (snk::world_view(h, true, &v)) return 1;
-    char msg[160];
-    const int bad = env_ids ? bad_id(env_ids, n_rows, v.n_envs) : -1;
-    if (bad >= 0) {
-        snprintf(msg, sizeof(msg), "snk_link_states_host: env_ids[%d] = %d is outside 0 .. %d", bad, (int)env_ids[bad], v.n_envs - 1);
-        return wfail(msg);
-    }
-    if (!env_ids && n_rows > v.n_envs) {
-        snprintf(msg, sizeof(msg), "snk_link_states_host: n_rows %d without env_ids is more than the handle's %d envs", (int)n_rows,
-                 v.n_envs);
-        return wfail(msg);
-    }
-    const size_t bytes = (size_t)n_rows * snk::link_rows(v.n) * snk::kLinkStateFloats * sizeof(float);
-    Staged s;
-    int32_t* d_ids = env_ids ? static_cast<int32_t*>(s.up(env_ids, (size_t)n_rows * sizeof(int32_t))) : nullptr;
-    float* d_out = static_cast<float*>(s.up(nullptr, bytes));
-    if ((env_ids && !d_ids) || !d_out)
-        return wfail(std::string("snk_link_states_host: ") + hipGetErrorString(hipGetLastError()));
-    if (snk_link_states(h, d_ids, n_rows, d_out, nullptr)) return 1;
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return wfail(std::string("snk_link_states_host: ") + hipGetErrorString(hipGetLastError()));
-    return 0;
+    if (env_ids ? snk::check_env_ids("snk_link_states_host", "env_ids", env_ids, n_rows, v.n_envs)
+                : snk::check_count_without_ids("snk_link_states_host", "n_rows", n_rows, v.n_envs)) return 1;
+    snk::HostCall c;
+    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    float* d_out = c.out(out, (size_t)n_rows * snk::link_rows(v.n) * snk::kLinkStateFloats * sizeof(float));
+    if (c.ok() && snk_link_states(h, d_ids, n_rows, d_out, nullptr)) return 1;
+    return c.finish("snk_link_states_host");
 }
 
 int snk_link_inertial_offsets(const snk_params* p, double* out) {
-    if (!p || !out) return wfail("snk_link_inertial_offsets: null argument");
-    if (p->n_modules != 16 && p->n_modules != 32) return wfail("snk_link_inertial_offsets: n_modules must be 16 or 32");
+    if (!p || !out) return api_fail("snk_link_inertial_offsets: null argument");
+    if (p->n_modules != 16 && p->n_modules != 32) return api_fail("snk_link_inertial_offsets: n_modules must be 16 or 32");
     std::unique_ptr<snk::HostModel> H(new snk::HostModel);      // (the model is large: on the heap)
     snk::build_host_model(*p, *H);
     for (int r = 0; r < snk::link_rows(H->n); r++)
@@ -130,71 +76,56 @@ int snk_link_inertial_offsets(const snk_params* p, double* out) {
 }
 
 int32_t snk_contact_slots(const snk_handle* h) {
-    if (!h) { wfail("snk_contact_slots: null handle"); return 0; }
+    if (!h) { api_fail("snk_contact_slots: null handle"); return 0; }
     snk::WorldView v;
     if (snk::world_view(const_cast<snk_handle*>(h), false, &v)) return 0;
     const int slots = contact_slots(v);
-    if (!slots) wfail("snk_contact_slots: this handle has contact_model 0 (no contact cache)");
+    if (!slots) api_fail("snk_contact_slots: this handle has contact_model 0 (no contact cache)");
     return slots;
 }
 
 int snk_contacts(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float* points_dev, float* force_dev,
                  int32_t* count_dev, void* stream) {
-    if (!h) return wfail("snk_contacts: null handle (h)");
-    if (n_rows < 1) return wfail("snk_contacts: n_rows must be at least 1");
-    if (!points_dev && !force_dev && !count_dev) return wfail("snk_contacts: points_dev, force_dev and count_dev are all null");
+    if (!h) return api_fail("snk_contacts: null handle (h)");
+    if (n_rows < 1) return api_fail("snk_contacts: n_rows must be at least 1");
+    if (!points_dev && !force_dev && !count_dev) return api_fail("snk_contacts: points_dev, force_dev and count_dev are all null");
     if (reinterpret_cast<uintptr_t>(points_dev) % 16 != 0)
-        return wfail("snk_contacts: points_dev must be 16-byte aligned (the records leave as 16-byte stores)");
+        return api_fail("snk_contacts: points_dev must be 16-byte aligned (the records leave as 16-byte stores)");
     snk::WorldView v;
     if (snk::world_view(h, false, &v)) return 1;
-    if (!contact_slots(v)) return wfail("snk_contacts: this handle has contact_model 0 (no contact cache)");
-    hipStream_t st = (hipStream_t)stream;
-    if (v.n == 16 && v.v2) launch_contacts<16, true>(v, env_ids_dev, n_rows, points_dev, force_dev, count_dev, st);
-    else if (v.n == 16) launch_contacts<16, false>(v, env_ids_dev, n_rows, points_dev, force_dev, count_dev, st);
-    else if (v.n == 32) launch_contacts<32, false>(v, env_ids_dev, n_rows, points_dev, force_dev, count_dev, st);
-    else return wfail("snk_contacts: unsupported n_modules (16 or 32)");
-    return launched("snk_contacts");
+    if (!contact_slots(v)) return api_fail("snk_contacts: this handle has contact_model 0 (no contact cache)");
+    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+        hipLaunchKernelGGL((snk::contacts_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64), 0,
+                           (hipStream_t)stream, v.d_model, v.d_recs, v.tables[snk::WorldView::kManifolds].d,
+                           v.tables[snk::WorldView::kBox].d, env_ids_dev, points_dev, force_dev, count_dev, n_rows, v.n_envs);
+        return 0;
+    });
+    if (rc == snk::kUnsupported) return api_fail("snk_contacts: unsupported n_modules (16 or 32)");
+    return launch_ok("snk_contacts");
 }
 
 int snk_contacts_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* points, float* force, int32_t* count) {
-    if (!h) return wfail("snk_contacts_host: null handle (h)");
-    if (n_rows < 1) return wfail("snk_contacts_host: n_rows must be at least 1");
-    if (!points && !force && !count) return wfail("snk_contacts_host: points, force and count are all null");
+    if (!h) return api_fail("snk_contacts_host: null handle (h)");
+    if (n_rows < 1) return api_fail("snk_contacts_host: n_rows must be at least 1");
+    if (!points && !force && !count) return api_fail("snk_contacts_host: points, force and count are all null");
     snk::WorldView v;
     if (snk::world_view(h, true, &v)) return 1;
     const int slots = contact_slots(v);
-    if (!slots) return wfail("snk_contacts_host: this handle has contact_model 0 (no contact cache)");
-    char msg[160];
-    const int bad = env_ids ? bad_id(env_ids, n_rows, v.n_envs) : -1;
-    if (bad >= 0) {
-        snprintf(msg, sizeof(msg), "snk_contacts_host: env_ids[%d] = %d is outside 0 .. %d", bad, (int)env_ids[bad], v.n_envs - 1);
-        return wfail(msg);
-    }
-    if (!env_ids && n_rows > v.n_envs) {
-        snprintf(msg, sizeof(msg), "snk_contacts_host: n_rows %d without env_ids is more than the handle's %d envs", (int)n_rows,
-                 v.n_envs);
-        return wfail(msg);
-    }
-    const size_t pb = (size_t)n_rows * slots * snk::kContactFloats * sizeof(float);
-    const size_t fb = (size_t)n_rows * (2 * v.n + 1) * sizeof(float), cb = (size_t)n_rows * sizeof(int32_t);
-    Staged s;
-    int32_t* d_ids = env_ids ? static_cast<int32_t*>(s.up(env_ids, (size_t)n_rows * sizeof(int32_t))) : nullptr;
-    float* d_pts = points ? static_cast<float*>(s.up(nullptr, pb)) : nullptr;
-    float* d_force = force ? static_cast<float*>(s.up(nullptr, fb)) : nullptr;
-    int32_t* d_count = count ? static_cast<int32_t*>(s.up(nullptr, cb)) : nullptr;
-    if ((env_ids && !d_ids) || (points && !d_pts) || (force && !d_force) || (count && !d_count))
-        return wfail(std::string("snk_contacts_host: ") + hipGetErrorString(hipGetLastError()));
-    if (snk_contacts(h, d_ids, n_rows, d_pts, d_force, d_count, nullptr)) return 1;
-    if (hipDeviceSynchronize() != hipSuccess || (points && hipMemcpy(points, d_pts, pb, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (force && hipMemcpy(force, d_force, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (count && hipMemcpy(count, d_count, cb, hipMemcpyDeviceToHost) != hipSuccess))
-        return wfail(std::string("snk_contacts_host: ") + hipGetErrorString(hipGetLastError()));
-    return 0;
+    if (!slots) return api_fail("snk_contacts_host: this handle has contact_model 0 (no contact cache)");
+    if (env_ids ? snk::check_env_ids("snk_contacts_host", "env_ids", env_ids, n_rows, v.n_envs)
+                : snk::check_count_without_ids("snk_contacts_host", "n_rows", n_rows, v.n_envs)) return 1;
+    snk::HostCall c;
+    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    float* d_pts = c.out(points, (size_t)n_rows * slots * snk::kContactFloats * sizeof(float));
+    float* d_force = c.out(force, (size_t)n_rows * (2 * v.n + 1) * sizeof(float));
+    int32_t* d_count = c.out(count, (size_t)n_rows * sizeof(int32_t));
+    if (c.ok() && snk_contacts(h, d_ids, n_rows, d_pts, d_force, d_count, nullptr)) return 1;
+    return c.finish("snk_contacts_host");
 }
 
 int snk_contact_links(const snk_params* p, int32_t* out) {
-    if (!p || !out) return wfail("snk_contact_links: null argument");
-    if (p->n_modules != 16 && p->n_modules != 32) return wfail("snk_contact_links: n_modules must be 16 or 32");
+    if (!p || !out) return api_fail("snk_contact_links: null argument");
+    if (p->n_modules != 16 && p->n_modules != 32) return api_fail("snk_contact_links: n_modules must be 16 or 32");
     // cylinder c is the collider of INPUT_INTERFACE_k (even c = 2k - 2: Bullet link 3k - 2) or of OUTPUT_BODY_k (odd c =
     // 2k - 1: link 3k) -- build_host_model's cylinder loop, in the link numbering of its link table (row = link + 1)
     for (int c = 0; c < 2 * p->n_modules; c++) out[c] = (c & 1) ? 3 * ((c + 1) / 2) : 3 * (c / 2) + 1;
@@ -203,10 +134,10 @@ int snk_contact_links(const snk_params* p, int32_t* out) {
 
 int snk_copy_envs(snk_handle* h, const int32_t* src_ids_dev, const int32_t* dst_ids_dev, int32_t n_pairs, int32_t flags,
                   void* stream) {
-    if (!h) return wfail("snk_copy_envs: null handle (h)");
-    if (!src_ids_dev || !dst_ids_dev) return wfail("snk_copy_envs: null id list");
-    if (n_pairs < 1) return wfail("snk_copy_envs: n_pairs must be at least 1");
-    if (flags & ~SNK_COPY_RESET_POSE) return wfail("snk_copy_envs: unknown bits in flags (SNK_COPY_RESET_POSE is the only one)");
+    if (!h) return api_fail("snk_copy_envs: null handle (h)");
+    if (!src_ids_dev || !dst_ids_dev) return api_fail("snk_copy_envs: null id list");
+    if (n_pairs < 1) return api_fail("snk_copy_envs: n_pairs must be at least 1");
+    if (flags & ~SNK_COPY_RESET_POSE) return api_fail("snk_copy_envs: unknown bits in flags (SNK_COPY_RESET_POSE is the only one)");
     snk::WorldView v;
     if (snk::world_view(h, false, &v)) return 1;
     static_assert((int)snk::WorldView::kTables == snk::kCopyTables, "one slot of the copy per table of the view");
@@ -216,32 +147,23 @@ int snk_copy_envs(snk_handle* h, const int32_t* src_ids_dev, const int32_t* dst_
         a.d[t] = take ? v.tables[t].d : nullptr;
         a.floats[t] = (int)v.tables[t].floats;
     }
-    const int blocks = n_pairs < 65536 ? n_pairs : 65536;
-    hipLaunchKernelGGL(snk::copy_envs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, src_ids_dev, dst_ids_dev,
+    hipLaunchKernelGGL(snk::copy_envs_kernel, dim3(snk::grid_for(n_pairs)), dim3(256), 0, (hipStream_t)stream, a, src_ids_dev, dst_ids_dev,
                        n_pairs, v.n_envs);
-    return launched("snk_copy_envs");
+    return launch_ok("snk_copy_envs");
 }
 
 int snk_copy_envs_host(snk_handle* h, const int32_t* src_ids, const int32_t* dst_ids, int32_t n_pairs, int32_t flags) {
-    if (!h) return wfail("snk_copy_envs_host: null handle (h)");
-    if (!src_ids || !dst_ids) return wfail("snk_copy_envs_host: null id list");
-    if (n_pairs < 1) return wfail("snk_copy_envs_host: n_pairs must be at least 1");
+    if (!h) return api_fail("snk_copy_envs_host: null handle (h)");
+    if (!src_ids || !dst_ids) return api_fail("snk_copy_envs_host: null id list");
+    if (n_pairs < 1) return api_fail("snk_copy_envs_host: n_pairs must be at least 1");
     if (flags & ~SNK_COPY_RESET_POSE)
-        return wfail("snk_copy_envs_host: unknown bits in flags (SNK_COPY_RESET_POSE is the only one)");
+        return api_fail("snk_copy_envs_host: unknown bits in flags (SNK_COPY_RESET_POSE is the only one)");
     snk::WorldView v;
     if (snk::world_view(h, true, &v)) return 1;
     // validated before anything is written: a refused call leaves every table as it was
     char msg[200];
-    int bad = bad_id(src_ids, n_pairs, v.n_envs);
-    if (bad >= 0) {
-        snprintf(msg, sizeof(msg), "snk_copy_envs_host: src_ids[%d] = %d is outside 0 .. %d", bad, (int)src_ids[bad], v.n_envs - 1);
-        return wfail(msg);
-    }
-    bad = bad_id(dst_ids, n_pairs, v.n_envs);
-    if (bad >= 0) {
-        snprintf(msg, sizeof(msg), "snk_copy_envs_host: dst_ids[%d] = %d is outside 0 .. %d", bad, (int)dst_ids[bad], v.n_envs - 1);
-        return wfail(msg);
-    }
+    if (snk::check_env_ids("snk_copy_envs_host", "src_ids", src_ids, n_pairs, v.n_envs) ||
+        snk::check_env_ids("snk_copy_envs_host", "dst_ids", dst_ids, n_pairs, v.n_envs)) return 1;
     std::vector<int> as_dst(v.n_envs, -1), as_src(v.n_envs, -1);      // the first index at which an env is named
     for (int k = 0; k < n_pairs; k++)
         if (as_src[src_ids[k]] < 0) as_src[src_ids[k]] = k;
@@ -250,24 +172,20 @@ int snk_copy_envs_host(snk_handle* h, const int32_t* src_ids, const int32_t* dst
         if (as_dst[d] >= 0) {
             snprintf(msg, sizeof(msg), "snk_copy_envs_host: dst_ids[%d] = %d repeats dst_ids[%d] (the destinations must be distinct)",
                      k, d, as_dst[d]);
-            return wfail(msg);
+            return api_fail(msg);
         }
         as_dst[d] = k;
         if (as_src[d] >= 0) {
             snprintf(msg, sizeof(msg), "snk_copy_envs_host: dst_ids[%d] = %d is also src_ids[%d] (no env may be both a source and a "
                      "destination)", k, d, as_src[d]);
-            return wfail(msg);
+            return api_fail(msg);
         }
     }
-    Staged s;
-    const size_t bytes = (size_t)n_pairs * sizeof(int32_t);
-    int32_t* d_src = static_cast<int32_t*>(s.up(src_ids, bytes));
-    int32_t* d_dst = static_cast<int32_t*>(s.up(dst_ids, bytes));
-    if (!d_src || !d_dst) return wfail(std::string("snk_copy_envs_host: ") + hipGetErrorString(hipGetLastError()));
-    if (snk_copy_envs(h, d_src, d_dst, n_pairs, flags, nullptr)) return 1;
-    if (hipDeviceSynchronize() != hipSuccess)
-        return wfail(std::string("snk_copy_envs_host: ") + hipGetErrorString(hipGetLastError()));
-    return 0;
+    snk::HostCall c;
+    const int32_t* d_src = c.in(src_ids, (size_t)n_pairs * sizeof(int32_t));
+    const int32_t* d_dst = c.in(dst_ids, (size_t)n_pairs * sizeof(int32_t));
+    if (c.ok() && snk_copy_envs(h, d_src, d_dst, n_pairs, flags, nullptr)) return 1;
+    return c.finish("snk_copy_envs_host");
 }
 
 }  // extern "C"

@@ -23,7 +23,52 @@ from . import _lib
 from .snake_env import FrozenInfo, params_from_args
 
 
-class DeviceVecEnv(object):
+class _TensorArgs(object):
+    """What DeviceVecEnv and DeviceWorld share: the current stream, and a caller's tensors as the kernels take them
+    (self.torch, self.device and self.num_envs are the subclass's)."""
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _arg(self, x, what, dtypes, shape):
+        """a caller's tensor as the kernels read it: on this device, of one of `dtypes`, of `shape`, contiguous"""
+        t = self.torch
+        if not isinstance(x, t.Tensor) or not x.is_cuda or x.device != self.device:
+            raise ValueError("%s must be a CUDA tensor on %s" % (what, self.device))
+        if x.dtype not in dtypes:
+            raise ValueError("%s must be %s, got %s" % (what, " or ".join(str(d) for d in dtypes), x.dtype))
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError("%s must have shape %s, got %s" % (what, tuple(shape), tuple(x.shape)))
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % what)
+        return x
+
+    def _out(self, out, what, shape, dtype=None):
+        t = self.torch
+        dtype = t.float32 if dtype is None else dtype
+        if out is None:
+            return t.empty(shape, dtype=dtype, device=self.device)
+        return self._arg(out, what, (dtype,), shape)
+
+    def _keep(self, *tensors):
+        """the kernels read these when the stream gets there: they stay alive until then"""
+        cur = self.torch.cuda.current_stream(self.device)
+        for x in tensors:
+            if x is not None:
+                x.record_stream(cur)
+
+    def _ids(self, env_ids, empty_ok=False):
+        """(int32 tensor on this device or None, how many envs it names) of an `env_ids` argument (None: all envs)"""
+        if env_ids is None:
+            return None, self.num_envs
+        t = self.torch
+        ids = t.as_tensor(env_ids, dtype=t.int32, device=self.device).reshape(-1).contiguous()
+        if ids.numel() < 1 and not empty_ok:
+            raise ValueError("env_ids must name at least one env")
+        return ids, int(ids.numel())
+
+
+class DeviceVecEnv(_TensorArgs):
     def __init__(self, num_envs, device_index=0, args=None, n_modules=16, params=None, **over):
         import torch
         self.torch = torch
@@ -39,9 +84,6 @@ class DeviceVecEnv(object):
         self.rew = torch.zeros((E,), dtype=torch.float32, device=self.device)
         self.done = torch.zeros((E,), dtype=torch.uint8, device=self.device)
         self.substeps = torch.zeros((E,), dtype=torch.int32, device=self.device)
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
 
     def reset(self):
         self.stepper.reset_device(0, self.obs.data_ptr(), self._stream())
@@ -116,11 +158,7 @@ class DeviceVecEnv(object):
         Returns CUDA tensors (rgba [k, height, width, 4] uint8, depth [k, height, width] float32 or None, seg int32
         primitive ids or None: 0 ground, 1 + c cylinder c, 1 + 2n box, -1 background)."""
         t = self.torch
-        if env_ids is None:
-            ids, k = None, self.num_envs
-        else:
-            ids = t.as_tensor(env_ids, dtype=t.int32, device=self.device).reshape(-1).contiguous()
-            k = int(ids.numel())
+        ids, k = self._ids(env_ids, empty_ok=True)          # (the library refuses an empty list, naming the argument)
         if view is None or proj is None:
             dv, dp = _lib.default_camera(width, height)
             view, proj = (dv if view is None else view), (dp if proj is None else proj)
@@ -139,11 +177,7 @@ class DeviceVecEnv(object):
                                    _lib.RENDER_SHADOW if shadow else 0, rgba.data_ptr(),
                                    dep.data_ptr() if dep is not None else 0, sg.data_ptr() if sg is not None else 0,
                                    self._stream())
-        # the kernels read ids / cams when the stream gets there: they stay alive until then
-        cur = t.cuda.current_stream(self.device)
-        cams.record_stream(cur)
-        if ids is not None:
-            ids.record_stream(cur)
+        self._keep(ids, cams)
         return rgba, dep, sg
 
     def set_reset_pose(self, pose, mask=None):
@@ -195,7 +229,7 @@ class DeviceVecEnv(object):
         self.stepper.close()
 
 
-class DeviceWorld(object):
+class DeviceWorld(_TensorArgs):
     """The simulator without a task, on torch CUDA tensors: what pybullet.stepSimulation, getLinkState and
     saveState / restoreState are to a script (snake.py:219-221, 286, 138-156), for every env of a handle at once.  Every
     call is one launch on torch's current stream, ordered with what is enqueued there (a DeviceVecEnv.step or render on
@@ -221,36 +255,6 @@ class DeviceWorld(object):
         self.n = stepper.n
         self.obs_dim = stepper.obs_dim
         self.link_rows = 3 * self.n + 2
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
-
-    def _arg(self, x, what, dtypes, shape):
-        """a caller's tensor as the kernels read it: on this device, of one of `dtypes`, of `shape`, contiguous"""
-        t = self.torch
-        if not isinstance(x, t.Tensor) or not x.is_cuda or x.device != self.device:
-            raise ValueError("%s must be a CUDA tensor on %s" % (what, self.device))
-        if x.dtype not in dtypes:
-            raise ValueError("%s must be %s, got %s" % (what, " or ".join(str(d) for d in dtypes), x.dtype))
-        if tuple(x.shape) != tuple(shape):
-            raise ValueError("%s must have shape %s, got %s" % (what, tuple(shape), tuple(x.shape)))
-        if not x.is_contiguous():
-            raise ValueError("%s must be contiguous" % what)
-        return x
-
-    def _out(self, out, what, shape, dtype=None):
-        t = self.torch
-        dtype = t.float32 if dtype is None else dtype
-        if out is None:
-            return t.empty(shape, dtype=dtype, device=self.device)
-        return self._arg(out, what, (dtype,), shape)
-
-    def _keep(self, *tensors):
-        """the kernels read these when the stream gets there: they stay alive until then"""
-        cur = self.torch.cuda.current_stream(self.device)
-        for x in tensors:
-            if x is not None:
-                x.record_stream(cur)
 
     def step_simulation(self, targets, k=1, active=None, info=None):
         """k physics substeps towards the joint targets [E, n] float32 (radians): setJointMotorControlArray +
@@ -292,14 +296,7 @@ class DeviceWorld(object):
         an int32 CUDA tensor or a sequence; ids may repeat, any order; an id outside the handle gives zero rows).  Row r
         is Bullet link r - 1 (row 0: the root); a row is [COM 3 | quaternion xyzw 4 | link-frame origin 3 | COM velocity
         3 | angular velocity 3], world frame."""
-        t = self.torch
-        if env_ids is None:
-            ids, k = None, self.num_envs
-        else:
-            ids = t.as_tensor(env_ids, dtype=t.int32, device=self.device).reshape(-1).contiguous()
-            k = int(ids.numel())
-        if k < 1:
-            raise ValueError("env_ids must name at least one env")
+        ids, k = self._ids(env_ids)
         out = self._out(out, "out", (k, self.link_rows, _lib.LINK_STATE_FLOATS))
         self.stepper.link_states_device(ids.data_ptr() if ids is not None else 0, k, out.data_ptr(), self._stream())
         self._keep(ids)
@@ -313,13 +310,7 @@ class DeviceWorld(object):
         slot is [point on the body 3 | point on the ground 3 | normal 3 | distance | normal force N | impulse | c (2n: the
         box) | j | live | 0], zeros when not live.  out: a (points, force, count) tuple of tensors to write into."""
         t = self.torch
-        if env_ids is None:
-            ids, k = None, self.num_envs
-        else:
-            ids = t.as_tensor(env_ids, dtype=t.int32, device=self.device).reshape(-1).contiguous()
-            k = int(ids.numel())
-        if k < 1:
-            raise ValueError("env_ids must name at least one env")
+        ids, k = self._ids(env_ids)
         po, fo, co = (None, None, None) if out is None else out
         points = self._out(po, "out[0]", (k, self.stepper.contact_slots, _lib.CONTACT_FLOATS))
         force = self._out(fo, "out[1]", (k, 2 * self.n + 1))

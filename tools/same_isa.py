@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Is the device code of the working tree the same as that of a git revision?  Compiles csrc/snk_api.hip device-only to
-assembly (tools/kernel_resources.py: build.py's flags) for both, drops the lines that carry the `__hip_cuid_<hash>` symbol
-(it hashes the input) and prints `identical`, or else the symbols whose text differs (exit status 1).  The check for a
+"""Is the device code of the working tree the same as that of a git revision?  Compiles each of the three translation units
+(csrc/snk_api.hip, snk_render.hip, snk_world.hip) device-only to assembly (tools/kernel_resources.py: build.py's flags) for
+both, drops the lines that carry the `__hip_cuid_<hash>` symbol (it hashes the input) and prints one verdict per file:
+`identical`, or else the symbols whose text differs (exit status 1 if any file differs).  The check for a
 change that is meant to move or rename code without touching what the compiler makes of it.
     python tools/same_isa.py [REVISION (default HEAD)] [-DSNK_PROFILE ...]"""
 import os
@@ -12,6 +13,8 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 from kernel_resources import ROOT, device_asm
+
+SOURCES = ("csrc/snk_api.hip", "csrc/snk_render.hip", "csrc/snk_world.hip")
 
 
 def sections(path):
@@ -31,21 +34,26 @@ def sections(path):
 def main():
     rev = next((a for a in sys.argv[1:] if not a.startswith("-")), "HEAD")
     defines = [a for a in sys.argv[1:] if a.startswith("-")]
+    status = 0
     with tempfile.TemporaryDirectory() as td:
         old = os.path.join(td, "old")
         os.mkdir(old)
         tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "bullet-envs_amd", "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
-        with ThreadPoolExecutor(2) as ex:
-            jobs = [ex.submit(device_asm, root, defines, os.path.join(td, tag + ".s")) for root, tag in ((old, "old"), (ROOT, "new"))]
-            [j.result() for j in jobs]
-        a, b = sections(os.path.join(td, "old.s")), sections(os.path.join(td, "new.s"))
-    differ = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
-    if not differ and list(a) == list(b):
-        print("identical")
-        return 0
-    print("\n".join(differ) if differ else "same symbols, same text, another order")
-    return 1
+        # (each tree is compiled with its own headers under its own names: a header renamed between the two is no difference)
+        jobs = [(src, root, os.path.join(td, "%s_%d.s" % (tag, i))) for i, src in enumerate(SOURCES)
+                for root, tag in ((old, "old"), (ROOT, "new"))]
+        with ThreadPoolExecutor(len(jobs)) as ex:
+            [j.result() for j in [ex.submit(device_asm, root, defines, out, src) for src, root, out in jobs]]
+        for i, src in enumerate(SOURCES):
+            a, b = sections(jobs[2 * i][2]), sections(jobs[2 * i + 1][2])
+            differ = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+            if not differ and list(a) == list(b):
+                print("%s: identical" % src)
+                continue
+            print("%s: %s" % (src, " ".join(differ) if differ else "same symbols, same text, another order"))
+            status = 1
+    return status
 
 
 if __name__ == "__main__":
