@@ -155,7 +155,9 @@ __global__ __launch_bounds__(64, 2) void substep_kernel(const DevModel* __restri
     load_env(L, recs, mf_all, box_all, env, lane);
     if (lane < N) L.targets[lane] = targets[(size_t)env * N + lane];
     lds_sync();
-    float mu = fminf(M.mu_link * mu_plane[env], 10.0f);
+    const float mup = mu_plane[env];
+    float mu = fminf(M.mu_link * mup, 10.0f);
+    set_box_plane_mu(L, box_all, mup, lane);
     fk_vel(L, M, lane);
     int iters = 0, nc = 0;
     SensorHint hint;
@@ -395,7 +397,9 @@ __global__ __launch_bounds__(64, 2) void env_step_kernel(StepArgs args_by_value)
     if (M.poison) { L.poison(lane); lds_sync(); }
     load_env(L, ap->recs, ap->mf_all, ap->box_all, env, lane);
     set_targets(L, M, ap->actions, env, lane);
-    float mu = fminf(M.mu_link * ap->mu_plane[env], 10.0f);
+    const float mup = ap->mu_plane[env];
+    float mu = fminf(M.mu_link * mup, 10.0f);
+    set_box_plane_mu(L, ap->box_all, mup, lane);
     float* env_rows = rows_of<N>(ap->rows_all);
     float* env_mf = cache_of<N>(ap->mf_all, env);
     unsigned long long* ovf = ap->ovf;
@@ -476,9 +480,11 @@ __global__ __launch_bounds__(64, SNK_LB) void env_step_sched_kernel(StepArgs arg
             break;
         }
         set_targets(L, M, ap->actions, env, lane);
-        const float mu = fminf(M.mu_link * ap->mu_plane[env], 10.0f);
+        const float mup = ap->mu_plane[env];
+        const float mu = fminf(M.mu_link * mup, 10.0f);
         load_mf(L, cache_of<N>(ap->mf_all, env), lane);
         load_box(L, box_of(ap->box_all, env), lane);
+        set_box_plane_mu(L, ap->box_all, mup, lane);
         fk_vel(L, M, lane);
         // Snake.step servo loop (snake.py:283-304), `quantum` substeps at a time
         bool end_height = false, complete = false;

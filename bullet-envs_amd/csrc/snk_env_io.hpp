@@ -137,6 +137,14 @@ __device__ __forceinline__ void store_box(LT& L, float* __restrict__ bx, int lan
         }
     }
 }
+// obstacle 2: the plane's coefficient of the environment a wave has just loaded, for find_box_ground_v1 (nothing without a
+// free box: box_all is null)
+template <class LT>
+__device__ __forceinline__ void set_box_plane_mu(LT& L, const float* __restrict__ box_all, float mu_plane, int lane) {
+    if constexpr (!LT::kV2 && LT::kN <= 16) {
+        if (box_all && lane == 0) L.bmu = mu_plane;
+    }
+}
 // the workgroup's block of streamed constraint rows (one per resident wave): the streamed-row solve's, and behind the
 // register-resident one, for the substeps whose contacts outgrow its slots (substep())
 template <int N>

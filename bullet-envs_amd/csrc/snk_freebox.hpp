@@ -39,7 +39,10 @@ __device__ __forceinline__ void box_frame_v1(LT& L, const DevModel& M, int lane)
 // as a link's hull -- refresh, then one new support corner per step (localGetSupportingVertex: the nominal corner,
 // the box keeps its margin inside), <= 4 cached points, threshold DevModel::obs_thr.  Appends its records behind the
 // `first` contacts already there (geometry slots NC + first ...): body kBoxBody against the world, normal +z, friction
-// directions btPlaneSpace1(+z) unscaled (no anisotropic friction on the box), coefficient mu_obstacle x the plane's.
+// directions btPlaneSpace1(+z) unscaled (no anisotropic friction on the box), coefficient min(mu_obstacle x the plane's,
+// 10): the pair combined, then clamped (Bullet's rule), from the plane's own coefficient (L.bmu) -- mu_ground, the snake's
+// min(mu_link x mu_plane, 10), is only the unit the solve bounds every friction pair in (rho = the pair's / mu_ground; none
+// at mu_ground 0, mu_link 0 included: the rule test_link_link_friction_without_ground_friction keeps open).
 // Returns the number of points (<= 4, less if the room for these contacts is used up: counted).
 template <class LT>
 __device__ __forceinline__ int find_box_ground_v1(LT& L, const DevModel& M, int lane, float mu_ground, int first,
@@ -116,7 +119,7 @@ __device__ __forceinline__ int find_box_ground_v1(LT& L, const DevModel& M, int 
     lds_sync();
     if (lane == 0) {
         L.bmn = n;
-        const float mu_bg = fminf(M.mu_obs * (M.mu_link > 0.f ? mu_ground / M.mu_link : 0.f), 10.0f);
+        const float mu_bg = fminf(M.mu_obs * L.bmu, 10.0f);
         const float rho = mu_ground > 0.f ? mu_bg / mu_ground : 0.f;
 #pragma unroll
         for (int j = 0; j < 4; j++) {

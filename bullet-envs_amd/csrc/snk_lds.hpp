@@ -186,6 +186,9 @@ struct Lds<N, false> : LdsCommon<N, 2 * N> {
     // lambda)) and the point count; travels with the state record (d_box)
     float box[13], bR[9], bIw[6], bman[24];
     int bmn;
+    // ... and the plane's own friction coefficient of the environment (set_box_plane_mu; lane 0 writes and reads it): the
+    // box-ground pair combines it with the box's and clamps the product, which the snake's clamped mu cannot give back
+    float bmu;
 };
 
 // v2: rows live in VGPRs during the solve; LDS only stages one 64-row batch while they are built

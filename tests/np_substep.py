@@ -25,11 +25,22 @@ Jacobians and mass matrix:
   point carried into the substep (`lam0`, one per contact), and the solve's velocity change starts at the sum of
   M^-1 J^T of those starts; friction and non-contact rows start at zero.
 
+* the free box (`obstacle 2`, `box` given): a second body with six velocity components of its own, omega (3) then v (3),
+  behind the snake's 6 + n.  The mass matrix is block diagonal, diag(M_snake, R diag(I) R^T, m 1_3), I = btBoxShape's
+  m / 3 (hy^2 + hz^2, hx^2 + hz^2, hx^2 + hy^2) of the nominal box, or (1, 100, 1) under inertia_from_file 1.  Free motion:
+  alpha = I_w^-1 (-w x I_w w - I_w w (k_a + k_a |w|)), a = (0, 0, g_z) - v (k_l + k_l |v|), clamped per component like the
+  snake's.  The row of a box point P along d is J_box = [(P - c) x d ; d] over the six components (c the box's centre): a
+  box-ground contact (link < 0, linkB -1) has the row +J_box(P), friction min(mu_obstacle mu_plane, 10), tangents unscaled
+  (the box has no anisotropy); a link-box contact (linkB -2) has J_link(P) - J_box(PB), friction min(mu_link mu_obstacle,
+  10), tangents scaled by link A's anisotropy only.  Every other rule (position error, slop, contact_erp_rule, cone /
+  pyramid / one direction, solve order, residual, warm start from `lam0`) is the snake's contacts'; the box's rows come
+  where the list has them.  The box is integrated like the base: v = clamp(v_free + dv), pos += dt v, the quaternion by
+  the same exponential map.
+
 The contact list (points, depths, links, normals) is an input, and so is `lam0`: tests/np_manifold.py is the model of
-the contact cache that yields both for the ground contacts.
+the contact cache that yields both for the ground contacts, the box's own (update_box) included.
 
 Out of scope (the callers do not ask for it):
-* the free box (`obstacle 2`);
 * `noncontact_order 1`;
 * the joint-0 force sensor's constraint pass (obs[55]): its [U] rules are themselves open.
 """
@@ -240,20 +251,63 @@ def _resolve(r, dv):
     return dI / r.dinv if r.dinv != 0 else 0.0
 
 
-def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_threshold=None, lam0=None):
+def box_inertia(p):
+    """The free box's inertia diagonal in its own axes."""
+    if int(p.inertia_from_file):
+        return np.array([1.0, 100.0, 1.0])
+    hx, hy, hz = (float(x) for x in p.obstacle_half[:])
+    return float(p.obstacle_mass) / 3.0 * np.array([hy * hy + hz * hz, hx * hx + hz * hz, hx * hx + hy * hy])
+
+
+def integrate_quat(quat, w, dt):
+    """The orientation after dt at the world angular velocity w: the exponential map with the angular motion limit and
+    the third-order branch at small rates, normalised."""
+    fa = np.linalg.norm(w)
+    if fa * dt > ANGULAR_MOTION_THRESHOLD:
+        fa = ANGULAR_MOTION_THRESHOLD / dt
+    if fa < 1e-3:
+        sc = 0.5 * dt - dt ** 3 / 48.0 * fa * fa      # sin(fa dt / 2) / fa to third order
+    else:
+        sc = np.sin(0.5 * fa * dt) / fa
+    nq = quat_mul(np.concatenate([w * sc, [np.cos(0.5 * fa * dt)]]), quat)
+    return nq / np.linalg.norm(nq)
+
+
+def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_threshold=None, lam0=None, box=None):
     """One substep from state s = [pos, quat xyzw, w, v, q, qd] with motor targets, on the contact list `contacts`
-    ([nc, 12]: P, dist, link, linkB (-1 ground, -2 the static box, >= 0 a link), normal, PB) in solve order; lam0
-    [nc]: the impulse each contact's cached point carried (read only under warm_start 1; None: all zero).
+    ([nc, 12]: P, dist, link, linkB (-1 ground, -2 the box, >= 0 a link), normal, PB; link < 0: the free box against the
+    ground) in solve order; lam0 [nc]: the impulse each contact's cached point carried (read only under warm_start 1;
+    None: all zero); box [13]: the free box's state [pos, quat xyzw, omega, v] (None: no free box; linkB -2 is then the
+    static one).
     Returns a dict: state (after the substep), v_free, normal / friction / limit / motor impulses, motor torques
-    (impulse / dt), iterations, and the rows themselves (for complementarity checks)."""
+    (impulse / dt), iterations, and the rows themselves (for complementarity checks); with `box`, its new state under
+    "box", and v_free, M and the rows carry its six components behind the snake's."""
     ch = Chain(p)
     n, nd = ch.n, ch.nd
+    nsn = nd                                           # the snake's components; nd: all of them
     dt = float(p.dt)
     mx = float(p.max_coord_vel)
     n_it = int(p.n_iterations if n_iterations is None else n_iterations)
     thr = float(p.residual_threshold if residual_threshold is None else residual_threshold)
     pos, quat, q, g0 = ch.split(np.asarray(s, float))
     a, M, (Rw, ow, J) = ch.free_acceleration(s, tau=-float(p.joint_damping) * g0[6:])
+    if box is not None:
+        box = np.asarray(box, float)
+        bc, bquat, bw, bv = box[0:3], box[3:7], box[7:10], box[10:13]
+        bR = np_model.quat_to_mat(bquat)
+        Iw = bR @ np.diag(box_inertia(p)) @ bR.T
+        ka, kl = float(p.ang_damping), float(p.lin_damping)
+        Iw_w = Iw @ bw
+        alpha = np.linalg.solve(Iw, -np.cross(bw, Iw_w) - Iw_w * (ka + ka * np.linalg.norm(bw)))
+        lin = np.array([0.0, 0.0, float(p.gravity_z)]) - bv * (kl + kl * np.linalg.norm(bv))
+        nd = nsn + 6
+        Mf = np.zeros((nd, nd))
+        Mf[:nsn, :nsn] = M
+        Mf[nsn:nsn + 3, nsn:nsn + 3] = Iw
+        Mf[nsn + 3:, nsn + 3:] = float(p.obstacle_mass) * np.eye(3)
+        M = Mf
+        g0 = np.concatenate([g0, bw, bv])
+        a = np.concatenate([a, alpha, lin])
     v = np.clip(g0 + a * dt, -mx, mx)
 
     def unit_row(j, sign):
@@ -279,8 +333,14 @@ def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_t
         noncontact.append(Row(Jr, np.linalg.solve(M, Jr), want - v[6 + j], -mi, mi, "motor", j))
 
     def point_jac(link, P):
-        Jw, Jv, c = J[link]
-        return Jv - skew(np.asarray(P) - c) @ Jw         # v_P = v_c + w x (P - c)
+        out = np.zeros((3, nd))
+        if link >= 0:
+            Jw, Jv, c = J[link]
+            out[:, :nsn] = Jv - skew(np.asarray(P) - c) @ Jw         # v_P = v_c + w x (P - c)
+        else:                                              # the free box: v_P = v + omega x (P - c)
+            out[:, nsn:nsn + 3] = -skew(np.asarray(P) - bc)
+            out[:, nsn + 3:] = np.eye(3)
+        return out
 
     def aniso(link, d):
         return Rw[link] @ (np.asarray(p.aniso, float) * (Rw[link].T @ d))
@@ -289,13 +349,17 @@ def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_t
     mu_ground = min(float(p.mu_link) * mu_plane, MAX_FRICTION)
     mu_self = min(float(p.mu_link) ** 2, MAX_FRICTION)
     mu_box = min(float(p.mu_link) * float(p.mu_obstacle), MAX_FRICTION)
+    mu_box_ground = min(float(p.mu_obstacle) * mu_plane, MAX_FRICTION)
     normals, pairs, mus = [], [], []
     for c in contacts:
         P, dist, la, lb, nrm, PB = c[0:3], c[3], int(c[4]), int(c[5]), c[6:9], c[9:12]
+        assert la >= 0 or (box is not None and lb == -1), "a contact of the free box itself: with the ground, `box` given"
         Jp = point_jac(la, P)
         if lb >= 0:
             Jp = Jp - point_jac(lb, PB)
-        mus.append(mu_self if lb >= 0 else (mu_box if lb == -2 else mu_ground))
+        elif lb == -2 and box is not None:
+            Jp = Jp - point_jac(-1, PB)
+        mus.append(mu_box_ground if la < 0 else mu_self if lb >= 0 else (mu_box if lb == -2 else mu_ground))
         Jn = nrm @ Jp
         Mn = np.linalg.solve(M, Jn)
         pen = dist + float(p.linear_slop)
@@ -309,7 +373,7 @@ def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_t
         normals.append(Row(Jn, Mn, -Jn @ v + err, 0.0, 1e10, "normal"))
         fr = []
         for f, t in enumerate(plane_space(nrm)):
-            d = aniso(la, t)
+            d = aniso(la, t) if la >= 0 else t             # (the box has no anisotropic friction)
             if lb >= 0:
                 d = aniso(lb, d)
             Jf = d @ Jp
@@ -366,19 +430,13 @@ def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_t
     vn = np.clip(v + dv, -mx, mx)
     out = np.asarray(s, float).copy()
     out[7:13] = vn[0:6]
-    out[13 + n:] = vn[6:]
-    out[13:13 + n] = q + dt * vn[6:]
+    out[13 + n:] = vn[6:nsn]
+    out[13:13 + n] = q + dt * vn[6:nsn]
     out[0:3] = pos + dt * vn[3:6]
-    w = vn[0:3]
-    fa = np.linalg.norm(w)
-    if fa * dt > ANGULAR_MOTION_THRESHOLD:
-        fa = ANGULAR_MOTION_THRESHOLD / dt
-    if fa < 1e-3:
-        sc = 0.5 * dt - dt ** 3 / 48.0 * fa * fa      # sin(fa dt / 2) / fa to third order
-    else:
-        sc = np.sin(0.5 * fa * dt) / fa
-    nq = quat_mul(np.concatenate([w * sc, [np.cos(0.5 * fa * dt)]]), quat)
-    out[3:7] = nq / np.linalg.norm(nq)
+    out[3:7] = integrate_quat(quat, vn[0:3], dt)
+    box_out = None
+    if box is not None:
+        box_out = np.concatenate([bc + dt * vn[nsn + 3:], integrate_quat(bquat, vn[nsn:nsn + 3], dt), vn[nsn:]])
     tau_motor = np.zeros(n)
     for r in noncontact:
         if r.kind == "motor":
@@ -386,4 +444,4 @@ def substep(p, s, targets, contacts, mu_plane=1.0, n_iterations=None, residual_t
     return dict(state=out, v_free=v, acc=a, M=M, iterations=iters, tau_motor=tau_motor,
                 normal=np.array([r.applied for r in normals]),
                 friction=np.array([[A.applied, B.applied] for A, B in pairs]).reshape(-1, 2),
-                noncontact=noncontact, normals=normals, pairs=pairs, mus=np.array(mus), dv=dv)
+                noncontact=noncontact, normals=normals, pairs=pairs, mus=np.array(mus), dv=dv, box=box_out)

@@ -21,6 +21,7 @@ import pytest
 
 import np_rows as nr
 import np_substep as ns
+from box_states import FREE_BOX, gait_box
 from conftest import f32_gate, random_state
 from test_gpu_np_substep import PATHS, _ground, _open, _path
 from test_gpu_np_sweeps import SCENARIOS, _scenario
@@ -29,7 +30,6 @@ from test_np_rows import BOX, MIRROR, folded32, model_dirs, relerr, static_box
 pytestmark = pytest.mark.gpu
 
 ROW_PATHS = [p[0] for p in PATHS if p[0] != "register-resident"]
-FREE_BOX = dict(obstacle=2, obstacle_pos=[0.100, 0.0, 0.1])
 G = nr.GEO_FIELDS
 
 
@@ -76,40 +76,14 @@ def the_set(oracle_mod, path, name):
         else:
             S, T, M, _, _ = gait_box(oracle_mod, n, 4, BOX)
             s = Set(n, S, T, BOX, M=M)
-    elif name == "free box":
+    elif name in ("free box", "free box, plane friction 6"):
         assert n == 16
         S, T, M, BS, BM = gait_box(oracle_mod, n, 8, FREE_BOX)
-        s = Set(n, S, T, FREE_BOX, M=M, box=(BS, BM))
+        s = Set(n, S, T, FREE_BOX, 6.0 if name.endswith("6") else None, M=M, box=(BS, BM))
     else:
         raise KeyError(name)
     _sets[key] = s
     return s
-
-
-_gait = {}
-
-
-def gait_box(oracle_mod, n, k, over):
-    """(S, T, M, box states, box manifolds) of gait runs into the box in front of the snake's head."""
-    from bench import gait_actions
-    key = (n, k, over["obstacle"])
-    if key in _gait:
-        return _gait[key]
-    rng = np.random.default_rng(1600 + n + over["obstacle"])
-    e = oracle_mod.OracleEnv(n_modules=n, **MIRROR, **over)
-    S, M, BS, BM = [], [], [], []
-    for i in range(k):
-        e.hard_reset()
-        e.reset()
-        for j in range(8 + i % 6):
-            e.env_step(gait_actions(np.array([i + 1]), j, e.act_dim)[0], vec_mode=True)
-        S.append(e.get_state())
-        M.append(e.get_manifold())
-        b = e.get_box() if over["obstacle"] == 2 else (np.zeros(13), np.zeros(29))
-        BS.append(b[0])
-        BM.append(b[1])
-    _gait[key] = (np.array(S), rng.uniform(-0.5, 0.5, (k, n)), np.array(M), np.array(BS), np.array(BM))
-    return _gait[key]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -168,8 +142,9 @@ _refs = {}
 
 def refs(oracle_mod, path, name, s, **extra):
     """Per state: the float64 and float32 oracles' contacts, rows and results under s.over + extra, the two oracles' free
-    velocity (n_iterations 0) and M^-1, and the numpy model's rows, free velocity and mass matrix (no model of the free
-    box: None)."""
+    velocity (n_iterations 0) and M^-1, and the numpy model's rows, free velocity and mass matrix (None for the sets with
+    the free box: their stages keep the float64 oracle as the reference; tests/test_gpu_np_box.py holds the kernels to the
+    model's box)."""
     key = (path, name, tuple(sorted(extra.items())))
     if key in _refs:
         return _refs[key]
@@ -265,7 +240,9 @@ def rhs_err(x, ref, dinv):
 # ------------------------------------------------------------------------------------------------------------------
 # A. contact records
 # ------------------------------------------------------------------------------------------------------------------
-A_SETS = [(p, s) for p in ROW_PATHS for s in ("default", "folded", "static box")] + [("streamed-row", "free box")]
+A_SETS_0 = [(p, s) for p in ROW_PATHS for s in ("default", "folded", "static box")] + [("streamed-row", "free box")]
+# (plane friction 6: where the clamp of a combined coefficient at 10 bites, 2 x 6 -- the box's own is 0.5 x 6 = 3)
+A_SETS = A_SETS_0 + [("streamed-row", "free box, plane friction 6")]
 
 
 @collected
@@ -273,12 +250,14 @@ def stage_a(pkg, oracle_mod, path, name):
     """Per compact contact, in the solve's order: P, dist, normal, PB (two-body contacts) against the float64 oracle's
     contacts; the two friction directions against plane_space / aniso of the numpy model (test_np_rows.model_dirs: link A's
     anisotropy, then link B's; the box has none), yardstick the float32 oracle's rows' directions; bodies, counts and (to 2
-    float32 ulps: three roundings) the friction scale exactly."""
+    float32 ulps: three roundings) the friction scale exactly -- the pair's own coefficient, combined and then clamped at 10,
+    over the snake's with the ground: min(mu_link^2, 10), min(mu_link mu_obstacle, 10), and for the free box against the
+    ground min(mu_obstacle mu_plane, 10)."""
     s = the_set(oracle_mod, path, name)
     g, r = gpu_run(pkg, path, name, s), refs(oracle_mod, path, name, s)
     L = g["layout"]
     st = Stage("A %s, %s" % (path, name))
-    two_body = 0
+    two_body = box_ground = 0
     for i in range(len(s.S)):
         dec = decoded(g, r, i)
         C = r[i]["o"]["C"]
@@ -286,24 +265,27 @@ def stage_a(pkg, oracle_mod, path, name):
         C32, F32 = r[i]["o32"]["C"], r[i]["o32"]["rows"]["frictions"]["dir"]
         same = len(C32) == len(C) and np.array_equal(C32[:, 4:6], C[:, 4:6])
         p = r[i]["params"]
-        mu_g = min(p.mu_link * inputs64(s, i)[4], 10.0)
+        mu_plane = inputs64(s, i)[4]
+        mu_g = min(p.mu_link * mu_plane, 10.0)
         for ci, c in enumerate(C):
             geo = dec["geo"][dec["slot"][ci]].astype(np.float64)
             la, lb = int(c[4]), int(c[5])
             assert int(geo[G["kA"]]) == body_of(la, L), (i, ci, geo[G["kA"]], la)
             kB = body_of(lb, L) if lb >= 0 else (L["kBoxBody"] if lb == -2 and p.obstacle == 2 else -1)
             assert int(geo[G["kB"]]) == kB, (i, ci, geo[G["kB"]], lb)
-            rho = 1.0
-            if lb >= 0:
-                rho = min(p.mu_link ** 2, 10.0) / mu_g
-            elif lb == -2 or la < 0:
-                rho = min((p.mu_link if la >= 0 else 1.0) * p.mu_obstacle, 10.0) / mu_g
             if la >= 0 and lb == -1:
                 assert geo[G["fscale"]] == 1.0
             elif mu_g == 0:
                 pass            # (no finite scale: test_link_link_friction_without_ground_friction)
-            elif la >= 0:
-                assert abs(geo[G["fscale"]] - rho) <= 2.0 ** -22 * rho, (i, ci, geo[G["fscale"]], rho)
+            else:
+                if lb >= 0:
+                    rho = min(p.mu_link ** 2, 10.0) / mu_g
+                elif la >= 0:
+                    rho = min(p.mu_link * p.mu_obstacle, 10.0) / mu_g
+                else:
+                    box_ground += 1
+                    rho = min(p.mu_obstacle * mu_plane, 10.0) / mu_g
+                assert abs(geo[G["fscale"]] - rho) <= 2.0 ** -22 * rho, (i, ci, la, lb, geo[G["fscale"]], rho)
             c32 = C32[ci] if same else None
             y = lambda f: None if c32 is None else f(c32)                  # noqa: E731
             st.add("P", relerr(geo[G["P"]], c[0:3]), y(lambda x: relerr(x[0:3], c[0:3])))
@@ -316,6 +298,8 @@ def stage_a(pkg, oracle_mod, path, name):
             st.add("direction B", relerr(geo[G["dirB"]], F[2 * ci + 1]), relerr(F32[2 * ci + 1], F[2 * ci + 1]) if same else None)
     if name != "default":
         assert two_body > 0
+    if name.startswith("free box"):
+        assert box_ground >= len(s.S), "the box's own ground contacts are among the records"
     return st
 
 
@@ -438,7 +422,7 @@ def reference_rows(d):
     return ref, (y if len(y["n"]) == len(ref["n"]) else None)
 
 
-D_SETS = A_SETS + [(p, s) for p in ROW_PATHS for s in ("plane friction 6", "friction_directions 1")]
+D_SETS = A_SETS_0 + [(p, s) for p in ROW_PATHS for s in ("plane friction 6", "friction_directions 1")]
 # The sets that miss a gate, with the figure that misses it by most: medians of the normal rows' den, J / den and rhs, and
 # single worst rows at 2 to 4.4 x the float32 oracle's worst.  DESIGN.md 3 says where the den's error comes from
 # (test_stage_d_den_decomposition prints it).

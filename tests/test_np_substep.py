@@ -6,6 +6,9 @@ the contact / limit / motor rows, btPlaneSpace1 tangents and their anisotropic s
 order, the residual exit -- was checked by invariants only, and the GPU is gated against the oracle.  Both programs
 here run the same sequence in float64, so any difference above round-off is a finding, not noise.
 
+The last section does the same for the free box (obstacle 2), which np_substep models as a second body behind the snake's
+velocity components: states from tests/box_states.py, the box's six velocities and its pose measured with the snake's.
+
 Every test prints `BOUND <what>: largest <observed> <= <bound>`.
 """
 import numpy as np
@@ -25,8 +28,9 @@ BOX = dict(obstacle=1, obstacle_pos=[0.100, 0.0, 0.1])        # its face 2 mm in
 class Worst:
     """The largest error per bound over a test's substeps, printed and asserted at the end."""
 
-    def __init__(self, name):
+    def __init__(self, name, bounds=None):
         self.name = name
+        self.bounds = BOUNDS if bounds is None else bounds
         self.e = dict(vel=0.0, pose=0.0, normal=0.0, tau=0.0)
         self.count = 0
         self.contacts = 0
@@ -50,26 +54,34 @@ class Worst:
             for k, (err, spread) in b.items():
                 print("  [%s] bifurcation: %s off by %.2e, the model's own spread under 1e-15 input noise %.2e"
                       % (self.name, k, err, spread))
-        for k, b in BOUNDS.items():
-            print("  BOUND %-58s largest %.2e <= %.0e" % ("%s: %s" % (self.name, k), self.e[k], b))
-        for k, b in BOUNDS.items():
+        for k, b in self.bounds.items():
+            print("  BOUND %-58s largest %.2e <= %.1e" % ("%s: %s" % (self.name, k), self.e[k], b))
+        for k, b in self.bounds.items():
             assert self.e[k] <= b, (self.name, k, self.e[k], b)
         assert len(self.bifurcations) <= 1, self.bifurcations
 
 
-def _errors(n, x, N, tau, ref, Nref, tauref):
+def _errors(n, x, N, tau, ref, Nref, tauref, box=None, boxref=None):
+    """(box, boxref: the free box's 13 floats; its six velocities and its pose join the snake's, measured the same way)"""
     d = {}
     d["vel"] = max((np.abs(x[7:13] - ref[7:13]) / (1 + np.abs(ref[7:13]))).max(),
                    (np.abs(x[13 + n:] - ref[13 + n:]) / (1 + np.abs(ref[13 + n:]))).max())
     vs = 1 + max(np.abs(ref[7:13]).max(), np.abs(ref[13 + n:]).max())
+    if boxref is not None:
+        d["vel"] = max(d["vel"], (np.abs(box[7:13] - boxref[7:13]) / (1 + np.abs(boxref[7:13]))).max())
+        vs = max(vs, 1 + np.abs(boxref[7:13]).max())
     d["pose"] = max(np.abs(x[0:7] - ref[0:7]).max(), np.abs(x[13:13 + n] - ref[13:13 + n]).max()) / vs
+    if boxref is not None:
+        d["pose"] = max(d["pose"], np.abs(box[0:7] - boxref[0:7]).max() / vs)
     d["normal"] = np.abs(N - Nref).max() / max(np.abs(Nref).max(), 1e-6) if len(Nref) else 0.0
     d["tau"] = np.abs(tau - tauref).max() / max(1.0, np.abs(tauref).max())
     return d
 
 
-def compare(e, s, T, mu_plane=1.0, manifold=None, lam0=None):
-    """One oracle substep from (s, manifold) and the numpy model on the contacts the oracle solved.
+def compare(e, s, T, mu_plane=1.0, manifold=None, lam0=None, box=None, bounds=None):
+    """One oracle substep from (s, manifold) and the numpy model on the contacts the oracle solved.  box: (state [13],
+    manifold [29]) of the free box (obstacle 2); lam0 then covers the whole list (box_states.start_impulses); bounds: the
+    figures beyond which a state is looked at as a bifurcation (BOUNDS).
 
     A figure beyond its bound is a finding unless the state is a bifurcation for THAT figure: the numpy model itself, run
     from inputs moved by 1e-15 relative, spreads in that figure by at least a tenth of the difference (a contact on the
@@ -77,10 +89,13 @@ def compare(e, s, T, mu_plane=1.0, manifold=None, lam0=None):
     figures so measured are excused (`excused`: {figure: (difference, spread)}), every other figure of the state still
     counts, and a test may hold at most one such state."""
     n = e.n
+    bounds = BOUNDS if bounds is None else bounds
     e.hard_reset()
     e.set_plane_friction(mu_plane)
     if manifold is not None:
         e.set_manifold(manifold)
+    if box is not None:
+        e.set_box(*box)
     e.set_state(s)
     e.substep(T)
     C = e.last_contacts_full()
@@ -90,20 +105,23 @@ def compare(e, s, T, mu_plane=1.0, manifold=None, lam0=None):
     assert len(N) == len(C)
     if lam0 is not None:
         lam0 = np.concatenate([lam0, np.zeros(len(C) - len(lam0))])      # link-link / box contacts carry none
-    r = ns.substep(e.params, s, T, C, mu_plane=mu_plane, lam0=lam0)
-    d = _errors(n, r["state"], r["normal"], r["tau_motor"], ref, N, tau)
-    d.update(nc=len(C), iters=r["iterations"], r=r, C=C, ref=ref, excused={})
+    b0 = None if box is None else np.asarray(box[0], float)
+    bref = None if box is None else e.get_box()[0]
+    r = ns.substep(e.params, s, T, C, mu_plane=mu_plane, lam0=lam0, box=b0)
+    d = _errors(n, r["state"], r["normal"], r["tau_motor"], ref, N, tau, r["box"], bref)
+    d.update(nc=len(C), iters=r["iterations"], r=r, C=C, ref=ref, boxref=bref, excused={})
     assert r["iterations"] == e.last_iterations, (r["iterations"], e.last_iterations)
-    if any(d[k] > b for k, b in BOUNDS.items()):
+    if any(d[k] > b for k, b in bounds.items()):
         rng = np.random.default_rng(0)
-        spread = dict.fromkeys(BOUNDS, 0.0)
+        spread = dict.fromkeys(bounds, 0.0)
         for _ in range(2):
             s2 = s * (1 + 1e-15 * rng.uniform(-1, 1, s.shape))
-            r2 = ns.substep(e.params, s2, T, C, mu_plane=mu_plane, lam0=lam0)
-            e2 = _errors(n, r2["state"], r2["normal"], r2["tau_motor"], r["state"], r["normal"], r["tau_motor"])
-            for k in BOUNDS:
+            r2 = ns.substep(e.params, s2, T, C, mu_plane=mu_plane, lam0=lam0, box=b0)
+            e2 = _errors(n, r2["state"], r2["normal"], r2["tau_motor"], r["state"], r["normal"], r["tau_motor"],
+                         r2["box"], r["box"])
+            for k in bounds:
                 spread[k] = max(spread[k], e2[k])
-        d["excused"] = {k: (d[k], spread[k]) for k, b in BOUNDS.items() if d[k] > b and spread[k] >= 0.1 * d[k]}
+        d["excused"] = {k: (d[k], spread[k]) for k, b in bounds.items() if d[k] > b and spread[k] >= 0.1 * d[k]}
     return d
 
 
@@ -497,3 +515,134 @@ def test_sweep_ladder(oracle_mod, n, switch, k):
     print("  BOUND %-58s largest %.2e <= 1e-09" % ("%d links, %s, %d sweeps: vel" % (n, switch, k), worst))
     assert contacts >= 3 * 8
     assert worst <= 1e-9, (n, switch, k, worst)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the free box (obstacle 2): a second body behind the snake's velocity components
+# ------------------------------------------------------------------------------------------------------------------
+# velocities (the box's six among them) 1e-9 relative, poses (the box's among them) 7e-12, normal impulses 1.5e-9
+BOX_BOUNDS = dict(vel=1e-9, pose=7e-12, normal=1.5e-9, tau=TOL_TAU)
+_box_sets = {}
+
+
+def box_set(oracle_mod, kind, **over):
+    """(S, T, M, BS, BM) of box_states, built once per (kind, parameters)."""
+    import box_states as bs
+    key = (kind,) + tuple(sorted(over.items()))
+    if key not in _box_sets:
+        full = dict(bs.FREE_BOX, **over)
+        if kind == "gait":
+            _box_sets[key] = bs.gait_box(oracle_mod, 16, 8, full)
+        elif kind == "beside":
+            _box_sets[key] = bs.beside_link(oracle_mod, np.random.default_rng(2100), 12, full)
+        else:
+            _box_sets[key] = bs.in_the_air(np.random.default_rng(2101), 8)
+    return _box_sets[key]
+
+
+def run_box_case(oracle_mod, name, kind, over, mu_plane=1.0, motion=("found", "twisted"), seed=0, min_link_box=0.5,
+                 set_over=None):
+    """One substep per (state, box motion) of a set under `over`, every figure against BOX_BOUNDS; at least `min_link_box`
+    of the substeps hold a link-box contact.  Returns the per-substep results."""
+    import box_states as bs
+    rng = np.random.default_rng(2200 + seed)
+    S, T, M, BS, BM = box_set(oracle_mod, kind, **(over if set_over is None else set_over))
+    e = oracle_mod.OracleEnv(**bs.MIRROR, **dict(bs.FREE_BOX, **over))
+    w = Worst(name, BOX_BOUNDS)
+    out, with_pair = [], 0
+    for how in motion:
+        B = dict(found=lambda: BS, twisted=lambda: bs.twisted(rng, BS), clamp=lambda: bs.at_the_clamp(rng, BS))[how]()
+        for i in range(len(S)):
+            m = None if M is None else M[i]
+            lam0 = None
+            if int(e.params.warm_start):
+                e.hard_reset()
+                if m is not None:
+                    e.set_manifold(m)
+                e.set_box(B[i], BM[i])
+                e.set_state(S[i])
+                lam0 = bs.start_impulses(e.params, S[i], m, (B[i], BM[i]), e.contacts_full())
+            d = compare(e, S[i], T[i], mu_plane=mu_plane, manifold=m, lam0=lam0, box=(B[i], BM[i]), bounds=BOX_BOUNDS)
+            with_pair += bool((d["C"][:, 5] == -2).any())
+            d["how"] = how
+            w.add(d)
+            out.append(d)
+    print("  [%s] %d of %d substeps with a link-box contact, %d box-ground contacts" %
+          (name, with_pair, len(out), sum(int((d["C"][:, 4] < 0).sum()) for d in out)))
+    assert 8 <= len(S) <= 16 and with_pair >= min_link_box * len(out), (with_pair, len(out))
+    w.check()
+    return out
+
+
+@pytest.mark.parametrize("mass", [200.0, 0.5])
+@pytest.mark.parametrize("mu_plane", [0.0, 1.0, 6.0])
+def test_free_box_gait_states(oracle_mod, mu_plane, mass):
+    """The 8 gait-into-the-box states with their caches (0.5 kg: of a gait run against the light box), the box as found and
+    with a twist added (|omega| <= 5, |v| <= 2), so that it slides on its ground contacts.  The box-ground pair's coefficient
+    is the product of the box's and the plane's, clamped after combining: 0, 0.5, and at plane friction 6 it is 3, not
+    min(2 x 6, 10) x 0.5 / 2 = 2.5."""
+    out = run_box_case(oracle_mod, "free box, gait states, %g kg, plane friction %g" % (mass, mu_plane), "gait",
+                       dict(obstacle_mass=mass), mu_plane, seed=int(mu_plane) + int(mass))
+    assert all((d["C"][:, 4] < 0).any() for d in out), "the box stands on the ground in every state"
+    mus = np.concatenate([d["r"]["mus"][d["C"][:, 4] < 0] for d in out])
+    assert np.all(mus == min(0.5 * mu_plane, 10.0))
+    slip = max(np.abs(d["boxref"][10:12]).max() for d in out if d["how"] == "twisted")
+    assert slip > 0.1, "the twisted box slides (%g)" % slip
+
+
+@pytest.mark.parametrize("motion", ["found", "twisted"])
+@pytest.mark.parametrize("from_file", [0, 1])
+@pytest.mark.parametrize("mass", [200.0, 0.5])
+def test_free_box_beside_a_link(oracle_mod, mass, from_file, motion):
+    """The box placed beside a link, as found (at rest: the small-angle branch of its integration) or twisted.  At 0.5 kg
+    the box's block of M^-1 J^T dominates a link-box row, so that a wrong sign or lever arm of its part shows;
+    inertia_from_file 1: the box's (1, 100, 1) (and the snake's file inertias)."""
+    over = dict(obstacle_mass=mass, inertia_from_file=from_file)
+    out = run_box_case(oracle_mod, "free box beside a link, %s, %g kg, inertia_from_file %d" % (motion, mass, from_file),
+                       "beside", over, motion=(motion,), seed=int(mass) + from_file, set_over=dict(inertia_from_file=from_file))
+    small = sum(np.linalg.norm(d["boxref"][7:10]) < 1e-3 for d in out)
+    if motion == "found":
+        assert small >= 1, "the third-order branch of the exponential map is met"
+    else:
+        assert small == 0
+    pushed = max(np.abs(d["boxref"][7:13] - d["r"]["v_free"][22:]).max() for d in out)
+    assert pushed > 1e-3, "the contacts move the box (%g)" % pushed
+
+
+BOX_SWITCHES = {"cone_friction 0": dict(cone_friction=0), "friction_directions 1": dict(friction_directions=1),
+                "contact_erp_rule 1": dict(contact_erp_rule=1)}
+
+
+@pytest.mark.parametrize("mass", [200.0, 0.5])
+@pytest.mark.parametrize("switch", list(BOX_SWITCHES))
+def test_free_box_switches(oracle_mod, switch, mass):
+    over = dict(BOX_SWITCHES[switch], obstacle_mass=mass)
+    run_box_case(oracle_mod, "free box beside a link, %g kg, %s" % (mass, switch), "beside", over, motion=("twisted",),
+                 seed=20 + int(mass) + len(switch), set_over={})
+
+
+@pytest.mark.parametrize("mass", [200.0, 0.5])
+def test_free_box_warm_start(oracle_mod, mass):
+    """warm_start 1 on gait states run under it: the box's own ground contacts start at the impulses of its cached points
+    (np_manifold.update_box), like the snake's."""
+    over = dict(warm_start=1, obstacle_mass=mass)
+    S, T, M, BS, BM = box_set(oracle_mod, "gait", **over)
+    assert np.abs(BM[:, 7::7]).max() > 1e-4, "the box's cache carries impulses"
+    run_box_case(oracle_mod, "free box, gait states, %g kg, warm start" % mass, "gait", over, seed=30 + int(mass))
+
+
+def test_free_box_free_fall(oracle_mod):
+    """Snake and box in the air, no contact: the box's free motion alone -- the gyroscopic term, the k + k|.| damping on
+    omega and v, gravity -- and its integration."""
+    out = run_box_case(oracle_mod, "free box in free fall", "air", {}, motion=("twisted",), seed=40, min_link_box=0.0)
+    assert all(d["nc"] == 0 for d in out)
+    for d in out:                                   # the gyroscopic term is not small against the bound
+        assert np.abs(d["boxref"][7:10]).max() > 0.5
+
+
+def test_free_box_velocity_clamp(oracle_mod):
+    """Every box velocity component at +-99.5 ... 100: max_coord_vel clamps v + a dt and v_free + dv per component, and the
+    angular motion limit of pi / 4 per substep holds the rotation."""
+    out = run_box_case(oracle_mod, "free box at the velocity clamp", "beside", {}, motion=("clamp",), seed=50)
+    at = sum(int((np.abs(d["boxref"][7:13]) == 100.0).sum()) + int((np.abs(d["r"]["v_free"][22:]) == 100.0).sum()) for d in out)
+    assert at >= len(out), at
