@@ -84,6 +84,10 @@ SYMBOLS = {
     "snk_contacts": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "snk_contacts_host": (C.c_int, [_vp, _I32, C.c_int32, _F, _F, _I32]),
     "snk_contact_links": (C.c_int, [C.POINTER(SnkParams), _I32]),
+    "snk_link_pairs": (C.c_int32, [_vp]),
+    "snk_closest_slots": (C.c_int32, [_vp, C.c_int32]),
+    "snk_closest_points": (C.c_int, [_vp, _vp, C.c_int32, C.c_float, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "snk_closest_points_host": (C.c_int, [_vp, _I32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _F, _F, _I32]),
     "snk_copy_envs": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "snk_copy_envs_host": (C.c_int, [_vp, _I32, _I32, C.c_int32, C.c_int32]),
     "snk_get_state": (C.c_int, [_vp, _F, _F]),
@@ -122,6 +126,8 @@ SYMBOLS = {
 }
 RENDER_SHADOW = 1      # SNK_RENDER_SHADOW
 COPY_RESET_POSE = 1    # SNK_COPY_RESET_POSE
+PAIRS_BOX = 1          # SNK_PAIRS_BOX: the (cylinder, obstacle box) pairs of snk_closest_points
+PAIRS_LINKS = 2        # SNK_PAIRS_LINKS: its link-link pairs
 CONTACT_FLOATS = 16     # SNK_CONTACT_FLOATS, floats per contact slot of snk_contacts: [point on the body 3 | point on the ground 3 |
 #                         normal 3 | distance | normal force N | impulse | cylinder (2n: the box) | j | live | 0]
 LINK_STATE_FLOATS = 16  # floats per row of snk_link_states: [COM 3 | quat xyzw 4 | link origin 3 | COM velocity 3 | omega 3]
@@ -693,6 +699,47 @@ class Stepper:
         out = np.zeros(2 * self.n, np.int32)
         check(self.lib.snk_contact_links(C.byref(self.params), out.ctypes.data_as(_I32)), "snk_contact_links")
         return out
+
+    @property
+    def link_pairs(self):
+        """snk_link_pairs: the link-link pairs of the chain, C(2n, 2) - (2n - 1) (465 / 1953)."""
+        k = int(self.lib.snk_link_pairs(self.h))
+        if k == 0:
+            raise RuntimeError("snk_link_pairs failed: %s" % last_error())
+        return k
+
+    def closest_slots(self, max_pairs):
+        """snk_closest_slots: slots per env of closest_points' table, 2n + max_pairs."""
+        k = int(self.lib.snk_closest_slots(self.h, int(max_pairs)))
+        if k == 0:
+            raise RuntimeError("snk_closest_slots failed: %s" % last_error())
+        return k
+
+    def closest_points_device(self, ids_ptr, n_rows, distance, flags, max_pairs, points_ptr=0, clearance_ptr=0, count_ptr=0,
+                              stream=0):
+        """snk_closest_points: points [n_rows, 2n + max_pairs, 16] f32, clearance [n_rows, 2, 2n] f32, count [n_rows, 2] i32
+        (each a device pointer or 0) for the envs ids [n_rows] i32 (0: envs 0 .. n_rows - 1).  Asynchronous on `stream`."""
+        check(self.lib.snk_closest_points(self.h, ids_ptr or None, int(n_rows), float(distance), int(flags), int(max_pairs),
+                                          points_ptr or None, clearance_ptr or None, count_ptr or None, stream or None),
+              "snk_closest_points")
+
+    def closest_points(self, distance, env_ids=None, flags=PAIRS_BOX | PAIRS_LINKS, max_pairs=None):
+        """snk_closest_points_host: (points [k, 2n + max_pairs, 16] float32, clearance [k, 2, 2n] float32, count [k, 2]
+        int32) of the envs `env_ids` (None: all; ids may repeat, any order) at the current pose: the link-box and link-link
+        pairs closer than `distance` (snk.h, "The closest points").  Slot c < 2n is the pair (cylinder c, box); the found
+        link-link pairs follow, compact, in the solver's order, the first `max_pairs` of them (None: room for every
+        pair).  A record is [point on cylinder a 3 | point on B 3 | normal on B 3 | distance | tier | 0 | a | b (2n: the
+        box) | live | 0]; clearance is min(found distances, distance) per cylinder for the box (row 0) and the other links
+        (row 1); count = (box pairs, link-link pairs) found, the latter not clipped to max_pairs."""
+        ids, k, idp = self._ids(env_ids)
+        mp = self.link_pairs if max_pairs is None else int(max_pairs)
+        ok = 0 <= mp <= 4096                                      # (the library refuses the rest by name; no huge buffers first)
+        points = np.zeros((max(k, 1), 2 * self.n + (mp if ok else 0), CONTACT_FLOATS), np.float32)
+        clearance = np.zeros((max(k, 1), 2, 2 * self.n), np.float32)
+        count = np.zeros((max(k, 1), 2), np.int32)
+        check(self.lib.snk_closest_points_host(self.h, idp, k, float(distance), int(flags), mp, fptr(points), fptr(clearance),
+                                               count.ctypes.data_as(_I32)), "snk_closest_points_host")
+        return points, clearance, count
 
     def copy_envs(self, src, dst, reset_pose=False):
         """snk_copy_envs_host: env dst[i] becomes env src[i] in everything a Snapshot holds (the reset pose only with

@@ -239,17 +239,22 @@ __device__ __forceinline__ float cyl_extent(const DevModel& M, f3 axis, f3 u) { 
     const float c = dot(axis, u);
     return M.cyl_hl * fabsf(c) + M.cyl_r * sqrtf(fmaxf(0.f, 1.0f - c * c));
 }
-__device__ __forceinline__ bool cyl_cyl_may_touch(const DevModel& M, f3 ca, f3 axa, f3 cb, f3 axb) {
+// (the forms that take the threshold serve the closest-point query, snk_world.hpp, at its caller's distance; the solver's
+//  forms are those at the handle's breaking threshold)
+__device__ __forceinline__ bool cyl_cyl_may_touch(const DevModel& M, f3 ca, f3 axa, f3 cb, f3 axb, float thr) {
     const f3 d = ca - cb;
     const float n2 = dot(d, d);
     if (!(n2 > 1e-12f)) return true;
     const float n = sqrtf(n2);
     const f3 u = d * (1.0f / n);
     const float bound = n - cyl_extent(M, axa, u) - cyl_extent(M, axb, u);
-    return bound - 2.0f * M.margin <= M.break_thr + 1e-5f;
+    return bound - 2.0f * M.margin <= thr + 1e-5f;
+}
+__device__ __forceinline__ bool cyl_cyl_may_touch(const DevModel& M, f3 ca, f3 axa, f3 cb, f3 axb) {
+    return cyl_cyl_may_touch(M, ca, axa, cb, axb, M.break_thr);
 }
 // cylinder against the box (centre bc, rotation Rb row-major, half extents hb): the three face normals of the box
-__device__ __forceinline__ bool cyl_box_may_touch(const DevModel& M, f3 ca, f3 axa, f3 bc, const float* Rb, f3 hb) {
+__device__ __forceinline__ bool cyl_box_may_touch(const DevModel& M, f3 ca, f3 axa, f3 bc, const float* Rb, f3 hb, float thr) {
     const f3 d = ca - bc;
     float bound = -3.0e38f;
 #pragma unroll
@@ -258,7 +263,10 @@ __device__ __forceinline__ bool cyl_box_may_touch(const DevModel& M, f3 ca, f3 a
         const float hi = i == 0 ? hb.x : (i == 1 ? hb.y : hb.z);
         bound = fmaxf(bound, fabsf(dot(d, e)) - (hi - M.margin) - cyl_extent(M, axa, e));
     }
-    return bound - 2.0f * M.margin <= M.break_thr + 1e-5f;
+    return bound - 2.0f * M.margin <= thr + 1e-5f;
+}
+__device__ __forceinline__ bool cyl_box_may_touch(const DevModel& M, f3 ca, f3 axa, f3 bc, const float* Rb, f3 hb) {
+    return cyl_box_may_touch(M, ca, axa, bc, Rb, hb, M.break_thr);
 }
 
 // Does any pair of cylinder links (parent-child pairs excepted) pass the broad phase and the separating-axis cull?

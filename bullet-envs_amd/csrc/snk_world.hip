@@ -1,8 +1,9 @@
-// snk_world.hip -- link states, reported contacts and the env fork behind snk_link_states / snk_contacts / snk_copy_envs and
-// their host forms, and the host-only link read-outs (include/snk.h).  A translation unit and a code object of its own, like snk_render.hip:
+// snk_world.hip -- link states, reported contacts, the env fork and the closest-point query behind snk_link_states /
+// snk_contacts / snk_copy_envs / snk_closest_points and their host forms, and the host-only link read-outs (include/snk.h).  A translation unit and a code object of its own, like snk_render.hip:
 // build.py compiles it to an object and links it into libsnk.so next to snk_api.hip, whose kernels it does not touch.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <memory>
@@ -130,6 +131,83 @@ int snk_contact_links(const snk_params* p, int32_t* out) {
     // 2k - 1: link 3k) -- build_host_model's cylinder loop, in the link numbering of its link table (row = link + 1)
     for (int c = 0; c < 2 * p->n_modules; c++) out[c] = (c & 1) ? 3 * ((c + 1) / 2) : 3 * (c / 2) + 1;
     return 0;
+}
+
+int32_t snk_link_pairs(const snk_handle* h) {
+    if (!h) { api_fail("snk_link_pairs: null handle"); return 0; }
+    snk::WorldView v;
+    if (snk::world_view(const_cast<snk_handle*>(h), false, &v)) return 0;
+    return snk::link_pairs_of(2 * v.n);
+}
+
+int32_t snk_closest_slots(const snk_handle* h, int32_t max_pairs) {
+    if (!h) { api_fail("snk_closest_slots: null handle"); return 0; }
+    snk::WorldView v;
+    if (snk::world_view(const_cast<snk_handle*>(h), false, &v)) return 0;
+    if (max_pairs < 0 || max_pairs > snk::link_pairs_of(2 * v.n)) {
+        api_fail("snk_closest_slots: max_pairs " + std::to_string(max_pairs) + " is outside 0 .. " +
+                 std::to_string(snk::link_pairs_of(2 * v.n)) + " (snk_link_pairs)");
+        return 0;
+    }
+    return 2 * v.n + max_pairs;
+}
+
+namespace {
+
+// what both forms of snk_closest_points refuse before they look at the handle; 0: nothing
+int closest_args_refused(const char* who, int32_t n_rows, float distance, int32_t flags, const void* points, const void* clearance,
+                         const void* count) {
+    const std::string w(who);
+    if (n_rows < 1) return api_fail(w + ": n_rows must be at least 1");
+    if (!std::isfinite(distance) || distance < 0.f) return api_fail(w + ": distance must be finite and not negative");
+    if (flags == 0 || (flags & ~(SNK_PAIRS_BOX | SNK_PAIRS_LINKS)))
+        return api_fail(w + ": flags must be SNK_PAIRS_BOX, SNK_PAIRS_LINKS or both");
+    if (!points && !clearance && !count) return api_fail(w + ": points, clearance and count are all null");
+    return 0;
+}
+int closest_pairs_refused(const char* who, int32_t max_pairs, int n) {
+    if (max_pairs >= 0 && max_pairs <= snk::link_pairs_of(2 * n)) return 0;
+    return api_fail(std::string(who) + ": max_pairs " + std::to_string(max_pairs) + " is outside 0 .. " +
+                    std::to_string(snk::link_pairs_of(2 * n)) + " (snk_link_pairs)");
+}
+
+}  // namespace
+
+int snk_closest_points(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float distance, int32_t flags,
+                       int32_t max_pairs, float* points_dev, float* clearance_dev, int32_t* count_dev, void* stream) {
+    if (!h) return api_fail("snk_closest_points: null handle (h)");
+    if (closest_args_refused("snk_closest_points", n_rows, distance, flags, points_dev, clearance_dev, count_dev)) return 1;
+    if (reinterpret_cast<uintptr_t>(points_dev) % 16 != 0)
+        return api_fail("snk_closest_points: points_dev must be 16-byte aligned (the records leave as 16-byte stores)");
+    snk::WorldView v;
+    if (snk::world_view(h, false, &v)) return 1;
+    if (closest_pairs_refused("snk_closest_points", max_pairs, v.n)) return 1;
+    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+        hipLaunchKernelGGL((snk::closest_points_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)),
+                           dim3(64), 0, (hipStream_t)stream, v.d_model, v.d_recs, v.tables[snk::WorldView::kBox].d, env_ids_dev,
+                           distance, flags, max_pairs, points_dev, clearance_dev, count_dev, n_rows, v.n_envs);
+        return 0;
+    });
+    if (rc == snk::kUnsupported) return api_fail("snk_closest_points: unsupported n_modules (16 or 32)");
+    return launch_ok("snk_closest_points");
+}
+
+int snk_closest_points_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float distance, int32_t flags,
+                            int32_t max_pairs, float* points, float* clearance, int32_t* count) {
+    if (!h) return api_fail("snk_closest_points_host: null handle (h)");
+    if (closest_args_refused("snk_closest_points_host", n_rows, distance, flags, points, clearance, count)) return 1;
+    snk::WorldView v;
+    if (snk::world_view(h, true, &v)) return 1;
+    if (closest_pairs_refused("snk_closest_points_host", max_pairs, v.n)) return 1;
+    if (env_ids ? snk::check_env_ids("snk_closest_points_host", "env_ids", env_ids, n_rows, v.n_envs)
+                : snk::check_count_without_ids("snk_closest_points_host", "n_rows", n_rows, v.n_envs)) return 1;
+    snk::HostCall c;
+    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    float* d_pts = c.out(points, (size_t)n_rows * (2 * v.n + max_pairs) * snk::kContactFloats * sizeof(float));
+    float* d_clr = c.out(clearance, (size_t)n_rows * 2 * 2 * v.n * sizeof(float));
+    int32_t* d_count = c.out(count, (size_t)n_rows * 2 * sizeof(int32_t));
+    if (c.ok() && snk_closest_points(h, d_ids, n_rows, distance, flags, max_pairs, d_pts, d_clr, d_count, nullptr)) return 1;
+    return c.finish("snk_closest_points_host");
 }
 
 int snk_copy_envs(snk_handle* h, const int32_t* src_ids_dev, const int32_t* dst_ids_dev, int32_t n_pairs, int32_t flags,

@@ -327,6 +327,35 @@ class DeviceWorld(_TensorArgs):
         self.stepper.contacts_device(0, self.num_envs, force_ptr=out.data_ptr(), stream=self._stream())
         return out
 
+    def closest_points(self, distance, env_ids=None, flags=_lib.PAIRS_BOX | _lib.PAIRS_LINKS, max_pairs=64, out=None):
+        """(points [k, 2n + max_pairs, 16] float32, clearance [k, 2, 2n] float32, count [k, 2] int32): PyBullet's
+        getClosestPoints(snake, block, distance) and (snake, snake, distance) of the envs `env_ids` (None: all; an int32
+        CUDA tensor or a sequence; ids may repeat, any order; an id outside the handle gives zeros), the solver's narrow
+        phase run as a query on the current pose by one launch (snk_closest_points; include/snk.h has the contract).  Slot
+        c < 2n is the pair (cylinder c, box); the found link-link pairs follow, compact, in the solver's order, the first
+        `max_pairs` of them.  A slot is [point on cylinder a 3 | point on B 3 | normal on B 3 | distance | tier | 0 | a |
+        b (2n: the box) | live | 0], zeros when not live; count[:, 1] is not clipped to max_pairs.  out: a (points,
+        clearance, count) tuple of tensors to write into."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        po, co, no = (None, None, None) if out is None else out
+        points = self._out(po, "out[0]", (k, self.stepper.closest_slots(max_pairs), _lib.CONTACT_FLOATS))
+        clearance = self._out(co, "out[1]", (k, 2, 2 * self.n))
+        count = self._out(no, "out[2]", (k, 2), t.int32)
+        self.stepper.closest_points_device(ids.data_ptr() if ids is not None else 0, k, distance, flags, max_pairs,
+                                           points.data_ptr(), clearance.data_ptr(), count.data_ptr(), self._stream())
+        self._keep(ids)
+        return points, clearance, count
+
+    def clearance(self, distance, flags=_lib.PAIRS_BOX | _lib.PAIRS_LINKS, out=None):
+        """[E, 2, 2n] float32: per cylinder of every env its distance to the box (row 0) and to the nearest other link it
+        forms a pair with (row 1), each min(found distances, distance) -- `distance` reads "nothing within reach".  The
+        proximity term of a reward written over step_simulation; no records are written."""
+        out = self._out(out, "out", (self.num_envs, 2, 2 * self.n))
+        self.stepper.closest_points_device(0, self.num_envs, distance, flags, 0, clearance_ptr=out.data_ptr(),
+                                           stream=self._stream())
+        return out
+
     def reset(self, mask=None, out=None):
         """The soft reset (snake.py:96-99, 119-127) of the envs of `mask` (uint8 / bool [E]; None: all) onto their rows
         of the reset-pose table.  Returns the observations [E, 3n + 8]; rows of unmasked envs are left as `out` had them

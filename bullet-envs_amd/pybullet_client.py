@@ -24,6 +24,9 @@ DeviceWorld.link_states (snk_link_states), and Snake.getLinkOrientations / getBa
 
 getContactPoints answers what the handle holds: the ground contacts of the snake and of the free block, from the contact
 cache (snk_contacts).  Link-link and link-block contacts are stateless in the kernels: a query for them is refused.
+
+getClosestPoints answers (snake, block) and (snake, snake) at a caller-given distance: the solver's narrow phase run as a
+query on the current pose (snk_closest_points), one point per pair, no forces.  Distances to the plane are refused.
 """
 import math
 import os
@@ -351,3 +354,37 @@ class BulletClient(object):
         return [(0, mover, self._PLANE, int(link), -1, tuple(float(v) for v in r[0:3]), tuple(float(v) for v in r[3:6]),
                  tuple(float(v) for v in r[6:9]), float(r[9]), float(r[10]), 0.0, zero3, 0.0, zero3)
                 for r, link in zip(rows, links) if r[14] != 0.0 and want_mover in (-2, link)]
+
+    def getClosestPoints(self, bodyA, bodyB, distance, linkIndexA=-2, linkIndexB=-2, **kw):
+        """PyBullet's list of 14-tuples (getContactPoints' layout) for the pair (snake, block) or (snake, snake): the pairs
+        closer than `distance` at the CURRENT pose, one point per pair (PyBullet: up to four, as of the last collision pass)
+        -- the live slots of snk_closest_points in slot order (include/snk.h, "The closest points").  normalForce and the
+        four lateral-friction entries are zeros: these contacts carry no stored impulse.  The pair may be given in either
+        order and the tuples are never swapped: A is the snake's cylinder a, B the block (link -1) or cylinder b > a; the
+        links are those of contact_links().  linkIndexA / linkIndexB (-2: any) filter by the link of the body they are
+        given for; in a (snake, snake) query linkIndexA filters A's link and linkIndexB B's.
+        Refused (NotImplementedError): pairs with the plane, unknown bodies, extra keywords."""
+        if kw:
+            raise NotImplementedError("BulletClient.getClosestPoints: %s" % sorted(kw))
+        pair = (bodyA, bodyB)
+        if (self._PLANE in pair or self._SNAKE not in pair or not all(b in self._bodies for b in pair)
+                or pair == (self._BLOCK, self._BLOCK)):
+            raise NotImplementedError(
+                "BulletClient.getClosestPoints: only (snake, block) and (snake, snake) are answered (snk_closest_points); got "
+                "bodyA=%r, bodyB=%r -- distances to the plane are not computed" % (bodyA, bodyB))
+        st = self._stepper()
+        n = self._n
+        links = np.asarray(st.contact_links(), dtype=np.int64)
+        zero3 = (0.0, 0.0, 0.0)
+        if bodyA == bodyB:
+            rows = st.closest_points(distance, flags=_lib.PAIRS_LINKS)[0][0][2 * n:].astype(np.float64)
+            other, want_a, want_b = self._SNAKE, linkIndexA, linkIndexB
+            link_b = lambda r: int(links[int(r[13])])      # noqa: E731
+        else:
+            rows = st.closest_points(distance, flags=_lib.PAIRS_BOX, max_pairs=0)[0][0].astype(np.float64)
+            other = self._BLOCK
+            want_a, want_b = (linkIndexA, linkIndexB) if bodyA == self._SNAKE else (linkIndexB, linkIndexA)
+            link_b = lambda r: -1                          # noqa: E731
+        return [(0, self._SNAKE, other, int(links[int(r[12])]), link_b(r), tuple(float(v) for v in r[0:3]),
+                 tuple(float(v) for v in r[3:6]), tuple(float(v) for v in r[6:9]), float(r[9]), 0.0, 0.0, zero3, 0.0, zero3)
+                for r in rows if r[14] != 0.0 and want_a in (-2, int(links[int(r[12])])) and want_b in (-2, link_b(r))]

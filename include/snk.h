@@ -377,8 +377,8 @@ int snk_copy_envs_host(snk_handle* h, const int32_t* src_ids, const int32_t* dst
  *   - The force is that of the last substep in which the point had a row.  An env-step of 0 substeps leaves it stale.
  *   - A cached point that the next refresh would drop (beyond the breaking threshold at the current pose) is reported
  *     as the cache holds it.  The cache is the state.
- *   - Link-link and link-box contacts are stateless in the kernels and carry no stored impulse: they are NOT reported.
- *     Friction impulses are not stored either.
+ *   - Link-link and link-box contacts are stateless in the kernels and carry no stored impulse: they are NOT reported
+ *     (their geometry is what snk_closest_points computes, below).  Friction impulses are not stored either.
  *
  * Outputs, per requested env (row):
  *   points_dev  [n_rows][slots][16] f32, 16-byte aligned;
@@ -405,6 +405,85 @@ int snk_contacts(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, floa
                  int32_t* count_dev, void* stream);
 int snk_contacts_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* points, float* force, int32_t* count);
 int snk_contact_links(const snk_params* p, int32_t* out /* [2n] */);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The closest points: the contract of snk_closest_points (replaces pybullet.getClosestPoints(snake, block, distance) and
+ * getClosestPoints(snake, snake, distance): "how far is each link from the block", "is the snake folding onto itself" --
+ * the obstacle is the only other body the reference simulates, snake_gait_test.py:51).  The kernel
+ * (bullet-envs_amd/csrc/snk_world.hpp: closest_points_kernel) and the tests (tests/np_closest.py) are both written from
+ * this text.  It is the solver's narrow phase (csrc/snk_selfcol.hpp) run as a query: at a caller-given distance, for any
+ * subset of envs, writing tensors and touching no state.
+ *
+ * The query.  Geometry of the pose the state holds NOW, the pose snk_link_states reports.  `distance` (metres, finite,
+ * >= 0) is PyBullet's argument: a pair is FOUND when its distance is < distance (strict, as the solver's test against its
+ * breaking threshold), the distance taken between the margin-inflated shapes: the GJK distance of the cores less both
+ * collision margins.  At distance = snk_params_derived(...)[0], the handle's own breaking threshold, the found pairs are
+ * exactly the link-link and link-box contacts the next substep's streamed-row solve would build rows for; above it the
+ * call is a proximity sensor.  (hull_sides 0: the implicit cylinder's GJK runs on here to a relative duality gap of 1e-6,
+ * the solver's stops at 1e-5 -- its distances are good to 1e-7 m, its normals to 3e-3 rad only --, so a pair within 1e-7 m
+ * of the threshold may be found by one and not by the other.)  The link-link part is computed whatever self_collision says: it is a geometry query.  The
+ * box is the static one (obstacle 1: obstacle_pos, identity rotation) or the free one where it is now (obstacle 2: centre
+ * and quaternion as snk_get_box reports them, R(quat) formed as snk_contacts forms it).  On a handle without an obstacle
+ * the box part is empty, not refused.
+ *
+ * The narrow phase, for a cylinder A and B = the box or a cylinder b > a.  Tier 0: GJK on the core shapes (the 32-gon hull
+ * or the implicit cylinder, as hull_sides says; the box's core is smaller than the nominal box by the margin), margin mg =
+ * collision_margin.  Tier 1, when those cores overlap: GJK on cores shrunk by 6 mm, mg = collision_margin + 6 mm.  With
+ * witness points pa, pb at core distance d: normal n = (pa - pb) / d, distance d - 2 mg, and the reported points lie on the
+ * inflated surfaces: P = pa - n mg on A, PB = pb + n mg on B.  Tier 2, when the shrunk cores overlap too: the line of
+ * centres -- n = (c_A - c_B) / |c_A - c_B| (for coincident centres (0, 0, 1), against the box (-1, 0, 0)), distance
+ * -2 (collision_margin + 6 mm), P = PB = the midpoint of the centres, against the box the cylinder's centre.  The broad
+ * phase (bounding spheres) and the separating-axis culls in front of it take `distance` and are conservative: a culled
+ * pair is one the narrow phase would reject.  One point per pair (PyBullet reports up to four per pair, from its cache).
+ *
+ * Slots.  One env's table has snk_closest_slots(h, max_pairs) = 2n + max_pairs slots of SNK_CONTACT_FLOATS floats.
+ *   slots 0 .. 2n - 1   slot c is the pair (cylinder c, box): dense; live only if found and flags has SNK_PAIRS_BOX.
+ *   slots 2n ..         the found link-link pairs, compact, in the solver's order: by offset b - a = 2, 3, ..., then by a
+ *                       (consecutive cylinders, b - a = 1, are parent and child and are no pair).  When more than
+ *                       max_pairs are found, the first max_pairs in that order are written.
+ * max_pairs is in 0 .. snk_link_pairs(h) = C(2n, 2) - (2n - 1): 465 for 16 links, 1953 for 32.
+ * The record:
+ *   0-2    the point on A = cylinder a, world coordinates, on the inflated surface
+ *   3-5    the point on B (the box, or cylinder b > a)
+ *   6-8    the unit normal on B, towards A (link-box: from the box to the link, as the solver has it)
+ *   9      the distance (negative: penetration); float 0-2 less float 3-5 is float 6-8 times it
+ *   10     the tier: 0, 1 or 2
+ *   11     0 (no force: these contacts carry no stored impulse)
+ *   12     a
+ *   13     b; 2n for the box.  (Small integers: exact as floats.)
+ *   14     1.0 if the slot is live
+ *   15     0.
+ * A slot that is not live is sixteen zeros.
+ *
+ * Outputs, per requested env (row):
+ *   points_dev     [n_rows][2n + max_pairs][16] f32, 16-byte aligned;
+ *   clearance_dev  [n_rows][2][2n] f32: row 0 per cylinder its distance to the box, row 1 per cylinder the least distance
+ *                  over the link-link pairs it belongs to -- each min(found distances, distance), so that `distance` reads
+ *                  "nothing within reach".  Row 1 counts every found pair, those beyond max_pairs included; a part not
+ *                  asked for in flags is filled with `distance`;
+ *   count_dev      [n_rows][2] i32: box pairs found, link-link pairs found -- the second NOT clipped to max_pairs, so that
+ *                  truncation shows.
+ * Each may be NULL; all three NULL is refused.
+ *
+ * snk_closest_points follows snk_contacts' shape and rules: env_ids_dev [n_rows] i32 or NULL (envs 0 .. n_rows - 1), ids may
+ * repeat and come in any order; an id outside 0 .. n_envs - 1 reads nothing and ALL its outputs are zeros (its clearance
+ * too).  Asynchronous on `stream`, one launch (one wave per row), no atomics to memory and no waits; it does not
+ * synchronise, copy or allocate.  Bytes beyond the outputs are left alone; nothing of the handle's state is written.
+ * Refused, naming the argument: a null or poisoned handle; n_rows < 1; a non-finite or negative distance; zero or unknown
+ * bits in flags; all three outputs null; a misaligned points_dev; max_pairs outside 0 .. snk_link_pairs(h).
+ * snk_closest_points_host: the same with HOST buffers; it synchronises the device first, like the state accessors, and also
+ * refuses an env id outside 0 .. n_envs - 1 and n_rows above n_envs without ids, each with its index.
+ * snk_link_pairs, snk_closest_slots: 0, with snk_last_error set, for a null or poisoned handle (snk_closest_slots also for a
+ * max_pairs out of range).
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SNK_PAIRS_BOX   1   /* flags: the 2n (cylinder, obstacle box) pairs */
+#define SNK_PAIRS_LINKS 2   /* flags: the link-link pairs (every cylinder pair except consecutive cylinders) */
+int32_t snk_link_pairs(const snk_handle* h);
+int32_t snk_closest_slots(const snk_handle* h, int32_t max_pairs);
+int snk_closest_points(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, float distance, int32_t flags,
+                       int32_t max_pairs, float* points_dev, float* clearance_dev, int32_t* count_dev, void* stream);
+int snk_closest_points_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float distance, int32_t flags,
+                            int32_t max_pairs, float* points, float* clearance, int32_t* count);
 
 /* State access (host buffers), for parity tests and checkpointing.  These calls (and snk_get_obs,
  * snk_mean_height, snk_link_positions, snk_set/get_ground_friction) synchronise the device first, so a step
@@ -570,8 +649,8 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
  * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
  * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction,
  * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) and snk_render / snk_render_host and the tensor seam
- * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host), snk_contacts(_host)) return
- * non-zero -- and snk_reset_pose_floats and snk_contact_slots 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
+ * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host), snk_contacts(_host), snk_closest_points(_host)) return
+ * non-zero -- and snk_reset_pose_floats, snk_contact_slots, snk_link_pairs and snk_closest_slots 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */
 int snk_debug_raise_alarm(snk_handle* h);
