@@ -6,6 +6,7 @@ or through the top-level shim:  import bullet_envs_amd as pkg
 """
 from ._lib import SnkParams, Snapshot, Stepper, default_params, load, LIB_PATH, trace_row_floats, trace_to_lists  # noqa: F401
 from ._lib import PAIRS_BOX, PAIRS_LINKS  # noqa: F401  (flags of closest_points)
+from ._lib import RAYS_ALL, RAYS_BOX, RAYS_GROUND, RAYS_SNAKE  # noqa: F401  (flags of ray_test)
 from .snake_env import (CloudpickleWrapper, Snake, SnakeGymEnv, SnakeVecEnv, SubprocVecEnv, VecEnv,  # noqa: F401
                         params_from_args)
 from .device_env import DeviceVecEnv, DeviceWorld, ShardedVecEnv  # noqa: F401

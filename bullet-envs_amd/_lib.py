@@ -120,6 +120,8 @@ SYMBOLS = {
     "snk_params_derived": (C.c_int, [C.c_void_p, _D]),
     "snk_render": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "snk_render_host": (C.c_int, [_vp, _I32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _U8, _F, _I32]),
+    "snk_ray_test": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "snk_ray_test_host": (C.c_int, [_vp, _I32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, _F]),
     "snk_view_matrix_ypr": (C.c_int, [_F, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _F]),
     "snk_projection_fov": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, _F]),
     "snk_last_error": (C.c_char_p, []),
@@ -131,6 +133,13 @@ PAIRS_LINKS = 2        # SNK_PAIRS_LINKS: its link-link pairs
 CONTACT_FLOATS = 16     # SNK_CONTACT_FLOATS, floats per contact slot of snk_contacts: [point on the body 3 | point on the ground 3 |
 #                         normal 3 | distance | normal force N | impulse | cylinder (2n: the box) | j | live | 0]
 LINK_STATE_FLOATS = 16  # floats per row of snk_link_states: [COM 3 | quat xyzw 4 | link origin 3 | COM velocity 3 | omega 3]
+RAY_FLOATS = 6          # SNK_RAY_FLOATS, a ray of snk_ray_test: [from 3 | to 3]
+HIT_FLOATS = 8          # SNK_HIT_FLOATS, its record: [fraction | position 3 | normal 3 | primitive id (-1: a miss)]
+RAYS_GROUND = 1         # SNK_RAYS_GROUND / _SNAKE / _BOX: what the rays can hit
+RAYS_SNAKE = 2
+RAYS_BOX = 4
+RAYS_SHARED = 8         # SNK_RAYS_SHARED: one set of rays [n_rays, 6] for every row
+RAYS_ALL = RAYS_GROUND | RAYS_SNAKE | RAYS_BOX
 
 #: the camera behind render() / getCameraImage when the caller gives no matrices [U]: the reference calls
 #: resetDebugVisualizerCamera(1.5, -30, -90, [1.28, 0, 0]) right before its getCameraImage (snake.py:322-327) -- the reading
@@ -780,6 +789,32 @@ class Stepper:
         check(self.lib.snk_render(self.h, ids_ptr or None, int(n_images), cams_ptr or None, 1 if shared else 0, int(width),
                                   int(height), int(flags), rgba_ptr or None, depth_ptr or None, seg_ptr or None,
                                   stream or None), "snk_render")
+
+    # ---- the ray test (snk_ray_test / snk_ray_test_host) ----
+    def ray_test(self, rays, env_ids=None, parent_row=-1, flags=RAYS_ALL):
+        """snk_ray_test_host: hit records [k, n_rays, 8] float32 of the envs `env_ids` (None: all; ids may repeat, any
+        order) at the current pose.  rays: [k, n_rays, 6] float32, [from 3 | to 3] per ray, or [n_rays, 6]: one set shared by
+        every row.  parent_row -1: world coordinates; r: the frame of row r of link_states of the row's own env (origin the
+        link's COM; PyBullet's parentLinkIndex L is row L + 1).  flags: RAYS_GROUND | RAYS_SNAKE | RAYS_BOX, what can be
+        hit.  A record is [hit fraction | position 3 | outward normal 3 | primitive id: 0 ground, 1 + c cylinder c, 1 + 2n
+        the box], world frame; a miss is [1, 0, 0, 0, 0, 0, 0, -1] (snk.h, "The ray test")."""
+        ids, k, idp = self._ids(env_ids)
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim not in (2, 3) or rays.shape[-1] != RAY_FLOATS or (rays.ndim == 3 and rays.shape[0] != k):
+            raise ValueError("rays must be [%d, n_rays, 6] or [n_rays, 6], got %s" % (k, rays.shape))
+        shared = rays.ndim == 2
+        R = int(rays.shape[-2])
+        ok = k >= 1 and 1 <= R <= 65536 and k * R <= 1 << 28      # (the library refuses the rest by name; no huge buffers first)
+        hits = np.zeros((k, R, HIT_FLOATS) if ok else (1,), np.float32)
+        check(self.lib.snk_ray_test_host(self.h, idp, k, fptr(rays) if rays.size else None, R, int(parent_row),
+                                         (int(flags) & ~RAYS_SHARED) | (RAYS_SHARED if shared else 0), fptr(hits)),
+              "snk_ray_test_host")
+        return hits
+
+    def ray_test_device(self, ids_ptr, n_rows, rays_ptr, n_rays, parent_row, flags, hits_ptr, stream=0):
+        """snk_ray_test: every buffer a device pointer (ids 0: envs 0 .. n_rows - 1), asynchronous on `stream`."""
+        check(self.lib.snk_ray_test(self.h, ids_ptr or None, int(n_rows), rays_ptr or None, int(n_rays), int(parent_row),
+                                    int(flags), hits_ptr or None, stream or None), "snk_ray_test")
 
     def timing_enable(self, capacity):
         check(self.lib.snk_timing_enable(self.h, int(capacity)), "snk_timing_enable")

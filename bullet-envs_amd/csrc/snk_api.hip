@@ -241,10 +241,10 @@ int check_alarm(const snk_handle* h) {
 //   D I A  snk_get_state  snk_set_state  snk_get_manifold  snk_set_manifold  snk_get_box  snk_set_box  snk_get_obs
 //          snk_mean_height  snk_link_positions  snk_joint3_reaction_fz  snk_set_ground_friction  snk_get_reset_pose
 //          snk_set_reset_pose  snk_debug_set_tickets  snk_render_host  snk_link_states_host  snk_copy_envs_host
-//          snk_debug_rows  snk_contacts_host
+//          snk_debug_rows  snk_contacts_host  snk_closest_points_host  snk_ray_test_host
 //   D . A  snk_reset  snk_step  snk_step_packed  snk_step_traced  snk_reset_host  snk_step_host  snk_step_traced_host
 //          snk_substep_host  snk_set_reset_pose_dev  snk_render  snk_substep  snk_observe  snk_link_states  snk_copy_envs
-//          snk_contacts  snk_contact_slots (returns 0)
+//          snk_contacts  snk_closest_points  snk_ray_test  snk_contact_slots (returns 0)
 //   . . A  snk_reset_pose_floats (returns 0)
 //   D I .  snk_get_ground_friction  snk_contact_overflow  snk_contact_histogram  snk_contact_histogram_enable
 //          snk_destroy (the two calls bare: errors ignored, snk_last_error untouched)

@@ -1,5 +1,5 @@
-// snk_render.hip -- the batched ray caster behind snk_render / snk_render_host, and PyBullet's two camera-matrix helpers
-// (include/snk.h: "The rendered scene").  A translation unit and a code object of its own: build.py compiles it to an
+// snk_render.hip -- the batched ray caster behind snk_render / snk_render_host and snk_ray_test / snk_ray_test_host, and
+// PyBullet's two camera-matrix helpers (include/snk.h: "The rendered scene", "The ray test").  A translation unit and a code object of its own: build.py compiles it to an
 // object and links it into libsnk.so next to snk_api.hip, whose kernels it does not touch.
 #include <hip/hip_runtime.h>
 
@@ -28,6 +28,27 @@ int check_shape(const char* who, const snk_handle* h, int32_t n_images, int32_t 
         return api_fail(w + ": n_images x width x height is more than 2^31 - 1 pixels");
     if (flags & ~SNK_RENDER_SHADOW) return api_fail(w + ": unknown bits in flags (SNK_RENDER_SHADOW is the only one)");
     return 0;
+}
+
+static_assert(snk::kRayFloats == SNK_RAY_FLOATS && snk::kHitFloats == SNK_HIT_FLOATS, "the kernels' ray and record are the header's");
+
+// the same for both forms of snk_ray_test
+int check_rays(const char* who, const snk_handle* h, int32_t n_rows, int32_t n_rays, int32_t flags) {
+    const std::string w(who);
+    if (!h) return api_fail(w + ": null handle (h)");
+    if (n_rows < 1) return api_fail(w + ": n_rows must be at least 1");
+    if (n_rays < 1 || n_rays > 65536) return api_fail(w + ": n_rays must be in 1 .. 65536");
+    if ((long long)n_rows * n_rays > (1LL << 28)) return api_fail(w + ": n_rows x n_rays is more than 2^28 rays");
+    const int32_t kinds = SNK_RAYS_GROUND | SNK_RAYS_SNAKE | SNK_RAYS_BOX;
+    if (flags & ~(kinds | SNK_RAYS_SHARED))
+        return api_fail(w + ": unknown bits in flags (SNK_RAYS_GROUND, SNK_RAYS_SNAKE, SNK_RAYS_BOX, SNK_RAYS_SHARED)");
+    if (!(flags & kinds)) return api_fail(w + ": flags name nothing to hit (SNK_RAYS_GROUND, SNK_RAYS_SNAKE, SNK_RAYS_BOX)");
+    return 0;
+}
+int check_parent(const char* who, int32_t parent_row, int n) {
+    if (parent_row >= -1 && parent_row < snk::link_rows(n)) return 0;
+    return api_fail(std::string(who) + ": parent_row " + std::to_string(parent_row) + " is outside -1 .. " +
+                    std::to_string(snk::link_rows(n) - 1));
 }
 
 }  // namespace
@@ -91,6 +112,65 @@ int snk_render_host(snk_handle* h, const int32_t* env_ids, int32_t n_images, con
     if (c.ok() && snk_render(h, d_ids, n_images, d_cam, shared_camera, width, height, flags, d_rgba, d_depth, d_seg, nullptr))
         return 1;
     return c.finish("snk_render_host");
+}
+
+int snk_ray_test(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, const float* rays_dev, int32_t n_rays,
+                 int32_t parent_row, int32_t flags, float* hits_dev, void* stream) {
+    if (check_rays("snk_ray_test", h, n_rows, n_rays, flags)) return 1;
+    if (!rays_dev) return api_fail("snk_ray_test: null rays_dev");
+    if (reinterpret_cast<uintptr_t>(rays_dev) % 4 != 0) return api_fail("snk_ray_test: rays_dev must be 4-byte aligned");
+    if (!hits_dev) return api_fail("snk_ray_test: null hits_dev");
+    if (reinterpret_cast<uintptr_t>(hits_dev) % 16 != 0)
+        return api_fail("snk_ray_test: hits_dev must be 16-byte aligned (the records leave as 16-byte stores)");
+    snk::WorldView v;
+    if (snk::world_view(h, false, &v)) return 1;
+    if (check_parent("snk_ray_test", parent_row, v.n)) return 1;
+    // the render's scratch with the render's growth rule: a row counts as an image, its camera's room left unused
+    const size_t pf = (size_t)snk::prim_stride(v.n), need = (size_t)n_rows * (pf + snk::kCamFloats) * sizeof(float);
+    float* prims = snk::render_scratch(h, need);
+    if (!prims) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+        hipLaunchKernelGGL((snk::ray_scene_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64),
+                           0, st, v.d_model, v.d_recs, v.d_box, v.d_links, env_ids_dev, parent_row, prims, n_rows, v.n_envs);
+        return 0;
+    });
+    if (rc == snk::kUnsupported) return api_fail("snk_ray_test: unsupported n_modules (16 or 32)");
+    const int chunks = (n_rays + snk::kRayChunk - 1) / snk::kRayChunk;
+    const long long work = (long long)n_rows * chunks;
+    const unsigned blocks = (unsigned)(work < (1LL << 20) ? work : (1LL << 20));
+    hipLaunchKernelGGL(snk::ray_cast_kernel, dim3(blocks), dim3(snk::kRayChunk), 0, st, prims, rays_dev,
+                       (flags & SNK_RAYS_SHARED) ? 1 : 0, 2 * v.n, n_rays, chunks, work, flags, hits_dev);
+    return snk::launch_ok("snk_ray_test");
+}
+
+int snk_ray_test_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, const float* rays, int32_t n_rays,
+                      int32_t parent_row, int32_t flags, float* hits) {
+    if (check_rays("snk_ray_test_host", h, n_rows, n_rays, flags)) return 1;
+    if (!rays) return api_fail("snk_ray_test_host: null rays");
+    if (!hits) return api_fail("snk_ray_test_host: null hits");
+    snk::WorldView v;
+    if (snk::world_view(h, true, &v)) return 1;
+    if (check_parent("snk_ray_test_host", parent_row, v.n)) return 1;
+    if (env_ids ? snk::check_env_ids("snk_ray_test_host", "env_ids", env_ids, n_rows, v.n_envs)
+                : snk::check_count_without_ids("snk_ray_test_host", "n_rows", n_rows, v.n_envs)) return 1;
+    const bool shared = (flags & SNK_RAYS_SHARED) != 0;
+    const size_t nray = (shared ? 1 : (size_t)n_rows) * (size_t)n_rays, total = (size_t)n_rows * (size_t)n_rays;
+    for (size_t k = 0; k < nray * SNK_RAY_FLOATS; k++)
+        if (!std::isfinite(rays[k])) {
+            char msg[200];
+            const size_t ray = k / SNK_RAY_FLOATS;
+            if (shared) snprintf(msg, sizeof(msg), "snk_ray_test_host: rays[%zu][%zu] is not finite", ray, k % SNK_RAY_FLOATS);
+            else snprintf(msg, sizeof(msg), "snk_ray_test_host: rays[%zu][%zu][%zu] is not finite", ray / (size_t)n_rays,
+                          ray % (size_t)n_rays, k % SNK_RAY_FLOATS);
+            return api_fail(msg);
+        }
+    snk::HostCall c;
+    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const float* d_rays = c.in(rays, nray * SNK_RAY_FLOATS * sizeof(float));
+    float* d_hits = c.out(hits, total * SNK_HIT_FLOATS * sizeof(float));
+    if (c.ok() && snk_ray_test(h, d_ids, n_rows, d_rays, n_rays, parent_row, flags, d_hits, nullptr)) return 1;
+    return c.finish("snk_ray_test_host");
 }
 
 int snk_view_matrix_ypr(const float target[3], float distance, float yaw_deg, float pitch_deg, float roll_deg, int32_t up_axis,

@@ -1,5 +1,6 @@
 // snk_render.hpp -- device parts of the ray caster (include/snk.h: "The rendered scene" is the contract): the per-image
-// tables render_scene_kernel writes and render_rays_kernel reads, the ray / solid intersections, the shading.
+// tables render_scene_kernel writes and render_rays_kernel reads, the ray / solid intersections, the shading -- and of
+// the ray test ("The ray test"): the same tables and intersections under caller-given rays, hit records for colours.
 // Only snk_render.hip includes this: the step kernels' code object (snk_api.hip) has none of it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +30,52 @@ constexpr float kRenderTie = 2e-4f;      // a later primitive replaces the kept 
 constexpr double kLightLen = 0.98615414616580109;
 constexpr float kLx = (float)(0.4 / kLightLen), kLy = (float)(-0.3 / kLightLen), kLz = (float)(0.85 / kLightLen);
 
+// The solids of one env as table entries at P, from the forward kinematics in L: lane = cylinder, lane 0 the box too.
+// What render_scene_kernel and ray_scene_kernel share.  !known (an env id outside the handle): nothing there.
+// QT: the arithmetic of the free box's rotation from its quaternion, rounded to float32 at the end -- float for the
+// render, as it always was; double for the ray test, whose records carry a column of that matrix as the hit's normal.
+template <int N, bool V2, typename QT>
+__device__ __forceinline__ void scene_prims(const Lds<N, V2>& L, const DevModel& M, const float* box_all, int env,
+                                            bool known, int lane, float* P) {
+    if (lane < 2 * N) {
+        const int c = lane;
+        float* o = P + c * kPrimFloats;
+        f3 ctr = mk3(0.f, 0.f, 0.f), ax = mk3(0.f, 0.f, 1.f);
+        float hl = -1.f;
+        if (known) {
+            const int b = M.cyl_body[c];
+            ctr = ld3(L.o[b]) + mulRv(L.R[b], ld3(M.cyl_c[c]));
+            ax = mulRv(L.R[b], mk3(M.cyl_R[c][2], M.cyl_R[c][5], M.cyl_R[c][8]));
+            hl = M.cyl_hl;
+        }
+        o[0] = ctr.x; o[1] = ctr.y; o[2] = ctr.z; o[3] = M.cyl_r;
+        o[4] = ax.x; o[5] = ax.y; o[6] = ax.z; o[7] = hl;
+    }
+    if (lane == 0) {
+        float* o = P + 2 * N * kPrimFloats;
+        float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+        f3 ctr = ld3(M.obs_c), hh = mk3(-1.f, -1.f, -1.f);
+        if (known && M.obstacle != 0) hh = ld3(M.obs_h);
+        if (known && M.obstacle == 2 && box_all) {
+            const float* bx = box_all + (size_t)env * kBoxFloats;      // [pos 3 | quat xyzw 4 | ...]
+            ctr = ld3(bx);
+            const QT qx = bx[3], qy = bx[4], qz = bx[5], qw = bx[6];
+            const QT s2 = QT(2) / (qx * qx + qy * qy + qz * qz + qw * qw);
+            const QT xs = qx * s2, ys = qy * s2, zs = qz * s2;
+            const QT wx = qw * xs, wy = qw * ys, wz = qw * zs;
+            const QT xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
+            R[0] = (float)(1 - (yy + zz)); R[1] = (float)(xy - wz); R[2] = (float)(xz + wy);
+            R[3] = (float)(xy + wz); R[4] = (float)(1 - (xx + zz)); R[5] = (float)(yz - wx);
+            R[6] = (float)(xz - wy); R[7] = (float)(yz + wx); R[8] = (float)(1 - (xx + yy));
+        }
+        o[0] = ctr.x; o[1] = ctr.y; o[2] = ctr.z;
+        o[3] = hh.x; o[4] = hh.y; o[5] = hh.z;
+#pragma unroll
+        for (int i = 0; i < 9; i++) o[6 + i] = R[i];      // (6 + 8 = 14: inside the entry's 16 floats)
+        o[15] = 0.f;
+    }
+}
+
 // ----------------------------------------------------------------------------------
 // render_scene_kernel: one wave per image.  The env's record -> forward kinematics -> lane = cylinder.
 // Plain loads of the records, the free boxes and the model; nothing of the handle's state is written.
@@ -54,43 +101,7 @@ __global__ __launch_bounds__(64) void render_scene_kernel(const DevModel* __rest
             load_rec(L, recs + (size_t)env * LT::REC, lane);
             fk_vel(L, M, lane);
         }
-        if (lane < 2 * N) {
-            const int c = lane;
-            float* o = P + c * kPrimFloats;
-            f3 ctr = mk3(0.f, 0.f, 0.f), ax = mk3(0.f, 0.f, 1.f);
-            float hl = -1.f;
-            if (known) {
-                const int b = M.cyl_body[c];
-                ctr = ld3(L.o[b]) + mulRv(L.R[b], ld3(M.cyl_c[c]));
-                ax = mulRv(L.R[b], mk3(M.cyl_R[c][2], M.cyl_R[c][5], M.cyl_R[c][8]));
-                hl = M.cyl_hl;
-            }
-            o[0] = ctr.x; o[1] = ctr.y; o[2] = ctr.z; o[3] = M.cyl_r;
-            o[4] = ax.x; o[5] = ax.y; o[6] = ax.z; o[7] = hl;
-        }
-        if (lane == 0) {
-            float* o = P + 2 * N * kPrimFloats;
-            float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-            f3 ctr = ld3(M.obs_c), hh = mk3(-1.f, -1.f, -1.f);
-            if (known && M.obstacle != 0) hh = ld3(M.obs_h);
-            if (known && M.obstacle == 2 && box_all) {
-                const float* bx = box_all + (size_t)env * kBoxFloats;      // [pos 3 | quat xyzw 4 | ...]
-                ctr = ld3(bx);
-                const float qx = bx[3], qy = bx[4], qz = bx[5], qw = bx[6];
-                const float s2 = 2.0f / (qx * qx + qy * qy + qz * qz + qw * qw);
-                const float xs = qx * s2, ys = qy * s2, zs = qz * s2;
-                const float wx = qw * xs, wy = qw * ys, wz = qw * zs;
-                const float xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
-                R[0] = 1 - (yy + zz); R[1] = xy - wz; R[2] = xz + wy;
-                R[3] = xy + wz; R[4] = 1 - (xx + zz); R[5] = yz - wx;
-                R[6] = xz - wy; R[7] = yz + wx; R[8] = 1 - (xx + yy);
-            }
-            o[0] = ctr.x; o[1] = ctr.y; o[2] = ctr.z;
-            o[3] = hh.x; o[4] = hh.y; o[5] = hh.z;
-#pragma unroll
-            for (int i = 0; i < 9; i++) o[6 + i] = R[i];      // (6 + 8 = 14: inside the entry's 16 floats)
-            o[15] = 0.f;
-        }
+        scene_prims<N, V2, float>(L, M, box_all, env, known, lane, P);
         if (lane == 1) {
             // M = P V and its inverse (cofactors), in float64: the near and far planes of a camera are orders of
             // magnitude apart, and every ray of the image goes through this inverse
@@ -298,6 +309,174 @@ __global__ __launch_bounds__(256) void render_rays_kernel(const float* __restric
             if (seg) seg[at] = id;
         }
         __syncthreads();      // (the table is replaced by the next work item's)
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// The ray test (include/snk.h: "The ray test" is the contract).
+// A row's table is the render's, with the parent frame of the row's rays in the entry the render leaves unused:
+//   entry 2n + 1  [R 9, row-major, frame -> world | origin 3 | known: 1, or 0 for an env id outside the handle | 3 unused]
+// ----------------------------------------------------------------------------------
+constexpr int kRayChunk = 256;            // rays of one workgroup, one per thread
+constexpr int kRayFloats = 6, kHitFloats = 8;
+// The staging image of a chunk's records: float j of ray w at hits[j * kHitStride + w].  The writes go lane = ray,
+// consecutive banks.  The read of float 4 p + e of ray w by the lane that stores quad 2 w + p sits at bank
+// ((4 p + e) * 260 + w) mod 32 = (16 p + 4 e + w) mod 32 (ds_read_b32: dword address mod 32 within a 32-lane half):
+// distinct over p = 0..1 and the 16 consecutive rays of a half.  (Any stride = 4 mod 8 does it; 260 is the first >= 256.)
+constexpr int kHitStride = 260;
+
+// ray_scene_kernel: one wave per row.  render_scene_kernel without a camera, plus the frame of link-table row
+// `parent_row` of the row's own env (-1: the world's) as link_state_kernel forms it: Rw = R(body) R(link in body),
+// origin = the link's COM.
+template <int N, bool V2>
+__global__ __launch_bounds__(64) void ray_scene_kernel(const DevModel* __restrict__ Mp, const float* __restrict__ recs,
+                                                       const float* __restrict__ box_all, const float* __restrict__ links,
+                                                       const int32_t* __restrict__ env_ids, int parent_row,
+                                                       float* __restrict__ prims, int n_rows, int n_envs) {
+    using LT = Lds<N, V2>;
+    __shared__ float4 smem_raw[(sizeof(LT) + 15) / 16];
+    LT& L = *reinterpret_cast<LT*>(smem_raw);
+    const DevModel& M = *Mp;
+    const int lane = threadIdx.x;
+    for (int row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        const int env = env_ids ? env_ids[row] : row;
+        float* P = prims + (size_t)row * prim_stride(N);
+        const bool known = env >= 0 && env < n_envs;
+        if (known) {
+            load_rec(L, recs + (size_t)env * LT::REC, lane);
+            fk_vel(L, M, lane);
+        }
+        scene_prims<N, V2, double>(L, M, box_all, env, known, lane, P);
+        if (lane == 1) {
+            float* o = P + (2 * N + 1) * kPrimFloats;
+            float Rw[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+            f3 org = mk3(0.f, 0.f, 0.f);
+            if (known && parent_row >= 0) {
+                const float* T = links + (size_t)parent_row * kLinkFloats;
+                const int b = __float_as_int(T[15]);
+                const float* Rb = L.R[b];
+#pragma unroll
+                for (int i = 0; i < 3; i++)
+#pragma unroll
+                    for (int j = 0; j < 3; j++)
+                        Rw[3 * i + j] = Rb[3 * i] * T[j] + Rb[3 * i + 1] * T[3 + j] + Rb[3 * i + 2] * T[6 + j];
+                const f3 ow = ld3(L.o[b]) + mulRv(Rb, ld3(T + 9));
+                org = ow + mulRv(Rw, ld3(T + 12));
+            }
+#pragma unroll
+            for (int i = 0; i < 9; i++) o[i] = Rw[i];
+            o[9] = org.x; o[10] = org.y; o[11] = org.z;
+            o[12] = known ? 1.f : 0.f;
+            o[13] = 0.f; o[14] = 0.f; o[15] = 0.f;
+        }
+        lds_sync();      // (the row's record is read by every lane above: the next row's load waits for them)
+    }
+}
+
+// ray_cast_kernel: one 256-thread workgroup per (row, chunk of 256 rays); thread = ray.
+// A ray is 24 bytes and a record 32: thread = ray accesses of global memory would stride.  So the chunk's 6 x 256 input
+// floats come in as consecutive dwords (lane i of a load reads dword i: the rays are 4-byte aligned, nothing more) and
+// each thread takes its ray from LDS as three 8-byte reads (24 t is a multiple of 8; ds_read_b64 banks on the dword
+// address mod 64, and 6 t mod 64 are 32 distinct even numbers over a half: no conflicts).  The records are staged
+// (kHitStride above) and leave as consecutive float4s: a wave-wide store writes 1 KB, every 128-byte line whole.
+__global__ __launch_bounds__(kRayChunk) void ray_cast_kernel(const float* __restrict__ prims, const float* __restrict__ rays,
+                                                             int shared_rays, int ncyl, int n_rays, int chunks,
+                                                             long long n_work, int flags, float* __restrict__ hits) {
+    __shared__ float4 T4[prim_stride(kMaxN) / 4];
+    __shared__ float2 in2[kRayChunk * kRayFloats / 2];
+    __shared__ float stage[kHitFloats * kHitStride];
+    const float* T = reinterpret_cast<const float*>(T4);
+    float* in = reinterpret_cast<float*>(in2);
+    const int tid = threadIdx.x;
+    const int pstride = (ncyl + 2) * kPrimFloats;                 // = prim_stride(n), ncyl = 2 n
+    for (long long w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const long long row = w / chunks;
+        const int r0 = (int)(w - row * chunks) * kRayChunk;
+        const int cnt = n_rays - r0 < kRayChunk ? n_rays - r0 : kRayChunk;      // rays of this chunk: nothing beyond them is touched
+        {
+            const float4* src = reinterpret_cast<const float4*>(prims + (size_t)row * pstride);
+            const int nq = (ncyl + 2) * (kPrimFloats / 4);           // cylinders, the box and the frame
+            for (int q = tid; q < nq; q += kRayChunk) T4[q] = src[q];
+            const float* rs = rays + ((size_t)(shared_rays ? 0 : row) * (size_t)n_rays + (size_t)r0) * kRayFloats;
+#pragma unroll
+            for (int k = 0; k < kRayFloats; k++) {
+                const int i = kRayChunk * k + tid;
+                if (i < cnt * kRayFloats) in[i] = rs[i];
+            }
+        }
+        __syncthreads();
+        if (tid < cnt) {
+            const float2 a = in2[3 * tid], b = in2[3 * tid + 1], c = in2[3 * tid + 2];
+            const float* F = T + (ncyl + 1) * kPrimFloats;            // [R 9 | origin 3 | known]
+            const bool finite = isfinite(a.x) && isfinite(a.y) && isfinite(b.x) && isfinite(b.y) && isfinite(c.x) && isfinite(c.y);
+            const f3 org = ld3(F + 9);
+            const f3 o = org + mulRv(F, mk3(a.x, a.y, b.x));
+            const f3 pt = org + mulRv(F, mk3(b.y, c.x, c.y));
+            f3 d = pt - o;
+            const float tf = sqrtf(dot(d, d));
+            float tbest = kRenderInf;
+            int id = -1;
+            f3 nrm = mk3(0.f, 0.f, 1.f);
+            // a zero-length ray, a non-finite one (or one whose length is) and an env outside the handle hit nothing
+            if (finite && tf > 0.f && tf < kRenderInf && F[12] != 0.f) {
+                d = mk3(d.x / tf, d.y / tf, d.z / tf);      // (a division each: the ranges carry the direction's round-off)
+                // nearest hit: a later primitive replaces the kept one only when it is nearer by more than kRenderTie
+                if ((flags & SNK_RAYS_GROUND) && d.z != 0.f) {
+                    const float t = -o.z / d.z;
+                    if (t >= 0.f && t <= tf) { tbest = t; id = 0; }
+                }
+                if (flags & SNK_RAYS_SNAKE)
+                    for (int cy = 0; cy < ncyl; cy++) {
+                        const float* p = T + cy * kPrimFloats;
+                        const f3 A = ld3(p + 4);
+                        float tin, tout, dp;
+                        bool cap;
+                        if (cyl_interval(o - ld3(p), d, A, p[3], p[7], tin, tout, cap, dp) && tin >= 0.f && tin <= tf &&
+                            tin < tbest - kRenderTie) {
+                            tbest = tin; id = 1 + cy;
+                            if (cap) nrm = A * (dp > 0.f ? -1.f : 1.f);
+                            else {
+                                const f3 m = o - ld3(p);
+                                const f3 q = m + d * tin;
+                                nrm = (q - A * dot(q, A)) * (1.0f / p[3]);
+                            }
+                        }
+                    }
+                if (flags & SNK_RAYS_BOX) {
+                    const float* p = T + ncyl * kPrimFloats;
+                    float tin, tout, sign;
+                    int axis;
+                    if (box_interval(o - ld3(p), d, p, tin, tout, axis, sign) && tin >= 0.f && tin <= tf && tin < tbest - kRenderTie) {
+                        tbest = tin; id = 1 + ncyl;
+                        nrm = mk3(p[6 + axis], p[9 + axis], p[12 + axis]) * sign;
+                    }
+                }
+            }
+            // the miss record is [1, 0 x 6, -1]: never zeros, which would read as the ground hit at the ray's origin
+            float v[kHitFloats] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, -1.f};
+            if (id >= 0) {
+                const f3 X = o + d * tbest;
+                v[0] = tbest / tf;
+                v[1] = X.x; v[2] = X.y; v[3] = X.z;
+                v[4] = nrm.x; v[5] = nrm.y; v[6] = nrm.z;
+                v[7] = (float)id;
+            }
+#pragma unroll
+            for (int j = 0; j < kHitFloats; j++) stage[j * kHitStride + tid] = v[j];
+        }
+        __syncthreads();
+        float4* dst = reinterpret_cast<float4*>(hits + ((size_t)row * (size_t)n_rays + (size_t)r0) * kHitFloats);
+        const int quads = cnt * (kHitFloats / 4);
+#pragma unroll
+        for (int k = 0; k < kHitFloats / 4; k++) {
+            const int Q = kRayChunk * k + tid;
+            if (Q < quads) {
+                const int ray = Q >> 1, f0 = 4 * (Q & 1);
+                dst[Q] = make_float4(stage[f0 * kHitStride + ray], stage[(f0 + 1) * kHitStride + ray],
+                                     stage[(f0 + 2) * kHitStride + ray], stage[(f0 + 3) * kHitStride + ray]);
+            }
+        }
+        __syncthreads();      // (the table and both staging images are replaced by the next work item's)
     }
 }
 

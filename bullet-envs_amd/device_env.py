@@ -356,6 +356,34 @@ class DeviceWorld(_TensorArgs):
                                            stream=self._stream())
         return out
 
+    def ray_test(self, rays, env_ids=None, parent_row=-1, flags=_lib.RAYS_ALL, out=None):
+        """[k, R, 8] float32: PyBullet's rayTestBatch for the envs `env_ids` (None: all; an int32 CUDA tensor or a sequence;
+        ids may repeat, any order; every ray of an id outside the handle misses), cast at the current pose by two launches
+        (snk_ray_test; include/snk.h has the contract).  rays: a float32 CUDA tensor [k, R, 6], [from 3 | to 3] per ray --
+        torch.cat((from, to), -1) -- or [R, 6]: one fan for every row.  parent_row -1: world coordinates; r: the frame of
+        row r of link_states of the row's own env (origin the link's COM; PyBullet's parentLinkIndex L is row L + 1).
+        flags: RAYS_GROUND | RAYS_SNAKE | RAYS_BOX, what can be hit.  A record is [hit fraction | position 3 | outward
+        normal 3 | primitive id: 0 ground, 1 + c cylinder c, 1 + 2n the box], world frame; a miss is [1, 0 x 6, -1]."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        if not isinstance(rays, t.Tensor) or rays.dim() not in (2, 3) or rays.shape[-1] != _lib.RAY_FLOATS or rays.shape[-2] < 1:
+            raise ValueError("rays must be a CUDA tensor [%d, R, 6] or [R, 6]" % k)
+        shared = rays.dim() == 2
+        R = int(rays.shape[-2])
+        rays = self._arg(rays, "rays", (t.float32,), (R, _lib.RAY_FLOATS) if shared else (k, R, _lib.RAY_FLOATS))
+        out = self._out(out, "out", (k, R, _lib.HIT_FLOATS))
+        self.stepper.ray_test_device(ids.data_ptr() if ids is not None else 0, k, rays.data_ptr(), R, parent_row,
+                                     (int(flags) & ~_lib.RAYS_SHARED) | (_lib.RAYS_SHARED if shared else 0), out.data_ptr(),
+                                     self._stream())
+        self._keep(ids, rays)
+        return out
+
+    def ranges(self, rays, env_ids=None, parent_row=-1, flags=_lib.RAYS_ALL):
+        """[k, R] float32: the range along every ray of ray_test, hit fraction x |to - from| in metres -- the ray's own
+        length where nothing is hit.  The reading of a range sensor riding on link row `parent_row`."""
+        hits = self.ray_test(rays, env_ids, parent_row, flags)
+        return hits[..., 0] * (rays[..., 3:6] - rays[..., 0:3]).norm(dim=-1)
+
     def reset(self, mask=None, out=None):
         """The soft reset (snake.py:96-99, 119-127) of the envs of `mask` (uint8 / bool [E]; None: all) onto their rows
         of the reset-pose table.  Returns the observations [E, 3n + 8]; rows of unmasked envs are left as `out` had them

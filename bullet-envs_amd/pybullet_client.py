@@ -27,6 +27,9 @@ cache (snk_contacts).  Link-link and link-block contacts are stateless in the ke
 
 getClosestPoints answers (snake, block) and (snake, snake) at a caller-given distance: the solver's narrow phase run as a
 query on the current pose (snk_closest_points), one point per pair, no forces.  Distances to the plane are refused.
+
+rayTest / rayTestBatch cast rays against the plane, the snake's link colliders and the block at the current pose
+(snk_ray_test): world rays, or rays riding on a link of the snake (parentObjectUniqueId, parentLinkIndex).
 """
 import math
 import os
@@ -388,3 +391,42 @@ class BulletClient(object):
         return [(0, self._SNAKE, other, int(links[int(r[12])]), link_b(r), tuple(float(v) for v in r[0:3]),
                  tuple(float(v) for v in r[3:6]), tuple(float(v) for v in r[6:9]), float(r[9]), 0.0, 0.0, zero3, 0.0, zero3)
                 for r in rows if r[14] != 0.0 and want_a in (-2, int(links[int(r[12])])) and want_b in (-2, link_b(r))]
+
+    def rayTestBatch(self, rayFromPositions, rayToPositions, parentObjectUniqueId=-1, parentLinkIndex=-1, **kw):
+        """PyBullet's list of (objectUniqueId, linkIndex, hitFraction, hitPosition, hitNormal), one per ray, from
+        snk_ray_test on the CURRENT pose (include/snk.h, "The ray test"): the first solid each ray enters -- the plane (body
+        0, link -1), a link collider of the snake (body 1, the cylinder's link of contact_links()) or the block (body 2,
+        link -1); a miss is (-1, -1, 1.0, zeros, zeros).  With parentObjectUniqueId = the snake the rays are in the frame
+        of link parentLinkIndex (-1: the base), its origin the link's COM [U], and ride on it; positions and normals come
+        back in world coordinates either way.
+        Refused (NotImplementedError): a parent other than the snake, extra keywords (numThreads, reportHitNumber,
+        collisionFilterMask, fractionEpsilon)."""
+        if kw:
+            raise NotImplementedError("BulletClient.rayTestBatch: %s" % sorted(kw))
+        if parentObjectUniqueId not in (-1, self._SNAKE) or (parentObjectUniqueId == -1 and parentLinkIndex != -1):
+            raise NotImplementedError("BulletClient.rayTestBatch: rays ride on the snake's links only; got "
+                                      "parentObjectUniqueId=%r, parentLinkIndex=%r" % (parentObjectUniqueId, parentLinkIndex))
+        frm = np.asarray(rayFromPositions, dtype=np.float32).reshape(-1, 3)
+        to = np.asarray(rayToPositions, dtype=np.float32).reshape(-1, 3)
+        if len(frm) != len(to):
+            raise ValueError("rayFromPositions and rayToPositions must name as many points each, got %d and %d" % (len(frm), len(to)))
+        if len(frm) == 0:
+            return []
+        st = self._stepper()
+        n = self._n
+        row = -1 if parentObjectUniqueId == -1 else int(parentLinkIndex) + 1
+        hits = st.ray_test(np.concatenate([frm, to], axis=1), parent_row=row)[0].astype(np.float64)
+        links = np.asarray(st.contact_links(), dtype=np.int64)
+        out = []
+        for r in hits:
+            pid = int(r[7])
+            body = int(self.segmentation_ids(pid))
+            link = int(links[pid - 1]) if 1 <= pid <= 2 * n else -1
+            out.append((body, link, float(r[0]), tuple(float(v) for v in r[1:4]), tuple(float(v) for v in r[4:7])))
+        return out
+
+    def rayTest(self, rayFromPosition, rayToPosition, **kw):
+        """PyBullet's rayTest: rayTestBatch of the one ray (a list of one tuple)."""
+        if kw:
+            raise NotImplementedError("BulletClient.rayTest: %s" % sorted(kw))
+        return self.rayTestBatch([rayFromPosition], [rayToPosition])

@@ -607,6 +607,70 @@ int snk_view_matrix_ypr(const float target[3], float distance, float yaw_deg, fl
  * farVal = nearVal (snake.py:320), and gets the infinite entries the formula gives. */
 int snk_projection_fov(float fov_deg, float aspect, float near_val, float far_val, float out[16]);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The ray test: the contract of snk_ray_test (replaces pybullet.rayTest / rayTestBatch, with parentObjectUniqueId /
+ * parentLinkIndex: a fan of rays that rides on a link -- a range sensor; the reference's only read-out of its block,
+ * snake_gait_test.py:51, is indirect).  The kernels (bullet-envs_amd/csrc/snk_render.hpp) and the independent float64
+ * model of the tests (tests/np_rays.py) are both written from this text.
+ *
+ * Rays.  A ray is 6 floats, [from 3 | to 3].  rays_dev is [n_rows][n_rays][6] f32 -- with SNK_RAYS_SHARED in flags ONE set
+ * [n_rays][6] used for every row (a sensor's fixed fan) -- 4-byte aligned, nothing more: torch.cat((from, to), -1) works.
+ * parent_row = -1: the rays are in world coordinates.  parent_row = 0 .. 3n + 1: they are in the frame of that row of
+ * snk_link_states OF THE ROW'S OWN ENV, at the pose the state holds now: x_world = origin + R x, the origin the link's COM
+ * (floats 0-2 of its row) and R the link's rotation (what floats 3-6 are the quaternion of; the kernel takes the matrix
+ * from the forward kinematics, R(body) R(link in body), as snk_link_states forms it, not through the quaternion).  Row =
+ * Bullet link + 1: PyBullet's parentLinkIndex L is row L + 1.  [U] PyBullet transforms attached rays by the link's cached
+ * world transform, which is the inertial (COM) frame; snk_link_inertial_offsets turns that into the URDF link frame.
+ * The ray is o + t d, o = from, d = (to - from) / |to - from|, t in metres; only hits with 0 <= t <= |to - from| count.
+ *
+ * What is hit.  The solids of "The rendered scene" above, verbatim, at the pose the state holds now -- the ground plane
+ * z = 0 (met from either side, as there), the 2n capped implicit cylinders, the box of obstacle 1 / 2 -- each kind only
+ * when its bit is set in flags (PyBullet's collisionFilterMask, per kind of body).  They are met where the ray ENTERS
+ * them; a solid the ray starts inside of is open along that ray ([U] Bullet's convex cast reports no hit from inside
+ * either).  The hit is the nearest; the primitives are tried in the order of their ids, and a later one replaces the kept
+ * hit only when its t is smaller by more than 2e-4 m -- the render's tie rule, for the same coaxial 5.7 mm overlaps.
+ * The render's deviation holds here too: the cylinder is the implicit one, at most r (1 - cos(pi / 32)) = 0.125 mm
+ * outside the 32-gon hull the solver uses, so a range onto a link may be that much short.
+ *
+ * The record.  hits_dev is [n_rows][n_rays][8] f32, 16-byte aligned:
+ *   0    the hit fraction t / |to - from| in [0, 1]: PyBullet's hitFraction
+ *   1-3  the hit position, world coordinates, whatever frame the ray came in
+ *   4-6  the outward unit normal at the hit, world coordinates: radial, or +-axis for a cap entry, or that of the entered
+ *        face of the box, or (0, 0, 1) for the ground
+ *   7    the primitive id as a float, as snk_render's segmentation: 0 ground, 1 + c cylinder c (snk_contact_links maps c
+ *        to its Bullet link), 1 + 2n the box
+ * A miss is [1, 0, 0, 0, 0, 0, 0, -1] (PyBullet: fraction 1, id -1, zero vectors).  Misses besides "nothing in the way":
+ * a zero-length ray; a ray with a non-finite entry (or whose float32 length is not finite); every ray of a row whose env
+ * id is outside 0 .. n_envs - 1, which reads nothing; flags selecting a kind the handle does not have (a box on obstacle
+ * 0) -- not refused.  A zero record is never written: it would read as a hit on the ground at the ray's origin.
+ *
+ * The call.  Asynchronous on `stream` (hipStream_t or NULL) and ordered behind the steps enqueued there.  env_ids_dev
+ * [n_rows] i32, device; NULL: envs 0 .. n_rows - 1; ids may repeat and come in any order.  Two launches -- one wave per
+ * row builds the row's table of primitives and its parent frame; one 256-thread workgroup per (row, chunk of 256 rays)
+ * casts them -- with no atomics and no waits; nothing of the handle's state is written; bytes beyond
+ * [n_rows][n_rays][8] are left alone.  The tables live in the render's scratch memory of the handle, with exactly its
+ * growth rule, rows counting as images: the first call, and any call with more rows than every render / ray call
+ * before had images / rows, frees and allocates, i.e. waits for the whole device once and must not happen while a stream
+ * is being captured into a graph: cast rays for n_envs rows once before capturing.
+ * Refused, naming the argument: a null or poisoned handle; n_rows < 1; n_rays outside 1 .. 65536; more than 2^28 rays in
+ * all; parent_row outside -1 .. 3n + 1; none of the three kind bits set, or unknown bits, in flags; a null (or
+ * misaligned) rays_dev; a null or misaligned hits_dev.
+ *
+ * snk_ray_test_host: the same with HOST buffers; it synchronises the device first, like the state accessors, and also
+ * refuses an env id outside 0 .. n_envs - 1, n_rows above n_envs without ids, and a non-finite ray entry -- each with its
+ * index.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SNK_RAY_FLOATS 6      /* a ray:  [from 3 | to 3] */
+#define SNK_HIT_FLOATS 8      /* a hit:  [fraction | position 3 | normal 3 | primitive id] */
+#define SNK_RAYS_GROUND 1     /* flags: what the rays can hit (PyBullet's collisionFilterMask, per kind of body) */
+#define SNK_RAYS_SNAKE  2
+#define SNK_RAYS_BOX    4
+#define SNK_RAYS_SHARED 8     /* rays_dev is ONE set [n_rays][6] used for every row (a sensor's fixed fan) */
+int snk_ray_test(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, const float* rays_dev, int32_t n_rays,
+                 int32_t parent_row, int32_t flags, float* hits_dev, void* stream);
+int snk_ray_test_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, const float* rays, int32_t n_rays,
+                      int32_t parent_row, int32_t flags, float* hits);
+
 /* Where this build's structural limits were met, counted on the device since snk_create (Bullet has no such limits;
  * DESIGN.md 3).  Ground contacts have none left: the streamed-row solve has a slot for every point its chain's manifolds
  * can hold (8n), and the register-resident 16-link solve hands the substeps that outgrow its 64 slots to it.
@@ -649,7 +713,7 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
  * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
  * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction,
  * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) and snk_render / snk_render_host and the tensor seam
- * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host), snk_contacts(_host), snk_closest_points(_host)) return
+ * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host), snk_contacts(_host), snk_closest_points(_host)) and snk_ray_test(_host) return
  * non-zero -- and snk_reset_pose_floats, snk_contact_slots, snk_link_pairs and snk_closest_slots 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */
