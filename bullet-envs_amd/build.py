@@ -51,8 +51,8 @@ def _render_command(obj, defines=(), extra=()):
 
 
 def _world_command(obj, defines=(), extra=()):
-    """The translation unit of the link states and the env fork (csrc/snk_world.hip): an object of its own, like the
-    renderer's, linked in by the library's command."""
+    """The translation unit of the link states, the reported contacts, the closest points and the env fork
+    (csrc/snk_world.hip): an object of its own, like the renderer's, linked in by the library's command."""
     return [_hipcc()] + FLAGS + ["-c", "-fPIC", os.path.join(CSRC, "snk_world.hip"), "-o", obj] + \
         ["-D" + d for d in defines] + list(extra)
 

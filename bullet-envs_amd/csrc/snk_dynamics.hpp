@@ -54,13 +54,8 @@ template <class LT>
 __device__ void fk_vel(LT& L, const DevModel& M, int lane) {
     constexpr int N = LT::kN;
     const float* bs = L.base();
-    float qx = bs[3], qy = bs[4], qz = bs[5], qw = bs[6];
-    float dd = qx * qx + qy * qy + qz * qz + qw * qw;
-    float s2 = 2.0f / dd;
-    float xs = qx * s2, ys = qy * s2, zs = qz * s2;
-    float wx = qw * xs, wy = qw * ys, wz = qw * zs;
-    float xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
-    float Rp[9] = {1 - (yy + zz), xy - wz, xz + wy, xy + wz, 1 - (xx + zz), yz - wx, xz - wy, yz + wx, 1 - (xx + yy)};
+    float Rp[9];
+    quat_rot(bs[3], bs[4], bs[5], bs[6], Rp);
     f3 op = ld3(bs), wp = ld3(bs + 7), vp = ld3(bs + 10);
     if (lane == 0) {
 #pragma unroll

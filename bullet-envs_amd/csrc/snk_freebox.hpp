@@ -17,11 +17,8 @@ namespace snk {
 // world rotation and world inverse inertia of the box for this substep
 template <class LT>
 __device__ __forceinline__ void box_frame_v1(LT& L, const DevModel& M, int lane) {
-    const float qx = L.box[3], qy = L.box[4], qz = L.box[5], qw = L.box[6];
-    const float s2 = 2.0f / (qx * qx + qy * qy + qz * qz + qw * qw);
-    const float xs = qx * s2, ys = qy * s2, zs = qz * s2;
-    const float wx = qw * xs, wy = qw * ys, wz = qw * zs, xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
-    const float R[9] = {1 - (yy + zz), xy - wz, xz + wy, xy + wz, 1 - (xx + zz), yz - wx, xz - wy, yz + wx, 1 - (xx + yy)};
+    float R[9];
+    quat_rot(L.box[3], L.box[4], L.box[5], L.box[6], R);
     const float d[6] = {M.obs_iinv[0], 0.f, 0.f, M.obs_iinv[1], 0.f, M.obs_iinv[2]};
     float W[6];
     rotSym(R, d, W);

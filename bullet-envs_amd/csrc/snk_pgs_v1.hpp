@@ -99,7 +99,7 @@ __device__ int find_contacts_v1(LT& L, const DevModel& M, int lane, float* __res
             const int b = (c + 1) >> 1;
             const float* Rb = L.R[b];
             const float* Rc = M.cyl_R[c];
-            float Rw[9];
+            float Rw[9];      // = cyl_world_rot(Rb, Rc, Rw), written out: the call changes this kernel's instruction text
 #pragma unroll
             for (int i = 0; i < 3; i++)
 #pragma unroll

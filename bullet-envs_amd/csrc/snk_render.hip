@@ -71,13 +71,11 @@ int snk_render(snk_handle* h, const int32_t* env_ids_dev, int32_t n_images, cons
     float* cams = prims + (size_t)n_images * pf;
     hipStream_t st = (hipStream_t)stream;
     const int shared = shared_camera ? 1 : 0;
-    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
-        hipLaunchKernelGGL((snk::render_scene_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_images)),
-                           dim3(64), 0, st, v.d_model, v.d_recs, v.d_box, env_ids_dev, cameras_dev, shared, prims, cams, n_images,
-                           v.n_envs);
-        return 0;
-    });
-    if (rc == snk::kUnsupported) return api_fail("snk_render: unsupported n_modules (16 or 32)");
+    if (snk::launch_variant("snk_render", v.n, v.v2, [&](auto n, auto v2) {
+            hipLaunchKernelGGL((snk::render_scene_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_images)),
+                               dim3(64), 0, st, v.d_model, v.d_recs, v.d_box, env_ids_dev, cameras_dev, shared, prims, cams,
+                               n_images, v.n_envs);
+        })) return 1;
     const int tx = (width + snk::kRenderTile - 1) / snk::kRenderTile, ty = (height + snk::kRenderTile - 1) / snk::kRenderTile;
     const long long work = (long long)n_images * tx * ty;
     const unsigned blocks = (unsigned)(work < (1LL << 20) ? work : (1LL << 20));
@@ -130,12 +128,11 @@ int snk_ray_test(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, cons
     float* prims = snk::render_scratch(h, need);
     if (!prims) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
-        hipLaunchKernelGGL((snk::ray_scene_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64),
-                           0, st, v.d_model, v.d_recs, v.d_box, v.d_links, env_ids_dev, parent_row, prims, n_rows, v.n_envs);
-        return 0;
-    });
-    if (rc == snk::kUnsupported) return api_fail("snk_ray_test: unsupported n_modules (16 or 32)");
+    if (snk::launch_variant("snk_ray_test", v.n, v.v2, [&](auto n, auto v2) {
+            hipLaunchKernelGGL((snk::ray_scene_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)),
+                               dim3(64), 0, st, v.d_model, v.d_recs, v.d_box, v.d_links, env_ids_dev, parent_row, prims, n_rows,
+                               v.n_envs);
+        })) return 1;
     const int chunks = (n_rays + snk::kRayChunk - 1) / snk::kRayChunk;
     const long long work = (long long)n_rows * chunks;
     const unsigned blocks = (unsigned)(work < (1LL << 20) ? work : (1LL << 20));

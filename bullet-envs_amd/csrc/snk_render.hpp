@@ -5,11 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "snk_dynamics.hpp"
-#include "snk_env_io.hpp"
-#include "snk_lds.hpp"
-#include "snk_model.hpp"
-#include "snk_wave.hpp"
+#include "snk_query.hpp"
 
 namespace snk {
 
@@ -32,8 +28,8 @@ constexpr float kLx = (float)(0.4 / kLightLen), kLy = (float)(-0.3 / kLightLen),
 
 // The solids of one env as table entries at P, from the forward kinematics in L: lane = cylinder, lane 0 the box too.
 // What render_scene_kernel and ray_scene_kernel share.  !known (an env id outside the handle): nothing there.
-// QT: the arithmetic of the free box's rotation from its quaternion, rounded to float32 at the end -- float for the
-// render, as it always was; double for the ray test, whose records carry a column of that matrix as the hit's normal.
+// QT: the arithmetic of the free box's rotation (quat_rot) -- float for the render, as it always was; double for the ray
+// test, whose records carry a column of that matrix as the hit's normal.
 template <int N, bool V2, typename QT>
 __device__ __forceinline__ void scene_prims(const Lds<N, V2>& L, const DevModel& M, const float* box_all, int env,
                                             bool known, int lane, float* P) {
@@ -43,9 +39,9 @@ __device__ __forceinline__ void scene_prims(const Lds<N, V2>& L, const DevModel&
         f3 ctr = mk3(0.f, 0.f, 0.f), ax = mk3(0.f, 0.f, 1.f);
         float hl = -1.f;
         if (known) {
-            const int b = M.cyl_body[c];
-            ctr = ld3(L.o[b]) + mulRv(L.R[b], ld3(M.cyl_c[c]));
-            ax = mulRv(L.R[b], mk3(M.cyl_R[c][2], M.cyl_R[c][5], M.cyl_R[c][8]));
+            float Rw[9];
+            ctr = cyl_frame(L, M, c, Rw);
+            ax = mk3(Rw[2], Rw[5], Rw[8]);
             hl = M.cyl_hl;
         }
         o[0] = ctr.x; o[1] = ctr.y; o[2] = ctr.z; o[3] = M.cyl_r;
@@ -56,18 +52,7 @@ __device__ __forceinline__ void scene_prims(const Lds<N, V2>& L, const DevModel&
         float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
         f3 ctr = ld3(M.obs_c), hh = mk3(-1.f, -1.f, -1.f);
         if (known && M.obstacle != 0) hh = ld3(M.obs_h);
-        if (known && M.obstacle == 2 && box_all) {
-            const float* bx = box_all + (size_t)env * kBoxFloats;      // [pos 3 | quat xyzw 4 | ...]
-            ctr = ld3(bx);
-            const QT qx = bx[3], qy = bx[4], qz = bx[5], qw = bx[6];
-            const QT s2 = QT(2) / (qx * qx + qy * qy + qz * qz + qw * qw);
-            const QT xs = qx * s2, ys = qy * s2, zs = qz * s2;
-            const QT wx = qw * xs, wy = qw * ys, wz = qw * zs;
-            const QT xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
-            R[0] = (float)(1 - (yy + zz)); R[1] = (float)(xy - wz); R[2] = (float)(xz + wy);
-            R[3] = (float)(xy + wz); R[4] = (float)(1 - (xx + zz)); R[5] = (float)(yz - wx);
-            R[6] = (float)(xz - wy); R[7] = (float)(yz + wx); R[8] = (float)(1 - (xx + yy));
-        }
+        if (known && M.obstacle == 2 && box_all) box_pose<QT>(box_all, env, ctr, R);
         o[0] = ctr.x; o[1] = ctr.y; o[2] = ctr.z;
         o[3] = hh.x; o[4] = hh.y; o[5] = hh.z;
 #pragma unroll
@@ -93,14 +78,9 @@ __global__ __launch_bounds__(64) void render_scene_kernel(const DevModel* __rest
     const DevModel& M = *Mp;
     const int lane = threadIdx.x;
     for (int img = blockIdx.x; img < n_images; img += gridDim.x) {
-        const int env = env_ids ? env_ids[img] : img;
+        int env;
+        const bool known = load_row_env(L, M, recs, env_ids, img, n_envs, lane, env);      // (not known: the ground alone)
         float* P = prims + (size_t)img * prim_stride(N);
-        // an env id cannot be refused from inside a launch: one outside the handle reads nothing and draws the ground alone
-        const bool known = env >= 0 && env < n_envs;
-        if (known) {
-            load_rec(L, recs + (size_t)env * LT::REC, lane);
-            fk_vel(L, M, lane);
-        }
         scene_prims<N, V2, float>(L, M, box_all, env, known, lane, P);
         if (lane == 1) {
             // M = P V and its inverse (cofactors), in float64: the near and far planes of a camera are orders of
@@ -319,15 +299,11 @@ __global__ __launch_bounds__(256) void render_rays_kernel(const float* __restric
 // ----------------------------------------------------------------------------------
 constexpr int kRayChunk = 256;            // rays of one workgroup, one per thread
 constexpr int kRayFloats = 6, kHitFloats = 8;
-// The staging image of a chunk's records: float j of ray w at hits[j * kHitStride + w].  The writes go lane = ray,
-// consecutive banks.  The read of float 4 p + e of ray w by the lane that stores quad 2 w + p sits at bank
-// ((4 p + e) * 260 + w) mod 32 = (16 p + 4 e + w) mod 32 (ds_read_b32: dword address mod 32 within a 32-lane half):
-// distinct over p = 0..1 and the 16 consecutive rays of a half.  (Any stride = 4 mod 8 does it; 260 is the first >= 256.)
+// The staging image of a chunk's records: float j of ray w at stage[j][w] (snk_query.hpp: store_rows_as_quads)
 constexpr int kHitStride = 260;
 
 // ray_scene_kernel: one wave per row.  render_scene_kernel without a camera, plus the frame of link-table row
-// `parent_row` of the row's own env (-1: the world's) as link_state_kernel forms it: Rw = R(body) R(link in body),
-// origin = the link's COM.
+// `parent_row` of the row's own env (-1: the world's; link_row_frame): origin = the link's COM.
 template <int N, bool V2>
 __global__ __launch_bounds__(64) void ray_scene_kernel(const DevModel* __restrict__ Mp, const float* __restrict__ recs,
                                                        const float* __restrict__ box_all, const float* __restrict__ links,
@@ -339,29 +315,17 @@ __global__ __launch_bounds__(64) void ray_scene_kernel(const DevModel* __restric
     const DevModel& M = *Mp;
     const int lane = threadIdx.x;
     for (int row = blockIdx.x; row < n_rows; row += gridDim.x) {
-        const int env = env_ids ? env_ids[row] : row;
+        int env;
+        const bool known = load_row_env(L, M, recs, env_ids, row, n_envs, lane, env);
         float* P = prims + (size_t)row * prim_stride(N);
-        const bool known = env >= 0 && env < n_envs;
-        if (known) {
-            load_rec(L, recs + (size_t)env * LT::REC, lane);
-            fk_vel(L, M, lane);
-        }
         scene_prims<N, V2, double>(L, M, box_all, env, known, lane, P);
         if (lane == 1) {
             float* o = P + (2 * N + 1) * kPrimFloats;
             float Rw[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
             f3 org = mk3(0.f, 0.f, 0.f);
             if (known && parent_row >= 0) {
-                const float* T = links + (size_t)parent_row * kLinkFloats;
-                const int b = __float_as_int(T[15]);
-                const float* Rb = L.R[b];
-#pragma unroll
-                for (int i = 0; i < 3; i++)
-#pragma unroll
-                    for (int j = 0; j < 3; j++)
-                        Rw[3 * i + j] = Rb[3 * i] * T[j] + Rb[3 * i + 1] * T[3 + j] + Rb[3 * i + 2] * T[6 + j];
-                const f3 ow = ld3(L.o[b]) + mulRv(Rb, ld3(T + 9));
-                org = ow + mulRv(Rw, ld3(T + 12));
+                f3 ow;
+                link_row_frame(L, links + (size_t)parent_row * kLinkFloats, Rw, ow, org);
             }
 #pragma unroll
             for (int i = 0; i < 9; i++) o[i] = Rw[i];
@@ -384,7 +348,7 @@ __global__ __launch_bounds__(kRayChunk) void ray_cast_kernel(const float* __rest
                                                              long long n_work, int flags, float* __restrict__ hits) {
     __shared__ float4 T4[prim_stride(kMaxN) / 4];
     __shared__ float2 in2[kRayChunk * kRayFloats / 2];
-    __shared__ float stage[kHitFloats * kHitStride];
+    __shared__ float stage[kHitFloats][kHitStride];
     const float* T = reinterpret_cast<const float*>(T4);
     float* in = reinterpret_cast<float*>(in2);
     const int tid = threadIdx.x;
@@ -462,20 +426,11 @@ __global__ __launch_bounds__(kRayChunk) void ray_cast_kernel(const float* __rest
                 v[7] = (float)id;
             }
 #pragma unroll
-            for (int j = 0; j < kHitFloats; j++) stage[j * kHitStride + tid] = v[j];
+            for (int j = 0; j < kHitFloats; j++) stage[j][tid] = v[j];
         }
         __syncthreads();
         float4* dst = reinterpret_cast<float4*>(hits + ((size_t)row * (size_t)n_rays + (size_t)r0) * kHitFloats);
-        const int quads = cnt * (kHitFloats / 4);
-#pragma unroll
-        for (int k = 0; k < kHitFloats / 4; k++) {
-            const int Q = kRayChunk * k + tid;
-            if (Q < quads) {
-                const int ray = Q >> 1, f0 = 4 * (Q & 1);
-                dst[Q] = make_float4(stage[f0 * kHitStride + ray], stage[(f0 + 1) * kHitStride + ray],
-                                     stage[(f0 + 2) * kHitStride + ray], stage[(f0 + 3) * kHitStride + ray]);
-            }
-        }
+        store_rows_as_quads<kRayChunk>(stage, dst, cnt, tid);
         __syncthreads();      // (the table and both staging images are replaced by the next work item's)
     }
 }

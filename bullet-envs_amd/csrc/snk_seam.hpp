@@ -69,6 +69,15 @@ int for_variant(int n, bool v2, F&& fn) {
     return kUnsupported;
 }
 
+// The tail of a device form: launch(integral_constant<int, N>{}, bool_constant<V2>{}) enqueues the variant's kernel.
+// 0, or "<who>: unsupported n_modules (16 or 32)" / launch_ok(who)'s report.
+template <class F>
+int launch_variant(const char* who, int n, bool v2, F&& launch) {
+    if (for_variant(n, v2, [&](auto N, auto V2) { launch(N, V2); return 0; }) == kUnsupported)
+        return api_fail(std::string(who) + ": unsupported n_modules (16 or 32)");
+    return launch_ok(who);
+}
+
 // A host id list (null: none) against the handle: 0, or the first id outside 0 .. n_envs - 1 reported.
 inline int check_env_ids(const char* who, const char* list_name, const int32_t* ids, int n, int n_envs) {
     for (int k = 0; ids && k < n; k++)

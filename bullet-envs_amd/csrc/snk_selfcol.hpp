@@ -19,6 +19,7 @@
 // command range (|target| <= 30 deg: 15 mm of clearance, tools/self_collision_clearance.py), but a snake bent further
 // (a larger scaling_factor, states set from outside) does fold onto itself.
 #pragma once
+#include "snk_contacts.hpp"
 #include "snk_lds.hpp"
 #include "snk_model.hpp"
 #include "snk_wave.hpp"
@@ -322,12 +323,7 @@ __device__ int find_self_contacts_v1(LT& L, const DevModel& M, int lane, float m
     auto frame = [&](int c, Cvx& s) {
         const int b = (c + 1) >> 1;
         const float* Rb = L.R[b];
-        const float* Rc = M.cyl_R[c];
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                s.R[3 * i + j] = Rb[3 * i] * Rc[j] + Rb[3 * i + 1] * Rc[3 + j] + Rb[3 * i + 2] * Rc[6 + j];
+        cyl_world_rot(Rb, M.cyl_R[c], s.R);
         s.c = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[c]));
         s.box = 0;
         s.half = mk3(0.f, 0.f, 0.f);

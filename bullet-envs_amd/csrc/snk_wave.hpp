@@ -33,6 +33,19 @@ __device__ __forceinline__ f3 mulRtv(const float* R, f3 v) {
     return mk3(R[0] * v.x + R[3] * v.y + R[6] * v.z, R[1] * v.x + R[4] * v.y + R[7] * v.z,
                R[2] * v.x + R[5] * v.y + R[8] * v.z);
 }
+// R (row-major, body -> world) of the quaternion (x, y, z, w), which need not be normalised: THE definition of the
+// rotation every kernel forms from a quaternion.  QT: the arithmetic, rounded to float32 at the end -- float everywhere
+// but in the ray test's table (snk_render.hpp: scene_prims), whose records carry a column of this matrix as a hit's normal.
+template <typename QT = float>
+__device__ __forceinline__ void quat_rot(QT qx, QT qy, QT qz, QT qw, float* R) {
+    const QT s2 = QT(2) / (qx * qx + qy * qy + qz * qz + qw * qw);
+    const QT xs = qx * s2, ys = qy * s2, zs = qz * s2;
+    const QT wx = qw * xs, wy = qw * ys, wz = qw * zs;
+    const QT xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
+    R[0] = (float)(1 - (yy + zz)); R[1] = (float)(xy - wz); R[2] = (float)(xz + wy);
+    R[3] = (float)(xy + wz); R[4] = (float)(1 - (xx + zz)); R[5] = (float)(yz - wx);
+    R[6] = (float)(xz - wy); R[7] = (float)(yz + wx); R[8] = (float)(1 - (xx + yy));
+}
 // symmetric 3x3 stored xx xy xz yy yz zz
 __device__ __forceinline__ f3 mulSv(const float* S, f3 v) {
     return mk3(S[0] * v.x + S[1] * v.y + S[2] * v.z, S[1] * v.x + S[3] * v.y + S[4] * v.z,

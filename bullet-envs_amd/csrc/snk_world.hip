@@ -1,6 +1,7 @@
-// snk_world.hip -- link states, reported contacts, the env fork and the closest-point query behind snk_link_states /
-// snk_contacts / snk_copy_envs / snk_closest_points and their host forms, and the host-only link read-outs (include/snk.h).  A translation unit and a code object of its own, like snk_render.hip:
-// build.py compiles it to an object and links it into libsnk.so next to snk_api.hip, whose kernels it does not touch.
+// snk_world.hip -- link states, reported contacts, the closest-point query and the env fork behind snk_link_states /
+// snk_contacts / snk_closest_points / snk_copy_envs and their host forms, and the host-only link read-outs (include/snk.h).
+// A translation unit and a code object of its own, like snk_render.hip: build.py compiles it to an object and links it
+// into libsnk.so next to snk_api.hip, whose kernels it does not touch.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -42,13 +43,10 @@ int snk_link_states(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, f
         return api_fail("snk_link_states: out_dev must be 16-byte aligned (the rows leave as 16-byte stores)");
     snk::WorldView v;
     if (snk::world_view(h, false, &v)) return 1;
-    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+    return snk::launch_variant("snk_link_states", v.n, v.v2, [&](auto n, auto v2) {
         hipLaunchKernelGGL((snk::link_state_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64),
                            0, (hipStream_t)stream, v.d_model, v.d_recs, v.d_links, env_ids_dev, out_dev, n_rows, v.n_envs);
-        return 0;
     });
-    if (rc == snk::kUnsupported) return api_fail("snk_link_states: unsupported n_modules (16 or 32)");
-    return launch_ok("snk_link_states");
 }
 
 int snk_link_states_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* out) {
@@ -95,14 +93,11 @@ int snk_contacts(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, floa
     snk::WorldView v;
     if (snk::world_view(h, false, &v)) return 1;
     if (!contact_slots(v)) return api_fail("snk_contacts: this handle has contact_model 0 (no contact cache)");
-    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+    return snk::launch_variant("snk_contacts", v.n, v.v2, [&](auto n, auto v2) {
         hipLaunchKernelGGL((snk::contacts_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64), 0,
                            (hipStream_t)stream, v.d_model, v.d_recs, v.tables[snk::WorldView::kManifolds].d,
                            v.tables[snk::WorldView::kBox].d, env_ids_dev, points_dev, force_dev, count_dev, n_rows, v.n_envs);
-        return 0;
     });
-    if (rc == snk::kUnsupported) return api_fail("snk_contacts: unsupported n_modules (16 or 32)");
-    return launch_ok("snk_contacts");
 }
 
 int snk_contacts_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float* points, float* force, int32_t* count) {
@@ -182,14 +177,11 @@ int snk_closest_points(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows
     snk::WorldView v;
     if (snk::world_view(h, false, &v)) return 1;
     if (closest_pairs_refused("snk_closest_points", max_pairs, v.n)) return 1;
-    const int rc = snk::for_variant(v.n, v.v2, [&](auto n, auto v2) {
+    return snk::launch_variant("snk_closest_points", v.n, v.v2, [&](auto n, auto v2) {
         hipLaunchKernelGGL((snk::closest_points_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)),
                            dim3(64), 0, (hipStream_t)stream, v.d_model, v.d_recs, v.tables[snk::WorldView::kBox].d, env_ids_dev,
                            distance, flags, max_pairs, points_dev, clearance_dev, count_dev, n_rows, v.n_envs);
-        return 0;
     });
-    if (rc == snk::kUnsupported) return api_fail("snk_closest_points: unsupported n_modules (16 or 32)");
-    return launch_ok("snk_closest_points");
 }
 
 int snk_closest_points_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, float distance, int32_t flags,

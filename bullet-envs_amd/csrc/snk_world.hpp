@@ -6,21 +6,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "snk_dynamics.hpp"
-#include "snk_env_io.hpp"
-#include "snk_lds.hpp"
-#include "snk_model.hpp"
+#include "snk_query.hpp"
 #include "snk_selfcol.hpp"
-#include "snk_wave.hpp"
 
 namespace snk {
 
 // One output row = 16 floats (64 bytes): [COM 3 | quaternion xyzw 4 | link-frame origin 3 | COM velocity 3 | omega 3]
 constexpr int kLinkStateFloats = 16;
-// The staging image of one pass: float j of the pass's row l at stage[j][l].  A row stride of 66 floats keeps both sides
-// free of bank conflicts (cdna_hip_programming.md 2: ds_write_b32 and ds_read_b32 bank = dword address mod 32 within a
-// 32-lane half): the writes go lane = row, consecutive banks; the read of float 4 p + e of row w by lane 4 w + p sits at
-// bank (8 p + 2 e + w) mod 32, distinct over the p = 0..3, w = 8 consecutive rows of a half.
+// The staging image of one pass: float j of the pass's row l at stage[j][l] (snk_query.hpp: store_rows_as_quads)
 constexpr int kStageStride = 66;
 
 // world orientation of a link from its rotation matrix (row-major, link -> world): the branch of the largest of
@@ -61,13 +54,8 @@ __global__ __launch_bounds__(64) void link_state_kernel(const DevModel* __restri
     const DevModel& M = *Mp;
     const int lane = threadIdx.x;
     for (int blk = blockIdx.x; blk < n_rows; blk += gridDim.x) {
-        const int env = env_ids ? env_ids[blk] : blk;
-        // an env id cannot be refused from inside a launch: one outside the handle reads nothing, its rows are zeros
-        const bool known = env >= 0 && env < n_envs;
-        if (known) {
-            load_rec(L, recs + (size_t)env * LT::REC, lane);
-            fk_vel(L, M, lane);
-        }
+        int env;
+        const bool known = load_row_env(L, M, recs, env_ids, blk, n_envs, lane, env);      // (not known: its rows are zeros)
         float4* dst = reinterpret_cast<float4*>(out + (size_t)blk * LR * kLinkStateFloats);
 #pragma unroll 1
         for (int r0 = 0; r0 < LR; r0 += 64) {
@@ -83,18 +71,10 @@ __global__ __launch_bounds__(64) void link_state_kernel(const DevModel* __restri
 #pragma unroll
                 for (int j = 0; j < 3; j++) { v[7 + j] = bs[j]; v[10 + j] = bs[10 + j]; v[13 + j] = bs[7 + j]; }
             } else if (known && r < LR) {
-                const float* T = links + (size_t)r * kLinkFloats;
-                const int b = __float_as_int(T[15]);
-                const float* Rb = L.R[b];
                 float Rw[9];
-#pragma unroll
-                for (int i = 0; i < 3; i++)
-#pragma unroll
-                    for (int j = 0; j < 3; j++)
-                        Rw[3 * i + j] = Rb[3 * i] * T[j] + Rb[3 * i + 1] * T[3 + j] + Rb[3 * i + 2] * T[6 + j];
+                f3 ow, cw;
+                const int b = link_row_frame(L, links + (size_t)r * kLinkFloats, Rw, ow, cw);
                 const f3 ob = ld3(L.o[b]);
-                const f3 ow = ob + mulRv(Rb, ld3(T + 9));
-                const f3 cw = ow + mulRv(Rw, ld3(T + 12));
                 // the body's twist at its joint origin carries the joint's own rate: v(COM) = v(o_b) + omega x (c - o_b)
                 const f3 w = ld3(L.w[b]);
                 const f3 vc = ld3(L.v[b]) + cross(w, cw - ob);
@@ -103,6 +83,8 @@ __global__ __launch_bounds__(64) void link_state_kernel(const DevModel* __restri
 #pragma unroll
             for (int j = 0; j < kLinkStateFloats; j++) stage[j][lane] = v[j];
             lds_sync();
+            // = store_rows_as_quads<64>(stage, dst + 4 r0, rows of this pass, lane), written out: through the call the 16-link
+            // kernels form the destination in two more vector registers and measured 0.5 to 4 % slower
             const int quads = (LR - r0 < 64 ? LR - r0 : 64) * (kLinkStateFloats / 4);
 #pragma unroll
             for (int k = 0; k < kLinkStateFloats / 4; k++) {
@@ -145,13 +127,8 @@ __global__ __launch_bounds__(64) void contacts_kernel(const DevModel* __restrict
     const int lane = threadIdx.x;
     const int units = NC + (box_all ? 1 : 0);      // units with slots; force has NC + 1 entries either way
     for (int blk = blockIdx.x; blk < n_rows; blk += gridDim.x) {
-        const int env = env_ids ? env_ids[blk] : blk;
-        // an env id cannot be refused from inside a launch: one outside the handle reads nothing, its outputs are zeros
-        const bool known = env >= 0 && env < n_envs;
-        if (known) {
-            load_rec(L, recs + (size_t)env * LT::REC, lane);
-            fk_vel(L, M, lane);
-        }
+        int env;
+        const bool known = load_row_env(L, M, recs, env_ids, blk, n_envs, lane, env);      // (not known: its outputs are zeros)
         float4* dst = points ? reinterpret_cast<float4*>(points + (size_t)blk * units * 4 * kContactFloats) : nullptr;
         float live_total = 0.f;
 #pragma unroll 1
@@ -168,34 +145,12 @@ __global__ __launch_bounds__(64) void contacts_kernel(const DevModel* __restrict
 #pragma unroll
             for (int j = 0; j < 4; j++) { p[j].a = mk3(0.f, 0.f, 0.f); p[j].b = mk3(0.f, 0.f, 0.f); p[j].d = 0.f; p[j].lam = 0.f; }
             if (known && u < NC) {
-                const int b = (u + 1) >> 1;
-                const float* Rb = L.R[b];
-                cyl_world_rot(Rb, M.cyl_R[u], R);
-                org = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[u]));
+                org = cyl_frame(L, M, u, R);
                 zo = M.cyl_zoff;
                 n = manifold_load_global(mf_all + ((size_t)env * NC + u) * kMfFloats, p);
             } else if (known && u == NC && box_all) {
-                // [state 13 | count | 4 x (a3, b.x, b.y, lambda) | padding]: floats 0 .. 39 as ten quads
-                const float4* bq = reinterpret_cast<const float4*>(box_all + (size_t)env * kBoxFloats);
-                float f[40];
-#pragma unroll
-                for (int i = 0; i < 10; i++) { const float4 q = bq[i]; f[4 * i] = q.x; f[4 * i + 1] = q.y; f[4 * i + 2] = q.z; f[4 * i + 3] = q.w; }
-                const float qx = f[3], qy = f[4], qz = f[5], qw = f[6];      // R(quat) as box_frame_v1 forms it
-                const float s2 = 2.0f / (qx * qx + qy * qy + qz * qz + qw * qw);
-                const float xs = qx * s2, ys = qy * s2, zs = qz * s2;
-                const float wx = qw * xs, wy = qw * ys, wz = qw * zs, xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys,
-                            yz = qy * zs, zz = qz * zs;
-                R[0] = 1 - (yy + zz); R[1] = xy - wz; R[2] = xz + wy; R[3] = xy + wz; R[4] = 1 - (xx + zz); R[5] = yz - wx;
-                R[6] = xz - wy; R[7] = yz + wx; R[8] = 1 - (xx + yy);
-                org = mk3(f[0], f[1], f[2]);
-                n = (int)f[13];
-                n = n < 0 ? 0 : (n > 4 ? 4 : n);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    p[j].a = mk3(f[14 + 6 * j], f[15 + 6 * j], f[16 + 6 * j]);
-                    p[j].b = mk3(f[17 + 6 * j], f[18 + 6 * j], 0.f);
-                    p[j].lam = f[19 + 6 * j];
-                }
+                box_pose(box_all, env, org, R);
+                n = box_manifold(box_all, env, p);
             }
             const f3 zoff = mk3(0.f, 0.f, zo);
             float fsum = 0.f;
@@ -236,8 +191,8 @@ __global__ __launch_bounds__(64) void contacts_kernel(const DevModel* __restrict
 //                (b) narrow phase: lane = candidate, 64 at a time, so the GJK runs on full waves whether one offset
 //                passed the cull with two lanes or with sixty; the hits are compacted by ballot again.
 // The work per env ranges from nothing (no pair passes the cull) to C(2n, 2) - (2n - 1) runs of GJK (a distance beyond the
-// snake's length); the list holds every pair.  Found records are staged in LDS (float j of record r at stage[j][r], the
-// bank rule of kStageStride: 130 = 4 x 32 + 2) and leave 64 at a time as consecutive float4s -- a record that waits for
+// snake's length); the list holds every pair.  Found records are staged in LDS (float j of record r at stage[j][r]:
+// snk_query.hpp, store_rows_as_quads) and leave 64 at a time as consecutive float4s -- a record that waits for
 // its 64 stays staged, so every store instruction but an env's last writes 4 KB whole.  The per-cylinder minimum of the
 // link-link distances is an integer minimum in LDS over an order-preserving key (any order of arrival gives the same
 // bits); the running counts are wave-uniform.  Plain stores; no atomics to global memory; nothing of the handle's state
@@ -361,11 +316,11 @@ __global__ __launch_bounds__(64) void closest_points_kernel(const DevModel* __re
     const int slots = NC + max_pairs;
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int blk = blockIdx.x; blk < n_rows; blk += gridDim.x) {
-        const int env = env_ids ? env_ids[blk] : blk;
+        int env;
+        const bool known = load_row_env(L, M, recs, env_ids, blk, n_envs, lane, env);
         float4* dst = points ? reinterpret_cast<float4*>(points + (size_t)blk * slots * kContactFloats) : nullptr;
         float* clr = clearance ? clearance + (size_t)blk * 2 * NC : nullptr;
-        // an env id cannot be refused from inside a launch: one outside the handle reads nothing, its outputs are zeros
-        if (!(env >= 0 && env < n_envs)) {
+        if (!known) {      // its outputs are zeros; nothing of L was read
             if (dst)
                 for (int q = lane; q < slots * (kContactFloats / 4); q += 64) dst[q] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (clr)
@@ -373,20 +328,8 @@ __global__ __launch_bounds__(64) void closest_points_kernel(const DevModel* __re
             if (count && lane < 2) count[2 * (size_t)blk + lane] = 0;
             continue;
         }
-        load_rec(L, recs + (size_t)env * LT::REC, lane);
-        fk_vel(L, M, lane);
-        // records r0 .. r0 + n - 1 of the stage to slots slot0 ..: consecutive float4s
-        auto flush = [&](int slot0, int n) {
-            const int quads = n * (kContactFloats / 4);
-            for (int k = 0; 64 * k < quads; k++) {
-                const int Q = 64 * k + lane;
-                if (Q < quads) {
-                    const int row = Q >> 2, f0 = 4 * (Q & 3);
-                    dst[(size_t)slot0 * (kContactFloats / 4) + Q] =
-                        make_float4(stage[f0][row], stage[f0 + 1][row], stage[f0 + 2][row], stage[f0 + 3][row]);
-                }
-            }
-        };
+        // records 0 .. n - 1 (n <= 64) of the stage to slots slot0 ..: consecutive float4s
+        auto flush = [&](int slot0, int n) { store_rows_as_quads<64>(stage, dst + (size_t)slot0 * (kContactFloats / 4), n, lane); };
         auto put = [&](int row, const Closest& r, int a, int b) {
             stage[0][row] = r.P.x; stage[1][row] = r.P.y; stage[2][row] = r.P.z;
             stage[3][row] = r.PB.x; stage[4][row] = r.PB.y; stage[5][row] = r.PB.z;
@@ -398,10 +341,8 @@ __global__ __launch_bounds__(64) void closest_points_kernel(const DevModel* __re
         const int a = lane < NC ? lane : NC - 1;
         f3 ca, axa;
         {
-            const int ba = (a + 1) >> 1;
             float Rw[9];
-            cyl_world_rot(L.R[ba], M.cyl_R[a], Rw);
-            ca = ld3(L.o[ba]) + mulRv(L.R[ba], ld3(M.cyl_c[a]));
+            ca = cyl_frame(L, M, a, Rw);
             axa = mk3(Rw[2], Rw[5], Rw[8]);      // the cylinder's axis in the world
             if (lane < NC) {
                 Cvx& F = fr[a].s;
@@ -428,18 +369,7 @@ __global__ __launch_bounds__(64) void closest_points_kernel(const DevModel* __re
             float Rx[9];
 #pragma unroll
             for (int i = 0; i < 9; i++) Rx[i] = (i % 4 == 0) ? 1.f : 0.f;
-            if (M.obstacle == 2 && box_all) {      // the free box where it is now; R(quat) as contacts_kernel forms it
-                const float4* bq = reinterpret_cast<const float4*>(box_all + (size_t)env * kBoxFloats);
-                const float4 q0 = bq[0], q1 = bq[1];
-                const float qx = q0.w, qy = q1.x, qz = q1.y, qw = q1.z;
-                const float s2 = 2.0f / (qx * qx + qy * qy + qz * qz + qw * qw);
-                const float xs = qx * s2, ys = qy * s2, zs = qz * s2;
-                const float wx = qw * xs, wy = qw * ys, wz = qw * zs, xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys,
-                            yz = qy * zs, zz = qz * zs;
-                Rx[0] = 1 - (yy + zz); Rx[1] = xy - wz; Rx[2] = xz + wy; Rx[3] = xy + wz; Rx[4] = 1 - (xx + zz);
-                Rx[5] = yz - wx; Rx[6] = xz - wy; Rx[7] = yz + wx; Rx[8] = 1 - (xx + yy);
-                bc = mk3(q0.x, q0.y, q0.z);
-            }
+            if (M.obstacle == 2 && box_all) box_pose(box_all, env, bc, Rx);      // the free box where it is now
             const f3 half = mk3(M.obs_h[0], M.obs_h[1], M.obs_h[2]);
             if (lane == 0) {
                 Cvx& F = fr[NC].s;

@@ -50,6 +50,13 @@ int main() {
         printf("%s for_variant(%d, %d) -> %d\n", rc == v[2] ? "ok  " : "BAD ", v[0], v[1], rc);
         if (rc != v[2]) g_bad++;
     }
+    // launch_variant: an unsupported variant launches nothing and is refused in the caller's name
+    {
+        int ran = 0;
+        expect("launch_variant: 8 links", snk::launch_variant("snk_contacts", 8, false, [&](auto, auto) { ran++; }), 1,
+               "snk_contacts: unsupported n_modules (16 or 32)");
+        if (ran) { printf("BAD  launch_variant ran a launch for an unsupported variant\n"); g_bad++; }
+    }
     // HostCall with no device: nothing can be allocated, nothing is downloaded, the failure is reported once by finish
     {
         const float host_in[4] = {1, 2, 3, 4};
