@@ -122,6 +122,11 @@ SYMBOLS = {
     "snk_render_host": (C.c_int, [_vp, _I32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _U8, _F, _I32]),
     "snk_ray_test": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "snk_ray_test_host": (C.c_int, [_vp, _I32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "snk_dyn_dofs": (C.c_int32, [_vp]),
+    "snk_dynamics": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "snk_dynamics_host": (C.c_int, [_vp, _I32, C.c_int32, C.c_int32, _F, _F]),
+    "snk_jacobians": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
+    "snk_jacobians_host": (C.c_int, [_vp, _I32, C.c_int32, _I32, _F, C.c_int32, _F]),
     "snk_view_matrix_ypr": (C.c_int, [_F, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _F]),
     "snk_projection_fov": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, _F]),
     "snk_last_error": (C.c_char_p, []),
@@ -140,6 +145,9 @@ RAYS_SNAKE = 2
 RAYS_BOX = 4
 RAYS_SHARED = 8         # SNK_RAYS_SHARED: one set of rays [n_rays, 6] for every row
 RAYS_ALL = RAYS_GROUND | RAYS_SNAKE | RAYS_BOX
+BIAS_VELOCITY = 1       # SNK_BIAS_VELOCITY: the Coriolis, centrifugal and gyroscopic terms of snk_dynamics' h
+BIAS_GRAVITY = 2        # SNK_BIAS_GRAVITY: minus the generalised gravity force
+JAC_MAX_POINTS = 256    # SNK_JAC_MAX_POINTS: points of one snk_jacobians call
 
 #: the camera behind render() / getCameraImage when the caller gives no matrices [U]: the reference calls
 #: resetDebugVisualizerCamera(1.5, -30, -90, [1.28, 0, 0]) right before its getCameraImage (snake.py:322-327) -- the reading
@@ -815,6 +823,59 @@ class Stepper:
         """snk_ray_test: every buffer a device pointer (ids 0: envs 0 .. n_rows - 1), asynchronous on `stream`."""
         check(self.lib.snk_ray_test(self.h, ids_ptr or None, int(n_rows), rays_ptr or None, int(n_rays), int(parent_row),
                                     int(flags), hits_ptr or None, stream or None), "snk_ray_test")
+
+    # ---- the dynamics queries (snk_dynamics / snk_jacobians and their host forms) ----
+    @property
+    def dyn_dofs(self):
+        """snk_dyn_dofs: nd = 6 + n, the components of u = [omega 3 | v of the root origin 3 | qd n]."""
+        k = int(self.lib.snk_dyn_dofs(self.h))
+        if k == 0:
+            raise RuntimeError("snk_dyn_dofs failed: %s" % last_error())
+        return k
+
+    def dynamics_device(self, ids_ptr, n_rows, flags, mass_ptr=0, bias_ptr=0, stream=0):
+        """snk_dynamics: mass [n_rows, nd, nd] f32, bias [n_rows, nd] f32 (each a device pointer or 0) for the envs ids
+        [n_rows] i32 (0: envs 0 .. n_rows - 1).  Asynchronous on `stream`."""
+        check(self.lib.snk_dynamics(self.h, ids_ptr or None, int(n_rows), int(flags), mass_ptr or None, bias_ptr or None,
+                                    stream or None), "snk_dynamics")
+
+    def dynamics(self, env_ids=None, flags=BIAS_VELOCITY | BIAS_GRAVITY, mass=True, bias=True):
+        """snk_dynamics_host: (M [k, nd, nd] float32 or None, h [k, nd] float32 or None) of the envs `env_ids` (None: all;
+        ids may repeat, any order) at the state they hold: M du/dt + h = Q over u = [omega 3 | v of the root origin 3 | qd
+        n].  flags: BIAS_VELOCITY | BIAS_GRAVITY, the terms of h (snk.h, "The dynamics queries")."""
+        ids, k, idp = self._ids(env_ids)
+        nd = self.n + 6
+        M = np.zeros((max(k, 1), nd, nd), np.float32) if mass else None
+        h = np.zeros((max(k, 1), nd), np.float32) if bias else None
+        check(self.lib.snk_dynamics_host(self.h, idp, k, int(flags), fptr(M) if mass else None, fptr(h) if bias else None),
+              "snk_dynamics_host")
+        return M, h
+
+    def jacobians_device(self, ids_ptr, n_rows, link_rows_ptr, local_ptr, n_points, jac_ptr, stream=0):
+        """snk_jacobians: jac [n_rows, n_points, 6, nd] f32 for the links link_rows [n_points] i32 (rows of link_states) and
+        the points local [n_points, 3] f32 in their COM frames (0: the COMs); every buffer a device pointer.  Asynchronous on
+        `stream`."""
+        check(self.lib.snk_jacobians(self.h, ids_ptr or None, int(n_rows), link_rows_ptr or None, local_ptr or None,
+                                     int(n_points), jac_ptr or None, stream or None), "snk_jacobians")
+
+    def jacobians(self, link_rows, local=None, env_ids=None):
+        """snk_jacobians_host: [k, n_points, 6, nd] float32 of the envs `env_ids` (None: all; ids may repeat, any order):
+        per point rows 0-2 the world linear velocity per unit of each component of u, rows 3-5 the link's angular velocity.
+        link_rows: rows of link_states (Bullet link + 1), one list for every env; local: [n_points, 3] points in the links'
+        COM frames (None: the COMs)."""
+        ids, k, idp = self._ids(env_ids)
+        rows = np.ascontiguousarray(link_rows, dtype=np.int32).reshape(-1)
+        P = len(rows)
+        loc = None
+        if local is not None:
+            loc = np.ascontiguousarray(local, dtype=np.float32)
+            if loc.shape != (P, 3):
+                raise ValueError("local must be [%d, 3], got %s" % (P, loc.shape))
+        ok = 1 <= P <= JAC_MAX_POINTS                         # (the library refuses the rest by name; no huge buffers first)
+        jac = np.zeros((max(k, 1), P, 6, self.n + 6) if ok else (1,), np.float32)
+        check(self.lib.snk_jacobians_host(self.h, idp, k, rows.ctypes.data_as(_I32) if P else None,
+                                          fptr(loc) if loc is not None else None, P, fptr(jac)), "snk_jacobians_host")
+        return jac
 
     def timing_enable(self, capacity):
         check(self.lib.snk_timing_enable(self.h, int(capacity)), "snk_timing_enable")

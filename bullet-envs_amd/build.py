@@ -15,6 +15,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "snk.h")
 
 RENDER_OBJ = os.path.join(HERE, "snk_render.o")
 WORLD_OBJ = os.path.join(HERE, "snk_world.o")
+DYN_OBJ = os.path.join(HERE, "snk_dyn.o")
 
 
 def sources():
@@ -57,6 +58,13 @@ def _world_command(obj, defines=(), extra=()):
         ["-D" + d for d in defines] + list(extra)
 
 
+def _dyn_command(obj, defines=(), extra=()):
+    """The translation unit of the dynamics queries (csrc/snk_dyn.hip: mass matrix, bias forces, link Jacobians): an object
+    of its own, like the renderer's and the world's, linked in by the library's command."""
+    return [_hipcc()] + FLAGS + ["-c", "-fPIC", os.path.join(CSRC, "snk_dyn.hip"), "-o", obj] + \
+        ["-D" + d for d in defines] + list(extra)
+
+
 def _stamp(out):
     return out + ".cmd"
 
@@ -69,6 +77,10 @@ def _render_stamp(out):
 
 def _world_stamp(out):
     return out + ".world.cmd"
+
+
+def _dyn_stamp(out):
+    return out + ".dyn.cmd"
 
 
 def toolchain_text():
@@ -105,7 +117,10 @@ def needs_build(cmd=None):
             if f.read() != _stamp_text(_render_command(RENDER_OBJ)):
                 return True
         with open(_world_stamp(LIB)) as f:
-            return f.read() != _stamp_text(_world_command(WORLD_OBJ))
+            if f.read() != _stamp_text(_world_command(WORLD_OBJ)):
+                return True
+        with open(_dyn_stamp(LIB)) as f:
+            return f.read() != _stamp_text(_dyn_command(DYN_OBJ))
     except OSError:
         return True
 
@@ -127,10 +142,12 @@ def build(force=False, verbose=False, defines=(), out=None):
         return LIB
     obj = RENDER_OBJ if out is None else os.path.splitext(target)[0] + "_render.o"
     wobj = WORLD_OBJ if out is None else os.path.splitext(target)[0] + "_world.o"
+    dobj = DYN_OBJ if out is None else os.path.splitext(target)[0] + "_dyn.o"
     rcmd = _render_command(obj, defines, extra)
     wcmd = _world_command(wobj, defines, extra)
-    run = [cmd[0], obj, wobj] + list(cmd[1:])      # (the objects first: hipcc reads every input behind a .hip file as HIP source)
-    for r in (rcmd, wcmd, run):
+    dcmd = _dyn_command(dobj, defines, extra)
+    run = [cmd[0], obj, wobj, dobj] + list(cmd[1:])      # (the objects first: hipcc reads every input behind a .hip file as HIP source)
+    for r in (rcmd, wcmd, dcmd, run):
         if verbose:
             r = [r[0], "-Rpass-analysis=kernel-resource-usage"] + r[1:]
             print(" ".join(r))
@@ -141,6 +158,8 @@ def build(force=False, verbose=False, defines=(), out=None):
         f.write(_stamp_text(rcmd))
     with open(_world_stamp(target), "w") as f:
         f.write(_stamp_text(wcmd))
+    with open(_dyn_stamp(target), "w") as f:
+        f.write(_stamp_text(dcmd))
     with open(target + ".toolchain", "w") as f:
         f.write(toolchain_text())
     return target

@@ -1,0 +1,125 @@
+// snk_dyn.hip -- the dynamics queries behind snk_dynamics / snk_jacobians and their host forms (include/snk.h, "The
+// dynamics queries"): mass matrix, bias forces and link Jacobians per env.  A translation unit and a code object of its
+// own, like snk_world.hip and snk_render.hip: build.py compiles it to an object and links it into libsnk.so next to
+// snk_api.hip, whose kernels it does not touch.  It sees a handle through snk_seam.hpp's world_view and writes nothing of it.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/snk.h"
+#include "snk_seam.hpp"
+#include "snk_dyn.hpp"
+
+namespace {
+
+using snk::api_fail;
+
+// what both forms of snk_dynamics refuse before they look at the handle; 0: nothing
+int dynamics_args_refused(const char* who, int32_t n_rows, int32_t flags, const void* mass, const void* bias) {
+    const std::string w(who);
+    if (n_rows < 1) return api_fail(w + ": n_rows must be at least 1");
+    if (flags == 0 || (flags & ~(SNK_BIAS_VELOCITY | SNK_BIAS_GRAVITY)))
+        return api_fail(w + ": flags must be SNK_BIAS_VELOCITY, SNK_BIAS_GRAVITY or both");
+    if (!mass && !bias) return api_fail(w + ": mass and bias are both null");
+    return 0;
+}
+
+// ... and of snk_jacobians
+int jacobians_args_refused(const char* who, int32_t n_rows, const void* link_rows, int32_t n_points, const void* jac) {
+    const std::string w(who);
+    if (n_rows < 1) return api_fail(w + ": n_rows must be at least 1");
+    if (n_points < 1 || n_points > SNK_JAC_MAX_POINTS)
+        return api_fail(w + ": n_points " + std::to_string(n_points) + " is outside 1 .. " + std::to_string(SNK_JAC_MAX_POINTS));
+    if (!link_rows) return api_fail(w + ": null link_rows");
+    if (!jac) return api_fail(w + ": null jac");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t snk_dyn_dofs(const snk_handle* h) {
+    if (!h) { api_fail("snk_dyn_dofs: null handle"); return 0; }
+    snk::WorldView v;
+    if (snk::world_view(const_cast<snk_handle*>(h), false, &v)) return 0;
+    return v.n + 6;
+}
+
+int snk_dynamics(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, int32_t flags, float* mass_dev, float* bias_dev,
+                 void* stream) {
+    if (!h) return api_fail("snk_dynamics: null handle (h)");
+    if (dynamics_args_refused("snk_dynamics", n_rows, flags, mass_dev, bias_dev)) return 1;
+    if (reinterpret_cast<uintptr_t>(mass_dev) % 16 != 0)
+        return api_fail("snk_dynamics: mass_dev must be 16-byte aligned (the blocks leave as 16-byte stores)");
+    if (reinterpret_cast<uintptr_t>(bias_dev) % 4 != 0) return api_fail("snk_dynamics: bias_dev must be 4-byte aligned");
+    snk::WorldView v;
+    if (snk::world_view(h, false, &v)) return 1;
+    return snk::launch_variant("snk_dynamics", v.n, v.v2, [&](auto n, auto v2) {
+        hipLaunchKernelGGL((snk::dynamics_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64), 0,
+                           (hipStream_t)stream, v.d_model, v.d_recs, env_ids_dev, flags, mass_dev, bias_dev, n_rows, v.n_envs);
+    });
+}
+
+int snk_dynamics_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, int32_t flags, float* mass, float* bias) {
+    if (!h) return api_fail("snk_dynamics_host: null handle (h)");
+    if (dynamics_args_refused("snk_dynamics_host", n_rows, flags, mass, bias)) return 1;
+    snk::WorldView v;
+    if (snk::world_view(h, true, &v)) return 1;
+    if (env_ids ? snk::check_env_ids("snk_dynamics_host", "env_ids", env_ids, n_rows, v.n_envs)
+                : snk::check_count_without_ids("snk_dynamics_host", "n_rows", n_rows, v.n_envs)) return 1;
+    const size_t nd = (size_t)v.n + 6;
+    snk::HostCall c;
+    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    float* d_mass = c.out(mass, (size_t)n_rows * nd * nd * sizeof(float));
+    float* d_bias = c.out(bias, (size_t)n_rows * nd * sizeof(float));
+    if (c.ok() && snk_dynamics(h, d_ids, n_rows, flags, d_mass, d_bias, nullptr)) return 1;
+    return c.finish("snk_dynamics_host");
+}
+
+int snk_jacobians(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, const int32_t* link_rows_dev, const float* local_dev,
+                  int32_t n_points, float* jac_dev, void* stream) {
+    if (!h) return api_fail("snk_jacobians: null handle (h)");
+    if (jacobians_args_refused("snk_jacobians", n_rows, link_rows_dev, n_points, jac_dev)) return 1;
+    if (reinterpret_cast<uintptr_t>(jac_dev) % 16 != 0)
+        return api_fail("snk_jacobians: jac_dev must be 16-byte aligned (the blocks leave as 16-byte stores)");
+    if (reinterpret_cast<uintptr_t>(link_rows_dev) % 4 != 0 || reinterpret_cast<uintptr_t>(local_dev) % 4 != 0)
+        return api_fail("snk_jacobians: link_rows_dev and local_dev must be 4-byte aligned");
+    snk::WorldView v;
+    if (snk::world_view(h, false, &v)) return 1;
+    return snk::launch_variant("snk_jacobians", v.n, v.v2, [&](auto n, auto v2) {
+        hipLaunchKernelGGL((snk::jacobians_kernel<decltype(n)::value, decltype(v2)::value>), dim3(snk::grid_for(n_rows)), dim3(64), 0,
+                           (hipStream_t)stream, v.d_model, v.d_recs, v.d_links, env_ids_dev, link_rows_dev, local_dev, n_points,
+                           jac_dev, n_rows, v.n_envs);
+    });
+}
+
+int snk_jacobians_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, const int32_t* link_rows, const float* local,
+                       int32_t n_points, float* jac) {
+    if (!h) return api_fail("snk_jacobians_host: null handle (h)");
+    if (jacobians_args_refused("snk_jacobians_host", n_rows, link_rows, n_points, jac)) return 1;
+    snk::WorldView v;
+    if (snk::world_view(h, true, &v)) return 1;
+    if (env_ids ? snk::check_env_ids("snk_jacobians_host", "env_ids", env_ids, n_rows, v.n_envs)
+                : snk::check_count_without_ids("snk_jacobians_host", "n_rows", n_rows, v.n_envs)) return 1;
+    const int last = snk::link_rows(v.n) - 1;
+    for (int p = 0; p < n_points; p++)
+        if (link_rows[p] < 0 || link_rows[p] > last)
+            return api_fail("snk_jacobians_host: link_rows[" + std::to_string(p) + "] = " + std::to_string(link_rows[p]) +
+                            " is outside 0 .. " + std::to_string(last));
+    for (int i = 0; local && i < 3 * n_points; i++)
+        if (!std::isfinite(local[i]))
+            return api_fail("snk_jacobians_host: local[" + std::to_string(i / 3) + "][" + std::to_string(i % 3) + "] is not finite");
+    const size_t nd = (size_t)v.n + 6;
+    snk::HostCall c;
+    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const int32_t* d_rows = c.in(link_rows, (size_t)n_points * sizeof(int32_t));
+    const float* d_local = c.in(local, (size_t)n_points * 3 * sizeof(float));
+    float* d_jac = c.out(jac, (size_t)n_rows * n_points * 6 * nd * sizeof(float));
+    if (c.ok() && snk_jacobians(h, d_ids, n_rows, d_rows, d_local, n_points, d_jac, nullptr)) return 1;
+    return c.finish("snk_jacobians_host");
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // snk_seam.hpp -- what the other translation units of libsnk.so (snk_render.hip: the renderer; snk_world.hip: link
-// states, contacts and the env fork) may see of a handle, and the host scaffolding every entry-point pair shares.
+// states, contacts and the env fork; snk_dyn.hip: mass matrix, bias forces, link Jacobians) may see of a handle, and the host scaffolding every entry-point pair shares.
 // snk_handle itself stays private to snk_api.hip; this is the one host-side seam between the objects of libsnk.so.  No
 // device code here: the step kernels' code object does not change with the renderer or with the world kernels.
 #pragma once

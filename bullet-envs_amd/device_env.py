@@ -384,6 +384,79 @@ class DeviceWorld(_TensorArgs):
         hits = self.ray_test(rays, env_ids, parent_row, flags)
         return hits[..., 0] * (rays[..., 3:6] - rays[..., 0:3]).norm(dim=-1)
 
+    def dynamics(self, env_ids=None, gravity=True, velocity=True, out=None):
+        """(M [k, nd, nd] float32, h [k, nd] float32), nd = 6 + n: the joint-space inertia and the bias forces of the envs
+        `env_ids` (None: all; an int32 CUDA tensor or a sequence; ids may repeat, any order; an id outside the handle gives
+        zeros) at the state they hold, by one launch (snk_dynamics; include/snk.h has the contract): M du/dt + h = Q over
+        u = [omega 3 | v of the root origin 3 | qd n] -- PyBullet's calculateMassMatrix and calculateInverseDynamics(q, qd,
+        0).  gravity / velocity: the terms of h.  out: an (M, h) tuple of tensors to write into."""
+        ids, k = self._ids(env_ids)
+        nd = self.n + 6
+        mo, ho = (None, None) if out is None else out
+        M = self._out(mo, "out[0]", (k, nd, nd))
+        h = self._out(ho, "out[1]", (k, nd))
+        self.stepper.dynamics_device(ids.data_ptr() if ids is not None else 0, k, self._bias_flags(gravity, velocity),
+                                     M.data_ptr(), h.data_ptr(), self._stream())
+        self._keep(ids)
+        return M, h
+
+    @staticmethod
+    def _bias_flags(gravity, velocity):
+        flags = (_lib.BIAS_GRAVITY if gravity else 0) | (_lib.BIAS_VELOCITY if velocity else 0)
+        if not flags:
+            raise ValueError("bias forces need gravity, velocity or both")
+        return flags
+
+    def mass_matrix(self, env_ids=None, out=None):
+        """[k, nd, nd] float32: M(q) alone (dynamics' first output), symmetric bit for bit; 1/2 u^T M u is the kinetic
+        energy."""
+        ids, k = self._ids(env_ids)
+        nd = self.n + 6
+        out = self._out(out, "out", (k, nd, nd))
+        self.stepper.dynamics_device(ids.data_ptr() if ids is not None else 0, k, _lib.BIAS_VELOCITY | _lib.BIAS_GRAVITY,
+                                     mass_ptr=out.data_ptr(), stream=self._stream())
+        self._keep(ids)
+        return out
+
+    def bias_forces(self, env_ids=None, gravity=True, velocity=True, out=None):
+        """[k, nd] float32: h alone (dynamics' second output): the Coriolis, centrifugal and gyroscopic forces at the
+        state's u (`velocity`) minus the generalised gravity force (`gravity`); gravity alone is what a controller adds to
+        hold the pose.  Rigid bodies only: none of the integrator's damping."""
+        ids, k = self._ids(env_ids)
+        out = self._out(out, "out", (k, self.n + 6))
+        self.stepper.dynamics_device(ids.data_ptr() if ids is not None else 0, k, self._bias_flags(gravity, velocity),
+                                     bias_ptr=out.data_ptr(), stream=self._stream())
+        self._keep(ids)
+        return out
+
+    def jacobians(self, link_rows, local=None, env_ids=None, out=None):
+        """[k, P, 6, nd] float32: PyBullet's calculateJacobian for P points of the envs `env_ids` (None: all; an int32 CUDA
+        tensor or a sequence; ids may repeat, any order; an id outside the handle gives zeros), by one launch
+        (snk_jacobians).  link_rows: P rows of link_states (Bullet link + 1), a list or an int32 tensor, shared by every
+        env; local: [P, 3] float32 points in the links' COM frames, a list or a tensor (None: the COMs).  Rows 0-2: the
+        point's world velocity per unit of each component of u; rows 3-5: the link's angular velocity.  A link row outside
+        0 .. 3n + 1 gives a zero Jacobian."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        rows = t.as_tensor(link_rows, dtype=t.int32, device=self.device).reshape(-1).contiguous()
+        P = int(rows.numel())
+        if not 1 <= P <= _lib.JAC_MAX_POINTS:
+            raise ValueError("link_rows must name 1 .. %d points, got %d" % (_lib.JAC_MAX_POINTS, P))
+        loc = None
+        if local is not None:
+            loc = t.as_tensor(local, device=self.device)
+            if loc.dtype != t.float32 and isinstance(local, t.Tensor):
+                raise ValueError("local must be torch.float32, got %s" % loc.dtype)
+            loc = loc.to(t.float32)
+            if tuple(loc.shape) != (P, 3):
+                raise ValueError("local must have shape %s, got %s" % ((P, 3), tuple(loc.shape)))
+            loc = loc.contiguous()
+        out = self._out(out, "out", (k, P, 6, self.n + 6))
+        self.stepper.jacobians_device(ids.data_ptr() if ids is not None else 0, k, rows.data_ptr(),
+                                      loc.data_ptr() if loc is not None else 0, P, out.data_ptr(), self._stream())
+        self._keep(ids, rows, loc)
+        return out
+
     def reset(self, mask=None, out=None):
         """The soft reset (snake.py:96-99, 119-127) of the envs of `mask` (uint8 / bool [E]; None: all) onto their rows
         of the reset-pose table.  Returns the observations [E, 3n + 8]; rows of unmasked envs are left as `out` had them

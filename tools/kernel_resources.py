@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def device_asm(root, args, out, src="csrc/snk_api.hip"):
     """Compiles <root>/bullet-envs_amd/<src> (the step kernels' translation unit; main() also lists the renderer's,
-    csrc/snk_render.hip, and the world kernels', csrc/snk_world.hip) device-only to assembly with the product's own flags (that tree's
+    csrc/snk_render.hip, the world kernels', csrc/snk_world.hip, and the dynamics queries', csrc/snk_dyn.hip) device-only to assembly with the product's own flags (that tree's
     `build.py --print-flags`) plus `args`; returns the command.  (tools/same_isa.py compares two trees with it.)"""
     pkg = os.path.join(root, "bullet-envs_amd")
     flags = subprocess.check_output([sys.executable, os.path.join(pkg, "build.py"), "--print-flags"], text=True).split()
@@ -25,7 +25,7 @@ def device_asm(root, args, out, src="csrc/snk_api.hip"):
 
 def main():
     print("%-46s %6s %6s %9s %5s" % ("kernel", "VGPRs", "SGPRs", "scratch B", "occ"))
-    for src in ("csrc/snk_api.hip", "csrc/snk_render.hip", "csrc/snk_world.hip"):
+    for src in ("csrc/snk_api.hip", "csrc/snk_render.hip", "csrc/snk_world.hip", "csrc/snk_dyn.hip"):
         if os.path.exists(os.path.join(ROOT, "bullet-envs_amd", src)):
             one(src)
 

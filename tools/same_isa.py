@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Is the device code of the working tree the same as that of a git revision?  Compiles each of the three translation units
-(csrc/snk_api.hip, snk_render.hip, snk_world.hip) device-only to assembly (tools/kernel_resources.py: build.py's flags) for
+"""Is the device code of the working tree the same as that of a git revision?  Compiles each of the four translation units
+(csrc/snk_api.hip, snk_render.hip, snk_world.hip, snk_dyn.hip) device-only to assembly (tools/kernel_resources.py: build.py's flags) for
 both, drops the lines that carry the `__hip_cuid_<hash>` symbol (it hashes the input) and prints one verdict per file:
-`identical`, or else the symbols whose text differs (exit status 1 if any file differs).  The check for a
+`identical`, or else the symbols whose text differs (exit status 1 if any file differs); a unit the revision does not
+have is `new in the working tree` with its kernels listed, and no difference.  The check for a
 change that is meant to move or rename code without touching what the compiler makes of it.
     python tools/same_isa.py [REVISION (default HEAD)] [-DSNK_PROFILE ...]"""
 import os
@@ -14,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 from kernel_resources import ROOT, device_asm
 
-SOURCES = ("csrc/snk_api.hip", "csrc/snk_render.hip", "csrc/snk_world.hip")
+SOURCES = ("csrc/snk_api.hip", "csrc/snk_render.hip", "csrc/snk_world.hip", "csrc/snk_dyn.hip")
 
 
 def sections(path):
@@ -43,9 +44,16 @@ def main():
         # (each tree is compiled with its own headers under its own names: a header renamed between the two is no difference)
         jobs = [(src, root, os.path.join(td, "%s_%d.s" % (tag, i))) for i, src in enumerate(SOURCES)
                 for root, tag in ((old, "old"), (ROOT, "new"))]
+        have = [os.path.exists(os.path.join(root, "bullet-envs_amd", src)) for src, root, out in jobs]
         with ThreadPoolExecutor(len(jobs)) as ex:
-            [j.result() for j in [ex.submit(device_asm, root, defines, out, src) for src, root, out in jobs]]
+            [j.result() for j in [ex.submit(device_asm, root, defines, out, src) for (src, root, out), h in zip(jobs, have) if h]]
         for i, src in enumerate(SOURCES):
+            if not have[2 * i] or not have[2 * i + 1]:
+                side = 2 * i + 1 if have[2 * i + 1] else 2 * i
+                kernels = sorted(k for k in sections(jobs[side][2]) if k.startswith("_Z") and "kernel" in k) if have[side] else []
+                print("%s: %s (%d kernels: %s)" % (src, "new in the working tree" if have[2 * i + 1] else "only in " + rev,
+                                                   len(kernels), " ".join(kernels)))
+                continue
             a, b = sections(jobs[2 * i][2]), sections(jobs[2 * i + 1][2])
             differ = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
             if not differ and list(a) == list(b):
