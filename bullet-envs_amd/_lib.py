@@ -397,17 +397,26 @@ class Stepper:
               "snk_reset_host")
         return obs
 
-    def step(self, actions, vec_mode=True):
-        """actions float32 [n_envs, act_dim], clipped in place.  Returns obs, rew, done, substeps."""
+    def _step(self, actions, vec_mode, traced):
+        """step and step_traced, as step_host is in C: the trace is the only variation."""
         assert actions.dtype == np.float32 and actions.flags.c_contiguous
         assert actions.shape == (self.n_envs, self.act_dim)
         obs = np.empty((self.n_envs, self.obs_dim), dtype=np.float32)
         rew = np.empty(self.n_envs, dtype=np.float32)
         done = np.empty(self.n_envs, dtype=np.uint8)
         sub = np.empty(self.n_envs, dtype=np.int32)
-        check(self.lib.snk_step_host(self.h, fptr(actions), fptr(obs), fptr(rew), done.ctypes.data_as(_U8),
-                                     sub.ctypes.data_as(_I32), 1 if vec_mode else 0), "snk_step_host")
-        return obs, rew, done.astype(bool), sub
+        out = (fptr(actions), fptr(obs), fptr(rew), done.ctypes.data_as(_U8), sub.ctypes.data_as(_I32))
+        if not traced:
+            check(self.lib.snk_step_host(self.h, *out, 1 if vec_mode else 0), "snk_step_host")
+            return obs, rew, done.astype(bool), sub
+        trace = np.full(self.trace_shape(), np.nan, dtype=np.float32)
+        check(self.lib.snk_step_traced_host(self.h, *out, fptr(trace), trace.shape[1], 1 if vec_mode else 0),
+              "snk_step_traced_host")
+        return obs, rew, done.astype(bool), sub, trace
+
+    def step(self, actions, vec_mode=True):
+        """actions float32 [n_envs, act_dim], clipped in place.  Returns obs, rew, done, substeps."""
+        return self._step(actions, vec_mode, False)
 
     def trace_shape(self):
         """[n_envs, rows, floats per row] of the trace step_traced returns (rows = max_counter + 1)."""
@@ -417,17 +426,7 @@ class Stepper:
         """step() that also records every physics substep (snk_step_traced_host).  Returns obs, rew, done, substeps,
         trace; trace [n_envs, max_counter + 1, row] float32: row s < substeps[i] of env i = [observation after substep s
         (3n + 8) | link positions (3(n + 1), x.. y.. z..) | padding]; the other rows are left as allocated (NaN here)."""
-        assert actions.dtype == np.float32 and actions.flags.c_contiguous
-        assert actions.shape == (self.n_envs, self.act_dim)
-        obs = np.empty((self.n_envs, self.obs_dim), dtype=np.float32)
-        rew = np.empty(self.n_envs, dtype=np.float32)
-        done = np.empty(self.n_envs, dtype=np.uint8)
-        sub = np.empty(self.n_envs, dtype=np.int32)
-        trace = np.full(self.trace_shape(), np.nan, dtype=np.float32)
-        check(self.lib.snk_step_traced_host(self.h, fptr(actions), fptr(obs), fptr(rew), done.ctypes.data_as(_U8),
-                                            sub.ctypes.data_as(_I32), fptr(trace), trace.shape[1], 1 if vec_mode else 0),
-              "snk_step_traced_host")
-        return obs, rew, done.astype(bool), sub, trace
+        return self._step(actions, vec_mode, True)
 
     def substep(self, targets, k=1):
         t = np.ascontiguousarray(targets, dtype=np.float32)

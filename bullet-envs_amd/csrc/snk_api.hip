@@ -44,18 +44,7 @@ struct snk_handle {
     snk::DevModel* d_model = nullptr;
     float* d_recs = nullptr;
     float* d_mu = nullptr;
-    // scratch for the host-buffer forms
-    float* d_act = nullptr;
-    float* d_obs = nullptr;
-    float* d_rew = nullptr;
-    uint8_t* d_done = nullptr;
-    int32_t* d_sub = nullptr;
-    uint8_t* d_mask = nullptr;
-    float* d_tgt = nullptr;
-    int32_t* d_info = nullptr;
-    float* d_h = nullptr;
-    float* d_linkpos = nullptr;   // made on first snk_link_positions (ensure)
-    float* d_trace = nullptr;     // made and grown by snk_step_traced_host (ensure): [n_envs][trace_rows][trace row floats]
+    void* d_stage = nullptr;      // the staging arena of every host form (snk::stage_arena), made on the first such call
     float* d_mf = nullptr;        // contact_model 1: the persistent contact manifolds, [n_envs][2n][kMfFloats]
     float* d_rows = nullptr;      // 32-link chains: constraint rows streamed from global memory (snk_device.hpp: pgs_v1)
     unsigned long long* d_ovf = nullptr;   // contacts the solves had no room for (snk_contact_overflow): 3 counters
@@ -278,7 +267,7 @@ int timed_step(snk_handle* h, float* act, float* obs, float* rew, uint8_t* done,
     return snk::launch_ok(nullptr);
 }
 
-// one obs_kernel pass over h's records, enqueued on st (snk_observe; the host read-outs below)
+// one obs_kernel pass over h's records, enqueued on st (snk_observe)
 int launch_obs(snk_handle* h, float* obs, float* height, float* linkpos, hipStream_t st) {
     h->rows_of_substep = false;
     const int rc = dispatch(h, [&](auto k) {
@@ -287,13 +276,6 @@ int launch_obs(snk_handle* h, float* obs, float* height, float* linkpos, hipStre
         return 0;
     });
     return (rc || snk::launch_ok(nullptr)) ? 1 : 0;
-}
-// that pass (the device idle, the handle alive), and its one output copied to out
-int obs_pass(snk_handle* h, float* obs, float* height, float* linkpos, void* out, size_t bytes) {
-    if (launch_obs(h, obs, height, linkpos, nullptr)) return 1;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, obs ? obs : (height ? height : linkpos), bytes, hipMemcpyDeviceToHost));
-    return 0;
 }
 
 // A contact manifold on the host (the oracle's layout): [count, 4 x (point on the link in link coordinates 3, point on
@@ -412,6 +394,10 @@ int world_view(snk_handle* h, bool sync, WorldView* v) {
     return 0;
 }
 float* render_scratch(snk_handle* h, size_t need) { return ensure(h, &h->d_render, need) ? nullptr : h->d_render; }
+// (SNK_POISON: a new or replaced arena starts as NaNs, like every fresh allocation of init_handle)
+void* stage_arena(snk_handle* h, size_t need) {
+    return ensure(h, &h->d_stage, need, h->D.poison ? 0xFF : kNoFill) ? nullptr : h->d_stage;
+}
 }  // namespace snk
 
 extern "C" {
@@ -517,7 +503,6 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     // SNK_POISON=1 (tests): the kernels' LDS images and every fresh device allocation start as NaNs instead of as
     // whatever was there, so that a read of something never written shows in the outputs
     const bool poison = getenv("SNK_POISON") != nullptr;
-    const int nans = poison ? 0xFF : kNoFill;
     h->D.poison = poison ? 1 : 0;
     h->D.hist = 0;
     h->rec = h->D.rec_floats;
@@ -545,13 +530,7 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
     if (ensure(h, &h->d_model, sizeof(snk::DevModel)) ||
         ensure(h, &h->d_recs, ne * h->rec * f, 0) ||
         ensure(h, &h->d_mu, ne * f) ||
-        ensure(h, &h->d_act, ne * h->D.act_dim * f, nans) ||
-        ensure(h, &h->d_obs, ne * h->D.obs_dim * f, nans) ||
-        ensure(h, &h->d_rew, ne * f, nans) ||
-        ensure(h, &h->d_tgt, ne * h->n * f, nans) ||
-        ensure(h, &h->d_h, ne * f, nans) ||
-        ensure(h, &h->d_done, ne) || ensure(h, &h->d_mask, ne) || ensure(h, &h->d_sub, ne * sizeof(int32_t)) ||
-        ensure(h, &h->d_info, ne * 2 * sizeof(int32_t)) || ensure(h, &h->d_order, ne * sizeof(int32_t)) ||
+        ensure(h, &h->d_order, ne * sizeof(int32_t)) ||
         ensure(h, &h->d_rows, nb * rf * f, poison ? 0xFF : 0) ||
         (p->obstacle == 2 && ensure(h, &h->d_box, ne * snk::kBoxFloats * f)) ||
         ensure(h, &h->d_reset, ne * R * f) ||
@@ -755,48 +734,43 @@ int snk_reset_host(snk_handle* h, const uint8_t* mask, float* obs) {
     if (!h) return fail("snk_reset_host: null handle");
     if (enter(h, kDev | kAlive)) return 1;
     const size_t ne = (size_t)h->n_envs;
-    if (mask) HIP_TRY(hipMemcpy(h->d_mask, mask, ne, hipMemcpyHostToDevice));
-    if (obs) HIP_TRY(hipMemcpy(h->d_obs, obs, ne * h->D.obs_dim * sizeof(float), hipMemcpyHostToDevice));
-    int rc = snk_reset(h, mask ? h->d_mask : nullptr, obs ? h->d_obs : nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (obs) HIP_TRY(hipMemcpy(obs, h->d_obs, ne * h->D.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    snk::HostCall c(h);
+    const auto s_mask = c.in(mask, ne);
+    const auto s_obs = c.inout(obs, ne * h->D.obs_dim * sizeof(float));      // (unmasked rows come back as they went)
+    if (c.stage() && snk_reset(h, s_mask, s_obs, nullptr)) return 1;
+    return c.finish("snk_reset_host");
 }
 
-// snk_step_host (trace null) and snk_step_traced_host: the alarm, the upload, the step, the device idle, the alarm again,
-// the downloads.  The callers have refused their null arguments.
-static int step_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps, float* trace,
-                     int32_t trace_rows, int32_t vec_mode) {
+// snk_step_host (trace null) and snk_step_traced_host (`who`): the alarm, the upload, the step, the device idle, the alarm
+// again, the downloads.  The callers have refused their null arguments.
+static int step_host(const char* who, snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
+                     float* trace, int32_t trace_rows, int32_t vec_mode) {
     if (enter(h, kDev | kAlive)) return 1;
-    const size_t ne = (size_t)h->n_envs, na = ne * h->D.act_dim * sizeof(float);
-    const size_t tbytes = trace ? ne * (size_t)trace_rows * trace_row_floats(h->n) * sizeof(float) : 0;
-    if (trace) {
-        if (ensure(h, &h->d_trace, tbytes)) return 1;
+    const size_t ne = (size_t)h->n_envs, f = sizeof(float);
+    const size_t tbytes = trace ? ne * (size_t)trace_rows * trace_row_floats(h->n) * f : 0;
+    snk::HostCall c(h);
+    const auto s_act = c.inout(actions, ne * h->D.act_dim * f);      // (clipped in place)
+    const auto s_obs = c.out(obs, ne * h->D.obs_dim * f);
+    const auto s_rew = c.out(rew, ne * f);
+    const auto s_done = c.out(done, ne);
+    const auto s_sub = c.out(substeps, ne * sizeof(int32_t));
+    const auto s_trace = c.out(trace, tbytes);
+    if (c.stage()) {
         // what the kernel does not write -- the padding of a row, the rows from an env's count on -- comes back as NaNs
         // (all bits set), whatever the caller's buffer held
-        HIP_TRY(hipMemsetAsync(h->d_trace, 0xFF, tbytes, nullptr));
+        if (trace) HIP_TRY(hipMemsetAsync(s_trace, 0xFF, tbytes, nullptr));
+        if (trace ? snk_step_traced(h, s_act, s_obs, s_rew, s_done, s_sub, s_trace, trace_rows, vec_mode, nullptr)
+                  : snk_step(h, s_act, s_obs, s_rew, s_done, s_sub, vec_mode, nullptr)) return 1;
     }
-    HIP_TRY(hipMemcpy(h->d_act, actions, na, hipMemcpyHostToDevice));
-    const int rc = trace ? snk_step_traced(h, h->d_act, h->d_obs, h->d_rew, h->d_done, h->d_sub, h->d_trace, trace_rows, vec_mode, nullptr)
-                         : snk_step(h, h->d_act, h->d_obs, h->d_rew, h->d_done, h->d_sub, vec_mode, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (check_alarm(h)) return 1;
-    HIP_TRY(hipMemcpy(actions, h->d_act, na, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(obs, h->d_obs, ne * h->D.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rew, h->d_rew, ne * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(done, h->d_done, ne, hipMemcpyDeviceToHost));
-    if (substeps) HIP_TRY(hipMemcpy(substeps, h->d_sub, ne * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (trace) HIP_TRY(hipMemcpy(trace, h->d_trace, tbytes, hipMemcpyDeviceToHost));
-    return 0;
+    if (c.wait(who) || check_alarm(h)) return 1;      // (a step that poisoned the handle downloads nothing)
+    return c.download(who);
 }
 
 int snk_step_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
                   int32_t vec_mode) {
     if (!h) return fail("snk_step_host: null handle");
     if (!actions || !obs || !rew || !done) return fail("snk_step_host: null buffer");
-    return step_host(h, actions, obs, rew, done, substeps, nullptr, 0, vec_mode);
+    return step_host("snk_step_host", h, actions, obs, rew, done, substeps, nullptr, 0, vec_mode);
 }
 
 int snk_step_traced_host(snk_handle* h, float* actions, float* obs, float* rew, uint8_t* done, int32_t* substeps,
@@ -804,7 +778,7 @@ int snk_step_traced_host(snk_handle* h, float* actions, float* obs, float* rew, 
     if (!h) return fail("snk_step_traced_host: null handle");
     if (!actions || !obs || !rew || !done || !substeps || !trace) return fail("snk_step_traced_host: null buffer");
     if (trace_rows <= 0) return fail("snk_step_traced_host: trace_rows must be positive");
-    return step_host(h, actions, obs, rew, done, substeps, trace, trace_rows, vec_mode);
+    return step_host("snk_step_traced_host", h, actions, obs, rew, done, substeps, trace, trace_rows, vec_mode);
 }
 
 int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* info) {
@@ -812,11 +786,11 @@ int snk_substep_host(snk_handle* h, const float* targets, int32_t k, int32_t* in
     if (k < 0) return fail("snk_substep_host: k < 0");
     if (enter(h, kDev | kAlive)) return 1;
     const size_t ne = (size_t)h->n_envs;
-    HIP_TRY(hipMemcpy(h->d_tgt, targets, ne * h->n * sizeof(float), hipMemcpyHostToDevice));
-    if (dispatch(h, [&](auto v) { return launch_substep(v, h, h->d_tgt, k, h->d_info, nullptr, nullptr); }) || snk::launch_ok(nullptr)) return 1;
-    HIP_TRY(hipDeviceSynchronize());
-    if (info) HIP_TRY(hipMemcpy(info, h->d_info, ne * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return 0;
+    snk::HostCall c(h);
+    const auto s_tgt = c.in(targets, ne * h->n * sizeof(float));
+    const auto s_info = c.out(info, ne * 2 * sizeof(int32_t));
+    if (c.stage() && snk_substep(h, s_tgt, k, nullptr, s_info, nullptr)) return 1;
+    return c.finish("snk_substep_host");
 }
 
 int snk_substep(snk_handle* h, const float* targets_dev, int32_t k, const uint8_t* active_dev, int32_t* info_dev, void* stream) {
@@ -970,19 +944,26 @@ int snk_contact_histogram(snk_handle* h, uint64_t* out, int32_t reset) {
 int snk_get_obs(snk_handle* h, float* obs) {
     if (!h || !obs) return fail("snk_get_obs: null argument");
     if (enter(h, kState)) return 1;
-    return obs_pass(h, h->d_obs, nullptr, nullptr, obs, (size_t)h->n_envs * h->D.obs_dim * sizeof(float));
+    snk::HostCall c(h);
+    const auto s_obs = c.out(obs, (size_t)h->n_envs * h->D.obs_dim * sizeof(float));
+    if (c.stage() && snk_observe(h, s_obs, nullptr, nullptr, nullptr)) return 1;
+    return c.finish("snk_get_obs");
 }
 int snk_mean_height(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_mean_height: null argument");
     if (enter(h, kState)) return 1;
-    return obs_pass(h, nullptr, h->d_h, nullptr, out, (size_t)h->n_envs * sizeof(float));
+    snk::HostCall c(h);
+    const auto s_height = c.out(out, (size_t)h->n_envs * sizeof(float));
+    if (c.stage() && snk_observe(h, nullptr, s_height, nullptr, nullptr)) return 1;
+    return c.finish("snk_mean_height");
 }
 int snk_link_positions(snk_handle* h, float* out) {
     if (!h || !out) return fail("snk_link_positions: null argument");
     if (enter(h, kState)) return 1;
-    const size_t bytes = (size_t)h->n_envs * 3 * (h->n + 1) * sizeof(float);
-    if (ensure(h, &h->d_linkpos, bytes)) return 1;
-    return obs_pass(h, nullptr, nullptr, h->d_linkpos, out, bytes);
+    snk::HostCall c(h);
+    const auto s_pos = c.out(out, (size_t)h->n_envs * 3 * (h->n + 1) * sizeof(float));
+    if (c.stage() && snk_observe(h, nullptr, nullptr, s_pos, nullptr)) return 1;
+    return c.finish("snk_link_positions");
 }
 
 int snk_set_ground_friction(snk_handle* h, const float* mu) {

@@ -71,11 +71,11 @@ int snk_dynamics_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, int
     if (env_ids ? snk::check_env_ids("snk_dynamics_host", "env_ids", env_ids, n_rows, v.n_envs)
                 : snk::check_count_without_ids("snk_dynamics_host", "n_rows", n_rows, v.n_envs)) return 1;
     const size_t nd = (size_t)v.n + 6;
-    snk::HostCall c;
-    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
-    float* d_mass = c.out(mass, (size_t)n_rows * nd * nd * sizeof(float));
-    float* d_bias = c.out(bias, (size_t)n_rows * nd * sizeof(float));
-    if (c.ok() && snk_dynamics(h, d_ids, n_rows, flags, d_mass, d_bias, nullptr)) return 1;
+    snk::HostCall c(h);
+    const auto d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const auto d_mass = c.out(mass, (size_t)n_rows * nd * nd * sizeof(float));
+    const auto d_bias = c.out(bias, (size_t)n_rows * nd * sizeof(float));
+    if (c.stage() && snk_dynamics(h, d_ids, n_rows, flags, d_mass, d_bias, nullptr)) return 1;
     return c.finish("snk_dynamics_host");
 }
 
@@ -113,12 +113,12 @@ int snk_jacobians_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, co
         if (!std::isfinite(local[i]))
             return api_fail("snk_jacobians_host: local[" + std::to_string(i / 3) + "][" + std::to_string(i % 3) + "] is not finite");
     const size_t nd = (size_t)v.n + 6;
-    snk::HostCall c;
-    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
-    const int32_t* d_rows = c.in(link_rows, (size_t)n_points * sizeof(int32_t));
-    const float* d_local = c.in(local, (size_t)n_points * 3 * sizeof(float));
-    float* d_jac = c.out(jac, (size_t)n_rows * n_points * 6 * nd * sizeof(float));
-    if (c.ok() && snk_jacobians(h, d_ids, n_rows, d_rows, d_local, n_points, d_jac, nullptr)) return 1;
+    snk::HostCall c(h);
+    const auto d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const auto d_rows = c.in(link_rows, (size_t)n_points * sizeof(int32_t));
+    const auto d_local = c.in(local, (size_t)n_points * 3 * sizeof(float));
+    const auto d_jac = c.out(jac, (size_t)n_rows * n_points * 6 * nd * sizeof(float));
+    if (c.stage() && snk_jacobians(h, d_ids, n_rows, d_rows, d_local, n_points, d_jac, nullptr)) return 1;
     return c.finish("snk_jacobians_host");
 }
 

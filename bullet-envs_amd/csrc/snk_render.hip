@@ -101,13 +101,13 @@ int snk_render_host(snk_handle* h, const int32_t* env_ids, int32_t n_images, con
             return api_fail(msg);
         }
     const size_t px = (size_t)n_images * width * height;
-    snk::HostCall c;
-    const int32_t* d_ids = c.in(env_ids, (size_t)n_images * 4);
-    const float* d_cam = c.in(cameras, ncam * 32 * 4);
-    uint8_t* d_rgba = c.out(rgba, px * 4);
-    float* d_depth = c.out(depth, px * 4);
-    int32_t* d_seg = c.out(seg, px * 4);
-    if (c.ok() && snk_render(h, d_ids, n_images, d_cam, shared_camera, width, height, flags, d_rgba, d_depth, d_seg, nullptr))
+    snk::HostCall c(h);
+    const auto d_ids = c.in(env_ids, (size_t)n_images * 4);
+    const auto d_cam = c.in(cameras, ncam * 32 * 4);
+    const auto d_rgba = c.out(rgba, px * 4);
+    const auto d_depth = c.out(depth, px * 4);
+    const auto d_seg = c.out(seg, px * 4);
+    if (c.stage() && snk_render(h, d_ids, n_images, d_cam, shared_camera, width, height, flags, d_rgba, d_depth, d_seg, nullptr))
         return 1;
     return c.finish("snk_render_host");
 }
@@ -162,11 +162,11 @@ int snk_ray_test_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, con
                           ray % (size_t)n_rays, k % SNK_RAY_FLOATS);
             return api_fail(msg);
         }
-    snk::HostCall c;
-    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
-    const float* d_rays = c.in(rays, nray * SNK_RAY_FLOATS * sizeof(float));
-    float* d_hits = c.out(hits, total * SNK_HIT_FLOATS * sizeof(float));
-    if (c.ok() && snk_ray_test(h, d_ids, n_rows, d_rays, n_rays, parent_row, flags, d_hits, nullptr)) return 1;
+    snk::HostCall c(h);
+    const auto d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const auto d_rays = c.in(rays, nray * SNK_RAY_FLOATS * sizeof(float));
+    const auto d_hits = c.out(hits, total * SNK_HIT_FLOATS * sizeof(float));
+    if (c.stage() && snk_ray_test(h, d_ids, n_rows, d_rays, n_rays, parent_row, flags, d_hits, nullptr)) return 1;
     return c.finish("snk_ray_test_host");
 }
 

@@ -57,10 +57,10 @@ int snk_link_states_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, 
     if (snk::world_view(h, true, &v)) return 1;
     if (env_ids ? snk::check_env_ids("snk_link_states_host", "env_ids", env_ids, n_rows, v.n_envs)
                 : snk::check_count_without_ids("snk_link_states_host", "n_rows", n_rows, v.n_envs)) return 1;
-    snk::HostCall c;
-    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
-    float* d_out = c.out(out, (size_t)n_rows * snk::link_rows(v.n) * snk::kLinkStateFloats * sizeof(float));
-    if (c.ok() && snk_link_states(h, d_ids, n_rows, d_out, nullptr)) return 1;
+    snk::HostCall c(h);
+    const auto d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const auto d_out = c.out(out, (size_t)n_rows * snk::link_rows(v.n) * snk::kLinkStateFloats * sizeof(float));
+    if (c.stage() && snk_link_states(h, d_ids, n_rows, d_out, nullptr)) return 1;
     return c.finish("snk_link_states_host");
 }
 
@@ -110,12 +110,12 @@ int snk_contacts_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, flo
     if (!slots) return api_fail("snk_contacts_host: this handle has contact_model 0 (no contact cache)");
     if (env_ids ? snk::check_env_ids("snk_contacts_host", "env_ids", env_ids, n_rows, v.n_envs)
                 : snk::check_count_without_ids("snk_contacts_host", "n_rows", n_rows, v.n_envs)) return 1;
-    snk::HostCall c;
-    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
-    float* d_pts = c.out(points, (size_t)n_rows * slots * snk::kContactFloats * sizeof(float));
-    float* d_force = c.out(force, (size_t)n_rows * (2 * v.n + 1) * sizeof(float));
-    int32_t* d_count = c.out(count, (size_t)n_rows * sizeof(int32_t));
-    if (c.ok() && snk_contacts(h, d_ids, n_rows, d_pts, d_force, d_count, nullptr)) return 1;
+    snk::HostCall c(h);
+    const auto d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const auto d_pts = c.out(points, (size_t)n_rows * slots * snk::kContactFloats * sizeof(float));
+    const auto d_force = c.out(force, (size_t)n_rows * (2 * v.n + 1) * sizeof(float));
+    const auto d_count = c.out(count, (size_t)n_rows * sizeof(int32_t));
+    if (c.stage() && snk_contacts(h, d_ids, n_rows, d_pts, d_force, d_count, nullptr)) return 1;
     return c.finish("snk_contacts_host");
 }
 
@@ -193,12 +193,12 @@ int snk_closest_points_host(snk_handle* h, const int32_t* env_ids, int32_t n_row
     if (closest_pairs_refused("snk_closest_points_host", max_pairs, v.n)) return 1;
     if (env_ids ? snk::check_env_ids("snk_closest_points_host", "env_ids", env_ids, n_rows, v.n_envs)
                 : snk::check_count_without_ids("snk_closest_points_host", "n_rows", n_rows, v.n_envs)) return 1;
-    snk::HostCall c;
-    const int32_t* d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
-    float* d_pts = c.out(points, (size_t)n_rows * (2 * v.n + max_pairs) * snk::kContactFloats * sizeof(float));
-    float* d_clr = c.out(clearance, (size_t)n_rows * 2 * 2 * v.n * sizeof(float));
-    int32_t* d_count = c.out(count, (size_t)n_rows * 2 * sizeof(int32_t));
-    if (c.ok() && snk_closest_points(h, d_ids, n_rows, distance, flags, max_pairs, d_pts, d_clr, d_count, nullptr)) return 1;
+    snk::HostCall c(h);
+    const auto d_ids = c.in(env_ids, (size_t)n_rows * sizeof(int32_t));
+    const auto d_pts = c.out(points, (size_t)n_rows * (2 * v.n + max_pairs) * snk::kContactFloats * sizeof(float));
+    const auto d_clr = c.out(clearance, (size_t)n_rows * 2 * 2 * v.n * sizeof(float));
+    const auto d_count = c.out(count, (size_t)n_rows * 2 * sizeof(int32_t));
+    if (c.stage() && snk_closest_points(h, d_ids, n_rows, distance, flags, max_pairs, d_pts, d_clr, d_count, nullptr)) return 1;
     return c.finish("snk_closest_points_host");
 }
 
@@ -251,10 +251,10 @@ int snk_copy_envs_host(snk_handle* h, const int32_t* src_ids, const int32_t* dst
             return api_fail(msg);
         }
     }
-    snk::HostCall c;
-    const int32_t* d_src = c.in(src_ids, (size_t)n_pairs * sizeof(int32_t));
-    const int32_t* d_dst = c.in(dst_ids, (size_t)n_pairs * sizeof(int32_t));
-    if (c.ok() && snk_copy_envs(h, d_src, d_dst, n_pairs, flags, nullptr)) return 1;
+    snk::HostCall c(h);
+    const auto d_src = c.in(src_ids, (size_t)n_pairs * sizeof(int32_t));
+    const auto d_dst = c.in(dst_ids, (size_t)n_pairs * sizeof(int32_t));
+    if (c.stage() && snk_copy_envs(h, d_src, d_dst, n_pairs, flags, nullptr)) return 1;
     return c.finish("snk_copy_envs_host");
 }
 

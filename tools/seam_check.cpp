@@ -1,10 +1,12 @@
 // seam_check.cpp -- the host scaffolding of csrc/snk_seam.hpp on its own, for the host sanitizers: the two id checks at
-// their edges, for_variant over supported and unsupported variants, and HostCall without a device, where every HIP call
-// fails (the error paths and the destructor).  Prints what it saw; exit status 1 if anything is not as expected.
+// their edges, for_variant over supported and unsupported variants, the carve arithmetic of the staging arena at its edges,
+// and HostCall without a device, where every HIP call fails (the error paths).  Prints what it saw; exit status 1 if
+// anything is not as expected.
 //     make -C tools seam_check && tools/seam_check        (a machine WITHOUT a GPU: the HostCall part expects the failures)
 #include <climits>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 #include "../bullet-envs_amd/csrc/snk_seam.hpp"
 
@@ -15,6 +17,10 @@ namespace snk {
 int api_fail(const char* msg) {      // libsnk.so's is snk_api.hip's; here the message is kept for the check
     g_msg = msg;
     return 1;
+}
+void* stage_arena(snk_handle*, size_t need) {      // libsnk.so's is the handle's arena; here it fails, as every HIP call does
+    void* d = nullptr;
+    return hipMalloc(&d, need) == hipSuccess ? d : nullptr;
 }
 }  // namespace snk
 
@@ -57,17 +63,42 @@ int main() {
                "snk_contacts: unsupported n_modules (16 or 32)");
         if (ran) { printf("BAD  launch_variant ran a launch for an unsupported variant\n"); g_bad++; }
     }
-    // HostCall with no device: nothing can be allocated, nothing is downloaded, the failure is reported once by finish
+    // stage_carve: offsets in whole 256-byte units, zero-byte entries without room, the total in size_t
+    {
+        const size_t A = snk::kStageAlign, G = (size_t)1 << 30;
+        struct Case { const char* what; std::vector<size_t> bytes, offsets; size_t total; };
+        const Case cases[] = {
+            {"no entries", {}, {}, 0},
+            {"one zero-byte entry", {0}, {0}, 0},
+            {"1 byte", {1}, {0}, A},
+            {"255, 256, 257 bytes", {A - 1, A, A + 1, 4}, {0, A, 2 * A, 4 * A}, 5 * A},
+            {"multiples of 256", {A, 3 * A, 2 * A}, {0, A, 4 * A}, 6 * A},
+            {"null entries between", {0, 16, 0, 0, 300, 0}, {0, 0, A, A, A, 3 * A}, 3 * A},
+            {"a total beyond 4 GiB", {3 * G + 1, 2 * G, 7}, {0, 3 * G + A, 5 * G + A}, 5 * G + 2 * A},
+        };
+        for (const Case& k : cases) {
+            std::vector<size_t> off(k.bytes.size(), ~(size_t)0);
+            const size_t total = snk::stage_carve(k.bytes.data(), k.bytes.size(), off.data());
+            const bool ok = total == k.total && off == k.offsets;
+            printf("%s stage_carve: %-24s total %zu\n", ok ? "ok  " : "BAD ", k.what, total);
+            if (!ok) g_bad++;
+        }
+    }
+    // HostCall with no device: the arena cannot be had, nothing is uploaded or downloaded, the failure is reported once by
+    // finish; null host pointers stay null, and a call of nothing but nulls asks for no arena at all
     {
         const float host_in[4] = {1, 2, 3, 4};
         float host_out[4] = {0, 0, 0, 0};
-        snk::HostCall c;
-        const float* none = c.in(static_cast<const float*>(nullptr), sizeof(host_in));
-        float* none_out = c.out(static_cast<float*>(nullptr), sizeof(host_out));
-        const bool fresh = c.ok() && !none && !none_out;
-        const float* d_in = c.in(host_in, sizeof(host_in));
-        float* d_out = c.out(host_out, sizeof(host_out));
-        const bool refused = fresh && !c.ok() && !d_in && !d_out;
+        snk::HostCall nulls(nullptr);
+        const auto none = nulls.in(static_cast<const float*>(nullptr), sizeof(host_in));
+        const auto none_out = nulls.out(static_cast<float*>(nullptr), sizeof(host_out));
+        const bool fresh = nulls.stage() && !static_cast<const float*>(none) && !static_cast<float*>(none_out);
+        snk::HostCall c(nullptr);
+        const auto d_in = c.in(host_in, sizeof(host_in));
+        const auto d_out = c.out(host_out, sizeof(host_out));
+        const auto d_both = c.inout(host_out, sizeof(host_out));
+        const bool refused = fresh && !c.stage() && !static_cast<const float*>(d_in) && !static_cast<float*>(d_out) &&
+                             !static_cast<float*>(d_both);
         const int rc = c.finish("snk_seam_check");
         const bool ok = refused && rc == 1 && g_msg.rfind("snk_seam_check: ", 0) == 0 && g_msg.size() > 16 && host_out[0] == 0.f;
         printf("%s HostCall without a device         rc %d  %s\n", ok ? "ok  " : "BAD ", rc, g_msg.c_str());
