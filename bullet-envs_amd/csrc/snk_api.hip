@@ -512,6 +512,8 @@ int init_handle(snk_handle* h, const snk_params* p, int32_t n_envs, int32_t devi
                                                                                             //  components, streamed rows)
     // SNK_MOTORS_APART=1 (cross-checks): the motor rows never ride in the normals' batch (snk_pgs_v2.hpp: substep_v2)
     h->D.motors_apart = getenv("SNK_MOTORS_APART") != nullptr ? 1 : 0;
+    // SNK_SUPPORT_SERIAL=1 (cross-checks): the support vertex of a hull by the serial search (snk_contacts.hpp: hull_support)
+    h->D.support_serial = getenv("SNK_SUPPORT_SERIAL") != nullptr ? 1 : 0;
     size_t rf = 0, z0 = 0, zn = 0, m0 = 0, m1 = 0;      // the layout of a block of streamed constraint rows (below)
     int rc = dispatch(h, [&](auto k) {
         using LR = snk::Lds<decltype(k)::N, false>;

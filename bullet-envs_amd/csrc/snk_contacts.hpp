@@ -2,6 +2,7 @@
 // cylinder's world frame and friction directions, and Bullet's persistent manifold [U] (one cached point set per
 // cylinder: update, overflow rule, its block in global memory, its place in the compact contact list).
 #pragma once
+#include "snk_lds.hpp"
 #include "snk_model.hpp"
 #include "snk_wave.hpp"
 
@@ -9,19 +10,111 @@ namespace snk {
 
 constexpr int kMfFloats = 28;      // per cylinder: [count, 3 pad, 4 x (a3, b.x, b.y, lambda)]
 
+// The wave-uniform model fields the contact functions read, fetched ONCE per call by scalar loads.  Such a function is
+// called, not inlined: its model arrives as a generic reference in vector registers, and every read through it is a vector
+// load of a wave-uniform value with a full wait behind it.  The model lives in constant or global memory and no kernel
+// writes it, so its address -- made uniform -- may be read through the constant address space.  Only loads move: the
+// arithmetic on these values is what it was.  Per-lane tables (cyl_R[c], cyl_c[c]) stay vector loads through M.
+struct ContactK {
+    float break_thr, margin, cyl_r, cyl_hl, cyl_zoff, aniso[3], fricB, warm_factor;
+    int hull_sides, contact_model, self_collision, obstacle, warm_start, contact_order, support_serial;
+};
+typedef const DevModel __attribute__((address_space(4))) * ModelConstPtr;
+__device__ __forceinline__ ModelConstPtr model_const(const DevModel& M) {
+    const unsigned long long a = reinterpret_cast<unsigned long long>(&M);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return (ModelConstPtr)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ ContactK contact_k(const DevModel& M) {
+    const ModelConstPtr C = model_const(M);
+    ContactK K;
+    K.break_thr = C->break_thr; K.margin = C->margin; K.cyl_r = C->cyl_r; K.cyl_hl = C->cyl_hl; K.cyl_zoff = C->cyl_zoff;
+    K.aniso[0] = C->aniso[0]; K.aniso[1] = C->aniso[1]; K.aniso[2] = C->aniso[2];
+    K.fricB = C->fricB; K.warm_factor = C->warm_factor;
+    K.hull_sides = C->hull_sides; K.contact_model = C->contact_model; K.self_collision = C->self_collision;
+    K.obstacle = C->obstacle; K.warm_start = C->warm_start; K.contact_order = C->contact_order;
+    K.support_serial = C->support_serial;
+    return K;
+}
+
+// The hull's vertex table in the lanes of two registers: lane k holds hull_xy[(k >> 1) & 31], both floats, from ONE
+// coalesced load.  Call it with every lane of the wave active: hull_support reads lanes that sit out the search itself.
+struct HullLanes {
+    float x, y;
+};
+__device__ __forceinline__ HullLanes hull_lanes(const DevModel& M, int lane) {
+    typedef float hl_v2 __attribute__((ext_vector_type(2)));
+    typedef const hl_v2 __attribute__((address_space(4))) * TablePtr;
+    const hl_v2 v = ((TablePtr)&model_const(M)->hull_xy[0][0])[(lane >> 1) & 31];
+    HullLanes H = {v.x, v.y};
+    // The two registers are pinned HERE, where every lane is active.  Their only reader sits inside the callers'
+    // `if (lane < 2 N)`, and a load whose only use is in a later block may be sunk into it: executed by the lower lanes
+    // alone, it left vertices 16..31 of the 16-link streamed-row kernels unloaded (the first build of this function:
+    // 24 contacts for a snake lying flat on 32 cylinders).  The price is that the load's round trip is waited for here.
+    asm volatile("" : "+v"(H.x), "+v"(H.y));
+    return H;
+}
+__device__ __forceinline__ float lane_value(float v, int l) {       // v of lane l (wave-uniform l), whatever EXEC says
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+// Support vertex of the hull towards dl: the FIRST maximum of dot(dl, c) over the candidates in the importer's order,
+//   CAPS   c = (vertex s, +hl), (vertex s, -hl) for s = 0, 1, ...: the prism's 2 * sides vertices (manifold_core)
+//   !CAPS  c = vertex s: the polygon's (rim_point; z of the result is 0)
+// the value it replaces came from a loop with one load of hull_xy per candidate and a divergent block on a new best
+// (SNK_SUPPORT_SERIAL=1 keeps those loops: tests/test_gpu_support_vertex.py holds the two against each other, bit for
+// bit).  Here vertex s comes out of the lanes (v_readlane, uniform index), and everything else is a select.  What is
+// kept, so that the bits are: the order k ascending; the start value, the strict >, so the first maximum wins and a NaN
+// changes nothing (the comparison is false); and the arithmetic tree the compiler made of dot(dl, c) there --
+//   t = dl.x * vx;  t = fma(dl.y, vy, t);  val = fma(dl.z, +-hl, t)       (rim_point: val = fma(dl.y, vy, dl.x * vx))
+// read off the parent's ISA (v_mul, v_fma, v_fma, with dl's negations of Rw's third row folded into operand modifiers,
+// which is exact) and spelled out under contract(off).  The first two steps do not depend on the sign of hl: they are
+// computed once per vertex for its two candidates, the same operations on the same operands.
+template <bool CAPS>
+__device__ __forceinline__ f3 hull_support(const HullLanes& H, int sides, f3 dl, float hl) {
+#pragma clang fp contract(off)
+    float best = -3.0e38f;
+    f3 sv = mk3(0.f, 0.f, 0.f);
+    for (int s = 0; s < sides; s++) {
+        const float vx = lane_value(H.x, 2 * s), vy = lane_value(H.y, 2 * s);
+        const float t = __builtin_fmaf(dl.y, vy, dl.x * vx);
+        if (CAPS) {
+            const float vp = __builtin_fmaf(dl.z, hl, t);
+            const bool gp = vp > best;
+            best = gp ? vp : best;
+            const float vm = __builtin_fmaf(dl.z, -hl, t);
+            const bool gm = vm > best;
+            best = gm ? vm : best;
+            sv.x = (gp || gm) ? vx : sv.x;
+            sv.y = (gp || gm) ? vy : sv.y;
+            sv.z = gm ? -hl : (gp ? hl : sv.z);
+        } else {
+            const bool g = t > best;
+            best = g ? t : best;
+            sv.x = g ? vx : sv.x;
+            sv.y = g ? vy : sv.y;
+        }
+    }
+    return sv;
+}
+
 // lowest rim point (x, y in the cylinder's frame) towards dl = world "down" in that frame
-__device__ __forceinline__ void rim_point(const DevModel& M, f3 dl, float& lx, float& ly) {
+__device__ __forceinline__ void rim_point(const DevModel& M, const ContactK& K, const HullLanes& H, f3 dl, float& lx, float& ly) {
     lx = 0.f; ly = 0.f;
-    if (M.hull_sides > 0) {
-        float best = -3.0e38f;
-        for (int s = 0; s < M.hull_sides; s++) {          // first maximum, the importer's vertex order
-            const float vx = M.hull_xy[s][0], vy = M.hull_xy[s][1];
-            const float val = dl.x * vx + dl.y * vy;
-            if (val > best) { best = val; lx = vx; ly = vy; }
+    if (K.hull_sides > 0) {
+        if (K.support_serial) {
+            float best = -3.0e38f;
+            for (int s = 0; s < K.hull_sides; s++) {          // first maximum, the importer's vertex order
+                const float vx = M.hull_xy[s][0], vy = M.hull_xy[s][1];
+                const float val = dl.x * vx + dl.y * vy;
+                if (val > best) { best = val; lx = vx; ly = vy; }
+            }
+        } else {
+            const f3 sv = hull_support<false>(H, K.hull_sides, dl, 0.f);
+            lx = sv.x; ly = sv.y;
         }
     } else {
         const float rr = sqrtf(dl.x * dl.x + dl.y * dl.y);
-        if (rr > 1e-12f) { lx = M.cyl_r * dl.x / rr; ly = M.cyl_r * dl.y / rr; }
+        if (rr > 1e-12f) { lx = K.cyl_r * dl.x / rr; ly = K.cyl_r * dl.y / rr; }
     }
 }
 // world rotation of cylinder c's frame
@@ -33,7 +126,8 @@ __device__ __forceinline__ void cyl_world_rot(const float* Rb, const float* Rc, 
             Rw[3 * i + j] = Rb[3 * i] * Rc[j] + Rb[3 * i + 1] * Rc[3 + j] + Rb[3 * i + 2] * Rc[6 + j];
 }
 // friction directions (0,-1,0), (1,0,0) scaled anisotropically in the link's axes: d' = Rw diag(aniso) Rw^T d
-__device__ __forceinline__ void friction_dirs(const DevModel& M, const float* Rw, f3& dA, f3& dB) {
+template <class MK>      // (DevModel, or the contact functions' ContactK)
+__device__ __forceinline__ void friction_dirs(const MK& M, const float* Rw, f3& dA, f3& dB) {
     const f3 a = mk3(M.aniso[0], M.aniso[1], M.aniso[2]);
     const f3 l1 = mulRtv(Rw, mk3(0.f, -1.f, 0.f));
     const f3 l2 = mulRtv(Rw, mk3(1.f, 0.f, 0.f));
@@ -91,11 +185,15 @@ __device__ __forceinline__ int manifold_sort_cached(const MPt (&p)[4], const MPt
 // this step's support point (getCacheEntry / replaceContactPoint / addManifoldPoint with sortCachedPoints, which sees
 // the refreshed distances) [U].  Returns the new number of cached points; their world positions on the link and
 // distances in wa / p[].d.  Everything is a select (mpt_sel): the cache stays in registers.
-__device__ __forceinline__ int manifold_core(const DevModel& M, int n, MPt (&p)[4], const float* Rw, f3 centre, f3 dl,
-                                             f3 (&wa)[4]) {
+__device__ __forceinline__ int manifold_core(const DevModel& M, const ContactK& K, const HullLanes& H, int n, MPt (&p)[4],
+                                             const float* Rw, f3 centre, f3 dl, f3 (&wa)[4]
+#ifdef SNK_PROFILE_FINE
+                                             , unsigned long long* prof_f = nullptr
+#endif
+                                             ) {
     n = n < 0 ? 0 : (n > 4 ? 4 : n);
-    const float thr = M.break_thr;
-    const f3 zoff = mk3(0.f, 0.f, M.cyl_zoff);
+    const float thr = K.break_thr;
+    const f3 zoff = mk3(0.f, 0.f, K.cyl_zoff);
     // refresh from the current pose, then drop what lifted off or drifted (last to first, the last one moves in)
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -119,23 +217,29 @@ __device__ __forceinline__ int manifold_core(const DevModel& M, int n, MPt (&p)[
         f3_sel(wa[j], wl, drop && j != last);
         n = drop ? n - 1 : n;
     }
+    SNK_FSTAMP(10)
     // the new point: support vertex towards the plane (+ margin along that direction)
     f3 sv;
-    if (M.hull_sides > 0) {
-        float best = -3.0e38f;
-        sv = mk3(0.f, 0.f, 0.f);
-        for (int k = 0; k < 2 * M.hull_sides; k++) {      // the importer's order: (+z, -z) of vertex 0, 1, ...
-            const f3 c = mk3(M.hull_xy[k >> 1][0], M.hull_xy[k >> 1][1], (k & 1) ? -M.cyl_hl : M.cyl_hl);
-            const float val = dot(dl, c);
-            if (val > best) { best = val; sv = c; }
+    if (K.hull_sides > 0) {
+        if (K.support_serial) {
+            float best = -3.0e38f;
+            sv = mk3(0.f, 0.f, 0.f);
+            for (int k = 0; k < 2 * K.hull_sides; k++) {      // the importer's order: (+z, -z) of vertex 0, 1, ...
+                const f3 c = mk3(M.hull_xy[k >> 1][0], M.hull_xy[k >> 1][1], (k & 1) ? -K.cyl_hl : K.cyl_hl);
+                const float val = dot(dl, c);
+                if (val > best) { best = val; sv = c; }
+            }
+        } else {
+            sv = hull_support<true>(H, K.hull_sides, dl, K.cyl_hl);
         }
     } else {                                              // btCylinderShapeZ's support function [U]
         const float rr = sqrtf(dl.x * dl.x + dl.y * dl.y);
-        sv = rr != 0.f ? mk3(M.cyl_r * dl.x / rr, M.cyl_r * dl.y / rr, 0.f) : mk3(M.cyl_r, 0.f, 0.f);
-        sv.z = dl.z < 0.f ? -M.cyl_hl : M.cyl_hl;
+        sv = rr != 0.f ? mk3(K.cyl_r * dl.x / rr, K.cyl_r * dl.y / rr, 0.f) : mk3(K.cyl_r, 0.f, 0.f);
+        sv.z = dl.z < 0.f ? -K.cyl_hl : K.cyl_hl;
     }
+    SNK_FSTAMP(11)
     MPt np;
-    const f3 loc = sv + dl * M.margin;                    // in the cylinder's own (centred) frame
+    const f3 loc = sv + dl * K.margin;                    // in the cylinder's own (centred) frame
     np.a = loc + zoff;
     const f3 wnew = centre + mulRv(Rw, loc);
     np.d = wnew.z;
@@ -162,6 +266,7 @@ __device__ __forceinline__ int manifold_core(const DevModel& M, int n, MPt (&p)[
 #pragma unroll
         for (int j = 0; j < 4; j++) { mpt_sel(p[j], np, add && j == where); f3_sel(wa[j], wnew, add && j == where); }
     }
+    SNK_FSTAMP(12)
     return n;
 }
 
@@ -294,8 +399,8 @@ __device__ __forceinline__ int lane_prefix3(int cnt, int lane, int& total) {
 // Otherwise position r fetches the count of the cylinder that sits there (DevModel::cyl_at), the prefix runs over
 // positions, and every cylinder fetches its own from its position (cyl_rank): two ds_bpermute per substep.
 // (wave-uniform branch: the model sits in constant memory)
-__device__ __forceinline__ int manifold_base(const DevModel& M, int ncyl, int kept, int lane, int& total) {
-    if (M.contact_order == 0) return lane_prefix3(kept, lane, total);
+__device__ __forceinline__ int manifold_base(const DevModel& M, const ContactK& K, int ncyl, int kept, int lane, int& total) {
+    if (K.contact_order == 0) return lane_prefix3(kept, lane, total);
     const int at = lane < ncyl ? (int)M.cyl_at[lane] : lane;
     const int rk = lane < ncyl ? (int)M.cyl_rank[lane] : lane;
     const int kept_r = __shfl(kept, at);

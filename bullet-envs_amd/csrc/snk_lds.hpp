@@ -15,8 +15,9 @@
 #endif
 // -DSNK_PROFILE -DSNK_PROFILE_FINE (build.py --profile-fine): a second set of stamps around the dynamics' own pieces --
 // integrate, fk_vel, body_bias, the inward sweep, the base inverse, the outward sweep -- whose durations take the coarse
-// phases' place in the record (tools/profile_phases.py fine).  A function that is also called without the table takes
-// it as a pointer that may be null.
+// phases' place in the record (tools/profile_phases.py fine), and behind them the pieces of find_contacts_v2 (obstacle and
+// self-pair tests; manifold load, refresh, drop; the support search; nearest / sort / insert; prefix and stores).  A
+// function that is also called without the table takes it as a pointer that may be null.
 #if defined(SNK_PROFILE) && defined(SNK_PROFILE_FINE)
 #define SNK_FSTAMP(i) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); if (prof_f) prof_f[i] = t_; }
 #else

@@ -85,6 +85,7 @@ struct DevModel {
     // offset max_b |pfix[b]|, reach_hb = |hbase|, each rounded up by 1.001 (snk_debug_reach_bound reads them back)
     float reach_l, reach_hb;
     int motors_apart;                    // SNK_MOTORS_APART=1 at snk_create: the motor rows always get a batch of their own (snk_pgs_v2.hpp)
+    int support_serial;                  // SNK_SUPPORT_SERIAL=1 at snk_create: the hull's support vertex by one load per candidate (snk_contacts.hpp)
 };
 // the fixed part of that bound [m]: ten times the float32 round-off of the forward kinematics of a 1.1 m chain
 // (17 x 6e-8 x 1.1 m), which is what separates the computed mean height from the rigid motion the bound is about

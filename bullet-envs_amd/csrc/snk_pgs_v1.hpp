@@ -22,6 +22,8 @@ __device__ int find_contacts_manifold_v1(LT& L, const DevModel& M, int lane, flo
                                          unsigned long long* __restrict__ ovf) {
     constexpr int N = LT::kN;
     static_assert(2 * N <= 64, "one cylinder per lane");
+    const ContactK K = contact_k(M);                 // (scalar loads; the vertex table into the lanes: every lane is active)
+    const HullLanes H = hull_lanes(M, lane);
     int cnt = 0;
     MPt p[4];
     f3 wa[4];
@@ -34,7 +36,7 @@ __device__ int find_contacts_manifold_v1(LT& L, const DevModel& M, int lane, flo
         const f3 dl = mk3(-Rw[6], -Rw[7], -Rw[8]);
         const f3 centre = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[c]));
         const int n0 = manifold_load_global(mf + (size_t)c * kMfFloats, p);
-        cnt = manifold_core(M, n0, p, Rw, centre, dl, wa);
+        cnt = manifold_core(M, K, H, n0, p, Rw, centre, dl, wa);
     }
     int total;
     (void)lane_prefix3(cnt, lane, total);
@@ -42,7 +44,7 @@ __device__ int find_contacts_manifold_v1(LT& L, const DevModel& M, int lane, flo
     const int mask = manifold_keep_mask(cnt, p, lane, total, room);
     const int kept = __popc(mask);
     int tk;
-    const int base = manifold_base(M, 2 * N, kept, lane, tk);
+    const int base = manifold_base(M, K, 2 * N, kept, lane, tk);
     if (total > room && lane == 0) {
         atomicAdd(ovf, 1ull);
         atomicAdd(ovf + 1, (unsigned long long)(total - tk));
@@ -54,7 +56,7 @@ __device__ int find_contacts_manifold_v1(LT& L, const DevModel& M, int lane, flo
         L.cidx[2 * lane] = base;
         L.cidx[2 * lane + 1] = kept | (mask << 8);
         f3 dA, dB;
-        friction_dirs(M, Rw, dA, dB);
+        friction_dirs(K, Rw, dA, dB);
         int idx = base;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -69,7 +71,7 @@ __device__ int find_contacts_manifold_v1(LT& L, const DevModel& M, int lane, flo
                 st3(geo + 10, mk3(0.f, 0.f, 1.f));
                 st3(geo + 13, mk3(0.f, 0.f, 0.f));
                 geo[16] = (float)b; geo[17] = -1.0f; geo[18] = 1.0f;
-                geo[19] = M.warm_start ? p[j].lam * M.warm_factor : 0.f;
+                geo[19] = K.warm_start ? p[j].lam * K.warm_factor : 0.f;
                 L.clist[idx] = idx;
                 idx++;
             }
@@ -89,7 +91,9 @@ template <class LT>
 __device__ int find_contacts_v1(LT& L, const DevModel& M, int lane, float* __restrict__ rows, float* __restrict__ mf,
                                 unsigned long long* __restrict__ ovf) {
     constexpr int N = LT::kN;
-    if (M.contact_model == 1) return find_contacts_manifold_v1(L, M, lane, rows, mf, ovf);
+    const ContactK K = contact_k(M);
+    if (K.contact_model == 1) return find_contacts_manifold_v1(L, M, lane, rows, mf, ovf);
+    const HullLanes H = hull_lanes(M, lane);
     int total = 0;
     for (int base = 0; base < 4 * N; base += 64) {
         const int slot = base + lane;
@@ -107,20 +111,20 @@ __device__ int find_contacts_v1(LT& L, const DevModel& M, int lane, float* __res
                     Rw[3 * i + j] = Rb[3 * i] * Rc[j] + Rb[3 * i + 1] * Rc[3 + j] + Rb[3 * i + 2] * Rc[6 + j];
             f3 dl = mk3(-Rw[6], -Rw[7], -Rw[8]);
             float lx, ly;
-            rim_point(M, dl, lx, ly);
-            float lz = (slot & 1) ? M.cyl_hl : -M.cyl_hl;
-            f3 loc = mk3(lx + M.margin * dl.x, ly + M.margin * dl.y, lz + M.margin * dl.z);
+            rim_point(M, K, H, dl, lx, ly);
+            float lz = (slot & 1) ? K.cyl_hl : -K.cyl_hl;
+            f3 loc = mk3(lx + K.margin * dl.x, ly + K.margin * dl.y, lz + K.margin * dl.z);
             f3 P = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[c])) + mulRv(Rw, loc);
             float dist = P.z;
-            active = dist < M.break_thr;
+            active = dist < K.break_thr;
             float* geo = rows + LT::kGeoOff + (size_t)slot * LT::kGeo;
             st3(geo, P);
             geo[3] = dist;
-            f3 a = mk3(M.aniso[0], M.aniso[1], M.aniso[2]);
+            f3 a = mk3(K.aniso[0], K.aniso[1], K.aniso[2]);
             f3 l1 = mulRtv(Rw, mk3(0.f, -1.f, 0.f));
             f3 l2 = mulRtv(Rw, mk3(1.f, 0.f, 0.f));
             st3(geo + 4, mulRv(Rw, mk3(l1.x * a.x, l1.y * a.y, l1.z * a.z)));
-            st3(geo + 7, mulRv(Rw, mk3(l2.x * a.x, l2.y * a.y, l2.z * a.z)) * M.fricB);
+            st3(geo + 7, mulRv(Rw, mk3(l2.x * a.x, l2.y * a.y, l2.z * a.z)) * K.fricB);
             st3(geo + 10, mk3(0.f, 0.f, 1.f));
             st3(geo + 13, mk3(0.f, 0.f, 0.f));
             geo[16] = (float)b; geo[17] = -1.0f; geo[18] = 1.0f; geo[19] = 0.f;

@@ -92,13 +92,13 @@ struct ObsHit {
     float dist;
 };
 template <class LT>
-__device__ __forceinline__ int find_obstacle_v2(LT& L, const DevModel& M, int lane, ObsHit& h,
+__device__ __forceinline__ int find_obstacle_v2(LT& L, const DevModel& M, const ContactK& K, int lane, ObsHit& h,
                                                 unsigned long long* __restrict__ ovf) {
     constexpr int N = LT::kN;
     h.hit = false;
     h.P = mk3(0, 0, 0); h.n = mk3(0, 0, 1); h.dA = mk3(0, 0, 0); h.dB = mk3(0, 0, 0);
     h.dist = 0.f;
-    if (!M.obstacle) return 0;
+    if (!K.obstacle) return 0;
     const float rb = sqrtf(M.cyl_r * M.cyl_r + M.cyl_hl * M.cyl_hl) + M.margin;
     Cvx Bx;
     Bx.c = mk3(M.obs_c[0], M.obs_c[1], M.obs_c[2]);
@@ -170,18 +170,29 @@ __device__ __forceinline__ void append_obstacle_v2(LT& L, int lane, const ObsHit
 }
 
 template <class LT>
-__device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned long long* __restrict__ ovf) {
+__device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned long long* __restrict__ ovf
+#ifdef SNK_PROFILE_FINE
+                                , unsigned long long* prof_f = nullptr
+#endif
+                                ) {
     constexpr int N = LT::kN;
     static_assert(4 * N == 64, "one contact slot per lane");
+    SNK_FSTAMP(8)
+    const ContactK K = contact_k(M);      // the model's wave-uniform fields, by scalar loads
     // link-link contacts have two-body rows, which only the streamed-row solve builds: a substep in which a pair of links
     // may be within the breaking threshold goes there (never under the reference's command range: snk_selfcol.hpp)
-    if (M.self_collision && any_self_pair_v2(L, M, lane)) {
+    if (K.self_collision && any_self_pair_v2(L, M, K, lane)) {
         if (lane == 0) atomicAdd(ovf, 1ull);
         return -1;
     }
     ObsHit oh;
-    const int n_ob = find_obstacle_v2(L, M, lane, oh, ovf);      // 0 without an obstacle
-    if (M.contact_model == 1) {
+    const int n_ob = find_obstacle_v2(L, M, K, lane, oh, ovf);      // 0 without an obstacle
+    // The hull's vertex table into the lanes, for the support search (every lane is active here; hull_lanes waits for the
+    // load).  Behind the obstacle's narrow phase, not in front: across that call the two registers would be callee-saved
+    // ones, which this function would have to spill and reload (16 more scratch bytes per lane of the whole kernel).
+    const HullLanes H = hull_lanes(M, lane);
+    SNK_FSTAMP(9)
+    if (K.contact_model == 1) {
         // lane = cylinder; its manifold lives in LDS while this wave holds the environment (Lds<N, true>::mfl)
         int cnt = 0;
         MPt p[4];
@@ -201,7 +212,11 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
             cyl_world_rot(Rb, M.cyl_R[c], Rw);
             const f3 dl = mk3(-Rw[6], -Rw[7], -Rw[8]);
             const f3 centre = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[c]));
-            cnt = manifold_core(M, (int)L.mfn[c], p, Rw, centre, dl, wa);
+#ifdef SNK_PROFILE_FINE
+            cnt = manifold_core(M, K, H, (int)L.mfn[c], p, Rw, centre, dl, wa, prof_f);
+#else
+            cnt = manifold_core(M, K, H, (int)L.mfn[c], p, Rw, centre, dl, wa);
+#endif
         }
         int total;
         (void)lane_prefix3(cnt, lane, total);
@@ -217,14 +232,14 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
         const int mask = (1 << cnt) - 1;
         const int kept = cnt;
         int tk;
-        const int base = manifold_base(M, 2 * N, kept, lane, tk);
+        const int base = manifold_base(M, K, 2 * N, kept, lane, tk);
         if (lane < 2 * N) {
             L.cylbase[c] = (unsigned char)base;
             L.cyln[c] = (unsigned char)kept;
             L.cylkeep[c] = (unsigned char)mask;
             L.mfn[c] = (unsigned char)cnt;
             f3 dA, dB;
-            friction_dirs(M, Rw, dA, dB);
+            friction_dirs(K, Rw, dA, dB);
             st3(L.cdir[c][0], dA);
             st3(L.cdir[c][1], dB);
             int idx = base;
@@ -242,13 +257,14 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
                     L.ccbody[idx] = (unsigned char)b;
                     L.ccds[idx] = (unsigned char)c;
                     // where the normal row starts (warm starting); the solve leaves the row's final impulse here
-                    L.app[kAppNormal + idx] = M.warm_start ? p[j].lam * M.warm_factor : 0.f;
+                    L.app[kAppNormal + idx] = K.warm_start ? p[j].lam * K.warm_factor : 0.f;
                     idx++;
                 }
             }
         }
         if (lane == 0) L.nplane = tk;
         if (n_ob) append_obstacle_v2(L, lane, oh, tk);
+        SNK_FSTAMP(13)
         return tk + n_ob;
     }
     const int slot = lane;
@@ -259,12 +275,12 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
     cyl_world_rot(Rb, M.cyl_R[c], Rw);
     f3 dl = mk3(-Rw[6], -Rw[7], -Rw[8]);
     float lx, ly;
-    rim_point(M, dl, lx, ly);
-    float lz = (slot & 1) ? M.cyl_hl : -M.cyl_hl;
-    f3 loc = mk3(lx + M.margin * dl.x, ly + M.margin * dl.y, lz + M.margin * dl.z);
+    rim_point(M, K, H, dl, lx, ly);
+    float lz = (slot & 1) ? K.cyl_hl : -K.cyl_hl;
+    f3 loc = mk3(lx + K.margin * dl.x, ly + K.margin * dl.y, lz + K.margin * dl.z);
     f3 P = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[c])) + mulRv(Rw, loc);
     const float dist = P.z;
-    bool active = dist < M.break_thr;
+    bool active = dist < K.break_thr;
     unsigned long long bal = __ballot(active);
     const int room = 4 * N - n_ob;                   // the solve's contact slots, less the box's contacts
     if (__popcll(bal) > room || n_ob > LT::kObs) {   // (only with an obstacle: two points per cylinder are 4 N at most)
@@ -284,7 +300,7 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
         float Rc[9];
         cyl_world_rot(L.R[(lane + 1) >> 1], M.cyl_R[lane], Rc);
         f3 dA, dB;
-        friction_dirs(M, Rc, dA, dB);
+        friction_dirs(K, Rc, dA, dB);
         st3(L.cdir[lane][0], dA);
         st3(L.cdir[lane][1], dB);
     }
@@ -1100,12 +1116,16 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     unsigned long long prof_t[17];
 #endif
 #ifdef SNK_PROFILE_FINE
-    unsigned long long prof_fine[8];
+    unsigned long long prof_fine[14] = {};
     unsigned long long* const prof_f = prof_fine;
 #endif
     SNK_STAMP(0)
     // (1) contacts of the current pose, (2) bias forces with gravity, joint damping torque
+#ifdef SNK_PROFILE_FINE
+    const int nc = __builtin_amdgcn_readfirstlane(find_contacts_v2(L, M, lane, ovf, prof_f));
+#else
     const int nc = __builtin_amdgcn_readfirstlane(find_contacts_v2(L, M, lane, ovf));
+#endif
     ncontacts = nc;
     if (nc < 0) return;            // does not fit this solve: nothing has been touched (substep() takes the other one)
     SNK_STAMP(1)
@@ -1529,8 +1549,11 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     SNK_FSTAMP(7)
     lds_sync();
 #ifdef SNK_PROFILE_FINE
-    // slots 0..6: body_bias, inward sweep, base inverse, outward sweep, (everything between), integrate, fk_vel
-    if (lane < 16) L.taum()[lane] = lane < 7 ? (float)(prof_fine[lane + 1] - prof_fine[lane]) : 0.f;
+    // slots 0..6: body_bias, inward sweep, base inverse, outward sweep, (everything between), integrate, fk_vel;
+    // slots 7..11: the pieces of find_contacts_v2 (stamps 8..13: obstacle and self-pair tests; manifold load, refresh and
+    // drop; the support search; nearest / sort / insert; prefix and stores)
+    if (lane < 16) L.taum()[lane] = lane < 7 ? (float)(prof_fine[lane + 1] - prof_fine[lane])
+                                   : (lane < 12 ? (float)(prof_fine[lane + 2] - prof_fine[lane + 1]) : 0.f);
 #else
     if (lane < 16) L.taum()[lane] = (float)(prof_t[lane + 1] - prof_t[lane]);
 #endif

@@ -236,13 +236,15 @@ __device__ __forceinline__ f3 aniso_scale(const DevModel& M, const float* Rw, f3
 // the contact set is the oracle's, which has no such cull.  A 32-gon hull lies inside its cylinder.  (Under the relative
 // breaking threshold, 1.2 mm, the neighbours across one joint -- 15 to 29 mm apart -- never pass; their bounding spheres
 // always overlap, and 62 of them went through the GJK every substep: 12 % of the 32-link kernel.)
-__device__ __forceinline__ float cyl_extent(const DevModel& M, f3 axis, f3 u) {      // |u| = 1
+template <class MK>      // (MK: DevModel, or the contact functions' ContactK -- snk_contacts.hpp)
+__device__ __forceinline__ float cyl_extent(const MK& M, f3 axis, f3 u) {      // |u| = 1
     const float c = dot(axis, u);
     return M.cyl_hl * fabsf(c) + M.cyl_r * sqrtf(fmaxf(0.f, 1.0f - c * c));
 }
 // (the forms that take the threshold serve the closest-point query, snk_world.hpp, at its caller's distance; the solver's
 //  forms are those at the handle's breaking threshold)
-__device__ __forceinline__ bool cyl_cyl_may_touch(const DevModel& M, f3 ca, f3 axa, f3 cb, f3 axb, float thr) {
+template <class MK>
+__device__ __forceinline__ bool cyl_cyl_may_touch(const MK& M, f3 ca, f3 axa, f3 cb, f3 axb, float thr) {
     const f3 d = ca - cb;
     const float n2 = dot(d, d);
     if (!(n2 > 1e-12f)) return true;
@@ -251,7 +253,8 @@ __device__ __forceinline__ bool cyl_cyl_may_touch(const DevModel& M, f3 ca, f3 a
     const float bound = n - cyl_extent(M, axa, u) - cyl_extent(M, axb, u);
     return bound - 2.0f * M.margin <= thr + 1e-5f;
 }
-__device__ __forceinline__ bool cyl_cyl_may_touch(const DevModel& M, f3 ca, f3 axa, f3 cb, f3 axb) {
+template <class MK>
+__device__ __forceinline__ bool cyl_cyl_may_touch(const MK& M, f3 ca, f3 axa, f3 cb, f3 axb) {
     return cyl_cyl_may_touch(M, ca, axa, cb, axb, M.break_thr);
 }
 // cylinder against the box (centre bc, rotation Rb row-major, half extents hb): the three face normals of the box
@@ -276,11 +279,11 @@ __device__ __forceinline__ bool cyl_box_may_touch(const DevModel& M, f3 ca, f3 a
 // traffic and one ballot at the end (the first version walked the offsets with three ds_bpermutes and a ballot each:
 // 1.1 % of the kernel in dependent latency).
 template <class LT>
-__device__ __forceinline__ bool any_self_pair_v2(LT& L, const DevModel& M, int lane) {
+__device__ __forceinline__ bool any_self_pair_v2(LT& L, const DevModel& M, const ContactK& K, int lane) {
     constexpr int NCYL = 2 * LT::kN;
     static_assert(NCYL == 32, "one cylinder per lane of a half");
-    const float rb = sqrtf(M.cyl_r * M.cyl_r + M.cyl_hl * M.cyl_hl) + M.margin;
-    const float reach = 2.0f * rb + M.break_thr;
+    const float rb = sqrtf(K.cyl_r * K.cyl_r + K.cyl_hl * K.cyl_hl) + K.margin;
+    const float reach = 2.0f * rb + K.break_thr;
     const int a = lane & 31, h = lane >> 5;
     const int ba = (a + 1) >> 1;
     const f3 ca = ld3(L.o[ba]) + mulRv(L.R[ba], ld3(M.cyl_c[a]));
@@ -299,7 +302,7 @@ __device__ __forceinline__ bool any_self_pair_v2(LT& L, const DevModel& M, int l
         const f3 cb = ld3(&L.stM[bb][0]);
         const f3 d = ca - cb;
         bool cand = valid && dot(d, d) <= reach * reach;
-        if (cand) cand = cyl_cyl_may_touch(M, ca, axa, cb, ld3(&L.stM[bb][3]));
+        if (cand) cand = cyl_cyl_may_touch(K, ca, axa, cb, ld3(&L.stM[bb][3]));
         hit = hit || cand;
     }
     const bool any = __any(hit) != 0;

@@ -183,7 +183,9 @@ int snk_reset(snk_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stre
  * every later call on the handle return non-zero ("env-step scheduler: ...").  Environment:
  * SNK_QUANTUM=<substeps per slice> (default 1; 0 = the unscheduled kernel), SNK_FORCE_STREAMED=1 (16 links on the
  * streamed-row kernels of the 32-link chain: diagnostics and cross-checks), SNK_MOTORS_APART=1 (the register-resident
- * substep builds its motor rows in a batch of their own at every contact count: cross-checks), all read by snk_create. */
+ * substep builds its motor rows in a batch of their own at every contact count: cross-checks), SNK_SUPPORT_SERIAL=1 (the
+ * contact functions find a hull's support vertex with one load per candidate instead of in the lanes' copy of the vertex
+ * table: cross-checks), all read by snk_create. */
 int snk_step(snk_handle* h, float* actions_dev, float* obs_dev, float* rew_dev,
              uint8_t* done_dev, int32_t* substeps_dev, int32_t vec_mode, void* stream);
 

@@ -18,6 +18,9 @@ names = ["contacts", "bias + ABA (factor, solve)", "sensor pass 1, v += a dt", "
 NL = int(sys.argv[1]) if len(sys.argv) > 1 and not FINE else 16
 if FINE:     # the stamps are not contiguous: slot 4 is everything between the outward sweep and the integration
     names = ["body_bias", "ABA inward sweep", "ABA base inverse", "ABA outward sweep", None, "integrate", "fk_vel"]
+    # slots 7..11: the pieces of find_contacts_v2 (printed as a table of their own: they come BEFORE body_bias)
+    CONTACTS = ["contacts: obstacle and self-pair tests", "contacts: manifold load, refresh, drop",
+                "contacts: support search", "contacts: nearest / sort / insert", "contacts: prefix and stores"]
 if NL == 32:
     names = ["ground contacts", "link-link contacts (GJK)", "bias + ABA (factor, solve)", "sensor pass 1, v += a dt",
              "rows: M^-1 columns (38 delta sweeps) + assembly, lane = dof", "PGS, 50 iterations", "sensor pass 2", "integrate", "FK of the new pose"]
@@ -34,4 +37,9 @@ for B in (1024, 2048):
     print("B=%d (%d wave(s)/SIMD): ticks per phase, mean over envs; total %.0f" % (B, B // 1024, m.sum()))
     for n_, v in zip([n_ for n_ in names if n_], m):
         print("   %-36s %9.0f  %5.1f %%" % (n_, v, 100 * v / m.sum()))
+    if FINE:
+        c = aux[:, len(names):len(names) + len(CONTACTS)].astype(np.float64).mean(axis=0)
+        print("   the contact phase's pieces (find_contacts_v2), total %.0f" % c.sum())
+        for n_, v in zip(CONTACTS, c):
+            print("   %-40s %9.0f  %5.1f %%" % (n_, v, 100 * v / c.sum()))
     st.close()
