@@ -3,6 +3,7 @@
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels to the GPU box
 with the gpurun snapshot.
 """
+import collections
 import os
 import subprocess
 import sys
@@ -12,10 +13,25 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsnk.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "snk.h")
 
-
-RENDER_OBJ = os.path.join(HERE, "snk_render.o")
-WORLD_OBJ = os.path.join(HERE, "snk_world.o")
-DYN_OBJ = os.path.join(HERE, "snk_dyn.o")
+# The library's translation units, one row each, in the order they are built and stamped: the source under csrc/, how it is
+# built, the suffix of its stamp (the command of its last build, kept next to the library) and its object.  A unit with an
+# object is a code object of its own, compiled apart and linked in by the unit without one: the library's own command.
+#   api     the step kernels and the C ABI.  libsnk.so.cmd stays the command of this unit alone, flags and source (the
+#           pinned bits of tests/test_gpu_bits.py are keyed by it and by the toolchain): the objects it links are not in it
+#   render  the renderer and the ray test
+#   world   the link states, the reported contacts, the closest points and the env fork
+#   dyn     the dynamics queries: mass matrix, bias forces, link Jacobians
+Unit = collections.namedtuple("Unit", "name source mode stamp obj")
+UNITS = (
+    Unit("api", "csrc/snk_api.hip", "-shared", ".cmd", None),
+    Unit("render", "csrc/snk_render.hip", "-c", ".render.cmd", "snk_render.o"),
+    Unit("world", "csrc/snk_world.hip", "-c", ".world.cmd", "snk_world.o"),
+    Unit("dyn", "csrc/snk_dyn.hip", "-c", ".dyn.cmd", "snk_dyn.o"),
+)
+# What the tools and the tests take from the table: the sources (tools/same_isa.py, tools/kernel_resources.py) and the
+# files that describe a build of the default library (tests/bit_pins.py keys the pinned bits by prefixes of this list)
+SOURCES = tuple(u.source for u in UNITS)
+STAMPS = (os.path.basename(LIB) + ".toolchain",) + tuple(os.path.basename(LIB) + u.stamp for u in UNITS)
 
 
 def sources():
@@ -39,48 +55,16 @@ def _hipcc():
     return hipcc if os.path.exists(hipcc) else "hipcc"
 
 
-def _command(out, defines=(), extra=()):
-    return [_hipcc()] + FLAGS + ["-shared", "-fPIC", os.path.join(CSRC, "snk_api.hip"), "-o", out] + \
+def _object(unit, target):
+    """snk_<unit>.o for the default library, <stem>_<unit>.o next to a variant"""
+    return os.path.join(HERE, unit.obj) if target == LIB else os.path.splitext(target)[0] + unit.obj[len("snk"):]
+
+
+def _command(unit, target=LIB, defines=(), extra=()):
+    """The command that builds `unit` for the library `target`: its object, or (the unit without one) the library."""
+    out = _object(unit, target) if unit.obj else target
+    return [_hipcc()] + FLAGS + [unit.mode, "-fPIC", os.path.join(HERE, unit.source), "-o", out] + \
         ["-D" + d for d in defines] + list(extra)
-
-
-def _render_command(obj, defines=(), extra=()):
-    """The renderer's translation unit (csrc/snk_render.hip), compiled to an object of its own -- its kernels are a code
-    object apart from the step kernels' -- which the library's command then links in."""
-    return [_hipcc()] + FLAGS + ["-c", "-fPIC", os.path.join(CSRC, "snk_render.hip"), "-o", obj] + \
-        ["-D" + d for d in defines] + list(extra)
-
-
-def _world_command(obj, defines=(), extra=()):
-    """The translation unit of the link states, the reported contacts, the closest points and the env fork
-    (csrc/snk_world.hip): an object of its own, like the renderer's, linked in by the library's command."""
-    return [_hipcc()] + FLAGS + ["-c", "-fPIC", os.path.join(CSRC, "snk_world.hip"), "-o", obj] + \
-        ["-D" + d for d in defines] + list(extra)
-
-
-def _dyn_command(obj, defines=(), extra=()):
-    """The translation unit of the dynamics queries (csrc/snk_dyn.hip: mass matrix, bias forces, link Jacobians): an object
-    of its own, like the renderer's and the world's, linked in by the library's command."""
-    return [_hipcc()] + FLAGS + ["-c", "-fPIC", os.path.join(CSRC, "snk_dyn.hip"), "-o", obj] + \
-        ["-D" + d for d in defines] + list(extra)
-
-
-def _stamp(out):
-    return out + ".cmd"
-
-
-def _render_stamp(out):
-    """libsnk.so.cmd stays the command of the step kernels' translation unit alone, flags and source (the pinned bits of
-    tests/test_gpu_bits.py are keyed by it and by the toolchain); the renderer's object has a stamp of its own."""
-    return out + ".render.cmd"
-
-
-def _world_stamp(out):
-    return out + ".world.cmd"
-
-
-def _dyn_stamp(out):
-    return out + ".dyn.cmd"
 
 
 def toolchain_text():
@@ -100,29 +84,37 @@ def _stamp_text(cmd):
     return " ".join(os.path.relpath(a, HERE) if os.path.isabs(a) and a.startswith(os.path.dirname(HERE)) else a for a in cmd)
 
 
-def needs_build(cmd=None):
-    """Stale when a source is newer than the library -- or when the library was built by ANOTHER command line (other
-    flags or -D defines: mtimes cannot see that, and a libsnk.so from an experiment would travel to the GPU box as the
-    product).  The command of the last build is kept next to the library (libsnk.so.cmd, git-ignored with it)."""
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
+def stamp_texts(target=LIB, defines=(), extra=()):
+    """[(file, text)] of everything a build of `target` leaves next to it, in STAMPS' order: the toolchain, then each
+    unit's command.  What build() writes, what an up-to-date library must hold, and what tests/test_bit_pin_keys.py
+    computes the pins' keys from without a compile."""
+    return [(target + ".toolchain", toolchain_text())] + \
+        [(target + u.stamp, _stamp_text(_command(u, target, defines, extra))) for u in UNITS]
+
+
+def _up_to_date(target, defines=()):
+    """The library is there, no source is newer than it, and it was built by THESE command lines (other flags or -D
+    defines: mtimes cannot see that)."""
+    if not os.path.exists(target):
+        return False
+    t = os.path.getmtime(target)
     if any(os.path.getmtime(d) > t for d in sources() + [HEADER, os.path.abspath(__file__)]):
-        return True
+        return False
     try:
-        with open(_stamp(LIB)) as f:
-            if f.read() != _stamp_text(cmd if cmd is not None else _command(LIB)):
-                return True
-        with open(_render_stamp(LIB)) as f:
-            if f.read() != _stamp_text(_render_command(RENDER_OBJ)):
-                return True
-        with open(_world_stamp(LIB)) as f:
-            if f.read() != _stamp_text(_world_command(WORLD_OBJ)):
-                return True
-        with open(_dyn_stamp(LIB)) as f:
-            return f.read() != _stamp_text(_dyn_command(DYN_OBJ))
+        for u in UNITS:
+            with open(target + u.stamp) as f:
+                if f.read() != _stamp_text(_command(u, target, defines)):
+                    return False
     except OSError:
-        return True
+        return False
+    return True
+
+
+def needs_build():
+    """Stale when a source is newer than the library -- or when the library was built by ANOTHER command line (a
+    libsnk.so from an experiment would travel to the GPU box as the product).  The command of each unit's last build is
+    kept next to the library (libsnk.so.cmd and the other stamps, git-ignored with it)."""
+    return not _up_to_date(LIB)
 
 
 def build(force=False, verbose=False, defines=(), out=None):
@@ -134,34 +126,22 @@ def build(force=False, verbose=False, defines=(), out=None):
         raise RuntimeError("bullet-envs_amd/build.py: -D defines / SNK_EXTRA_FLAGS need an output of their own (out=...): "
                            "libsnk.so is the product and is built with the default flags only")
     target = out or LIB
-    cmd = _command(target, defines, extra)
-    if out is None and not force and not needs_build(cmd):
+    if out is None and not force and not needs_build():
         if not os.path.exists(LIB + ".toolchain"):          # (a library from before round 6: same image, same compiler)
             with open(LIB + ".toolchain", "w") as f:
                 f.write(toolchain_text())
         return LIB
-    obj = RENDER_OBJ if out is None else os.path.splitext(target)[0] + "_render.o"
-    wobj = WORLD_OBJ if out is None else os.path.splitext(target)[0] + "_world.o"
-    dobj = DYN_OBJ if out is None else os.path.splitext(target)[0] + "_dyn.o"
-    rcmd = _render_command(obj, defines, extra)
-    wcmd = _world_command(wobj, defines, extra)
-    dcmd = _dyn_command(dobj, defines, extra)
-    run = [cmd[0], obj, wobj, dobj] + list(cmd[1:])      # (the objects first: hipcc reads every input behind a .hip file as HIP source)
-    for r in (rcmd, wcmd, dcmd, run):
+    (link,) = [_command(u, target, defines, extra) for u in UNITS if not u.obj]
+    objs = [_object(u, target) for u in UNITS if u.obj]
+    # (the objects first: hipcc reads every input behind a .hip file as HIP source)
+    for r in [_command(u, target, defines, extra) for u in UNITS if u.obj] + [[link[0]] + objs + link[1:]]:
         if verbose:
             r = [r[0], "-Rpass-analysis=kernel-resource-usage"] + r[1:]
             print(" ".join(r))
         subprocess.check_call(r)
-    with open(_stamp(target), "w") as f:
-        f.write(_stamp_text(cmd))
-    with open(_render_stamp(target), "w") as f:
-        f.write(_stamp_text(rcmd))
-    with open(_world_stamp(target), "w") as f:
-        f.write(_stamp_text(wcmd))
-    with open(_dyn_stamp(target), "w") as f:
-        f.write(_stamp_text(dcmd))
-    with open(target + ".toolchain", "w") as f:
-        f.write(toolchain_text())
+    for path, text in stamp_texts(target, defines, extra):
+        with open(path, "w") as f:
+            f.write(text)
     return target
 
 
@@ -173,16 +153,8 @@ def build_scalar(force=False):
     refresh (csrc/snk_dynamics.hpp) that the shipped kernels' lane form is compared with, byte for byte
     (tests/test_gpu_lane_dynamics.py), and timed against.  Unlike the other variants it belongs to the test suite, so it
     is rebuilt only when stale: a source newer than it, or another command line."""
-    cmd = _command(SCALAR_LIB, ("SNK_SCALAR_DYNAMICS",))
-    if not force and os.path.exists(SCALAR_LIB):
-        t = os.path.getmtime(SCALAR_LIB)
-        try:
-            with open(_stamp(SCALAR_LIB)) as f:
-                same = f.read() == _stamp_text(cmd)
-        except OSError:
-            same = False
-        if same and not any(os.path.getmtime(d) > t for d in sources() + [HEADER, os.path.abspath(__file__)]):
-            return SCALAR_LIB
+    if not force and _up_to_date(SCALAR_LIB, ("SNK_SCALAR_DYNAMICS",)):
+        return SCALAR_LIB
     return build(force=True, defines=("SNK_SCALAR_DYNAMICS",), out=SCALAR_LIB)
 
 

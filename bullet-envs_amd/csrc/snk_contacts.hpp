@@ -186,11 +186,7 @@ __device__ __forceinline__ int manifold_sort_cached(const MPt (&p)[4], const MPt
 // the refreshed distances) [U].  Returns the new number of cached points; their world positions on the link and
 // distances in wa / p[].d.  Everything is a select (mpt_sel): the cache stays in registers.
 __device__ __forceinline__ int manifold_core(const DevModel& M, const ContactK& K, const HullLanes& H, int n, MPt (&p)[4],
-                                             const float* Rw, f3 centre, f3 dl, f3 (&wa)[4]
-#ifdef SNK_PROFILE_FINE
-                                             , unsigned long long* prof_f = nullptr
-#endif
-                                             ) {
+                                             const float* Rw, f3 centre, f3 dl, f3 (&wa)[4] SNK_PROF_F_PARAM) {
     n = n < 0 ? 0 : (n > 4 ? 4 : n);
     const float thr = K.break_thr;
     const f3 zoff = mk3(0.f, 0.f, K.cyl_zoff);

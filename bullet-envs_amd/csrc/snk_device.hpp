@@ -22,7 +22,7 @@
 // Layers, bottom to top (each header includes what it uses, nothing that comes later):
 //   snk_wave.hpp      f3 / 3x3 helpers, wave64 primitives, own_stores_visible, DPP reduction steps
 //   snk_lds.hpp       the LDS images Lds<N, V2>, the solver-rules variants, the -D knobs
-//   snk_dynamics.hpp  FK, bias forces, ABA, sensor_pass_needed
+//   snk_dynamics.hpp  FK, bias forces, ABA, sensor_pass_needed, step_base_pose
 //   snk_contacts.hpp  rim point, friction directions, persistent manifolds: shared by both solves
 //   snk_selfcol.hpp   link-link and obstacle contacts (GJK)
 //   snk_freebox.hpp   obstacle 2, the free box

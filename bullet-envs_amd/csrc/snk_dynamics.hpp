@@ -238,11 +238,7 @@ __device__ void body_bias(LT& L, const DevModel& M, int lane) {
 // FACTOR: also builds the articulated inertias IA, U = IA S, D = S^T U and the base inverse.
 // ----------------------------------------------------------------------------------
 template <class LT, bool FACTOR>
-__device__ void aba_main(LT& L, const DevModel& M, int lane
-#ifdef SNK_PROFILE_FINE
-                         , unsigned long long* prof_f = nullptr
-#endif
-) {
+__device__ void aba_main(LT& L, const DevModel& M, int lane SNK_PROF_F_PARAM) {
     constexpr int N = LT::kN;
     float cA[6], cB[9], cC[6];   // child contribution to the parent's articulated inertia
 #pragma unroll
@@ -458,6 +454,31 @@ __device__ __forceinline__ bool sensor_pass_needed(LT& L, const DevModel& M, int
     const float tol = M.servo_tol * 1.001f;
     const bool sensor = !(se > tol * tol) || hint.counter_next > M.max_counter || !(hint.h_prev + reach < M.height_thr);
     return __builtin_amdgcn_readfirstlane(sensor ? 1 : 0) != 0;
+}
+
+// The pose of a free base `bs` ([pos3, quat4, omega3, vel3]: the snake's base, the free box) after dt at its new
+// velocity: btMultiBody::stepPositionsMultiDof's exponential-map update with its ANGULAR_MOTION_THRESHOLD rule [U].
+// Every lane computes it; lane 0 stores it behind a barrier (the other lanes' reads of bs), and the caller's barrier follows.
+__device__ __forceinline__ void step_base_pose(float* bs, float dt, int lane) {
+    f3 om = ld3(bs + 7), vl = ld3(bs + 10);
+    float fA = sqrtf(dot(om, om));
+    const float kThr = 0.78539816339744831f;   // 0.5 * pi/2  [U] ANGULAR_MOTION_THRESHOLD
+    if (fA * dt > kThr) fA = kThr / dt;
+    float sc;
+    if (fA < 0.001f) sc = 0.5f * dt - (dt * dt * dt) * 0.020833333333f * fA * fA;
+    else sc = sinf(0.5f * fA * dt) / fA;
+    float dx = om.x * sc, dy = om.y * sc, dz = om.z * sc, dw = cosf(fA * dt * 0.5f);
+    float qx = bs[3], qy = bs[4], qz = bs[5], qw = bs[6];
+    float nw = dw * qw - dx * qx - dy * qy - dz * qz;
+    float nx = dw * qx + dx * qw + dy * qz - dz * qy;
+    float ny = dw * qy - dx * qz + dy * qw + dz * qx;
+    float nz = dw * qz + dx * qy - dy * qx + dz * qw;
+    float inv = 1.0f / sqrtf(nx * nx + ny * ny + nz * nz + nw * nw);
+    lds_sync();
+    if (lane == 0) {
+        bs[0] += dt * vl.x; bs[1] += dt * vl.y; bs[2] += dt * vl.z;
+        bs[3] = nx * inv; bs[4] = ny * inv; bs[5] = nz * inv; bs[6] = nw * inv;
+    }
 }
 
 }  // namespace snk

@@ -10,8 +10,12 @@
 // durations (ticks) replace the motor torques of the record (tools/profile_phases.py)
 #ifdef SNK_PROFILE
 #define SNK_STAMP(i) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); prof_t[i] = t_; }
+#define SNK_PROF_T_PARAM , unsigned long long* prof_t
+#define SNK_PROF_T_ARG , prof_t
 #else
 #define SNK_STAMP(i)
+#define SNK_PROF_T_PARAM
+#define SNK_PROF_T_ARG
 #endif
 // -DSNK_PROFILE -DSNK_PROFILE_FINE (build.py --profile-fine): a second set of stamps around the dynamics' own pieces --
 // integrate, fk_vel, body_bias, the inward sweep, the base inverse, the outward sweep -- whose durations take the coarse
@@ -22,6 +26,16 @@
 #define SNK_FSTAMP(i) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); if (prof_f) prof_f[i] = t_; }
 #else
 #define SNK_FSTAMP(i)
+#endif
+// The tables travel as a last parameter that exists in the instrumented builds only (SNK_PROF_T_PARAM / SNK_PROF_F_PARAM
+// close a signature, SNK_PROF_T_ARG / SNK_PROF_F_ARG a call): text, not a type, so that a __noinline__ function's ABI
+// in the product is the one it has without them.
+#ifdef SNK_PROFILE_FINE
+#define SNK_PROF_F_PARAM , unsigned long long* prof_f = nullptr
+#define SNK_PROF_F_ARG , prof_f
+#else
+#define SNK_PROF_F_PARAM
+#define SNK_PROF_F_ARG
 #endif
 
 namespace snk {

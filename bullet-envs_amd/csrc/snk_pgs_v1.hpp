@@ -1082,51 +1082,14 @@ __device__ __forceinline__ void substep_v1(LT& L, const DevModel& M, int lane, f
         L.taum()[lane] = L.nc_app[nn - N + lane] * M.inv_dt;
     }
     lds_sync();
-    {
-        float* bs = L.base();
-        f3 om = ld3(bs + 7), vl = ld3(bs + 10);
-        float fA = sqrtf(dot(om, om));
-        const float kThr = 0.78539816339744831f;   // 0.5 * pi/2  [U] ANGULAR_MOTION_THRESHOLD
-        if (fA * dt > kThr) fA = kThr / dt;
-        float sc;
-        if (fA < 0.001f) sc = 0.5f * dt - (dt * dt * dt) * 0.020833333333f * fA * fA;
-        else sc = sinf(0.5f * fA * dt) / fA;
-        float dx = om.x * sc, dy = om.y * sc, dz = om.z * sc, dw = cosf(fA * dt * 0.5f);
-        float qx = bs[3], qy = bs[4], qz = bs[5], qw = bs[6];
-        float nw = dw * qw - dx * qx - dy * qy - dz * qz;
-        float nx = dw * qx + dx * qw + dy * qz - dz * qy;
-        float ny = dw * qy - dx * qz + dy * qw + dz * qx;
-        float nz = dw * qz + dx * qy - dy * qx + dz * qw;
-        float inv = 1.0f / sqrtf(nx * nx + ny * ny + nz * nz + nw * nw);
-        lds_sync();
-        if (lane == 0) {
-            bs[0] += dt * vl.x; bs[1] += dt * vl.y; bs[2] += dt * vl.z;
-            bs[3] = nx * inv; bs[4] = ny * inv; bs[5] = nz * inv; bs[6] = nw * inv;
-            L.fz() = fz;
-            L.fz3() = fz3;
-        }
+    step_base_pose(L.base(), dt, lane);
+    if (lane == 0) {
+        L.fz() = fz;
+        L.fz3() = fz3;
     }
     lds_sync();
     if (fbox) {
-        // the box's pose: btMultiBody::stepPositionsMultiDof, the same exponential-map update as the snake's base [U]
-        float* bx = L.box;
-        const f3 om = ld3(bx + 7), vl = ld3(bx + 10);
-        float fA = sqrtf(dot(om, om));
-        const float kThr = 0.78539816339744831f;
-        if (fA * dt > kThr) fA = kThr / dt;
-        const float sc = fA < 0.001f ? 0.5f * dt - (dt * dt * dt) * 0.020833333333f * fA * fA : sinf(0.5f * fA * dt) / fA;
-        const float dx = om.x * sc, dy = om.y * sc, dz = om.z * sc, dw = cosf(fA * dt * 0.5f);
-        const float qx = bx[3], qy = bx[4], qz = bx[5], qw = bx[6];
-        const float nw = dw * qw - dx * qx - dy * qy - dz * qz;
-        const float nx = dw * qx + dx * qw + dy * qz - dz * qy;
-        const float ny = dw * qy - dx * qz + dy * qw + dz * qx;
-        const float nz = dw * qz + dx * qy - dy * qx + dz * qw;
-        const float inv = 1.0f / sqrtf(nx * nx + ny * ny + nz * nz + nw * nw);
-        lds_sync();
-        if (lane == 0) {
-            bx[0] += dt * vl.x; bx[1] += dt * vl.y; bx[2] += dt * vl.z;
-            bx[3] = nx * inv; bx[4] = ny * inv; bx[5] = nz * inv; bx[6] = nw * inv;
-        }
+        step_base_pose(L.box, dt, lane);      // the box's pose: the same update as the snake's base [U]
         lds_sync();
     }
     SNK_STAMP(8)

@@ -170,11 +170,7 @@ __device__ __forceinline__ void append_obstacle_v2(LT& L, int lane, const ObsHit
 }
 
 template <class LT>
-__device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned long long* __restrict__ ovf
-#ifdef SNK_PROFILE_FINE
-                                , unsigned long long* prof_f = nullptr
-#endif
-                                ) {
+__device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned long long* __restrict__ ovf SNK_PROF_F_PARAM) {
     constexpr int N = LT::kN;
     static_assert(4 * N == 64, "one contact slot per lane");
     SNK_FSTAMP(8)
@@ -212,11 +208,7 @@ __device__ int find_contacts_v2(LT& L, const DevModel& M, int lane, unsigned lon
             cyl_world_rot(Rb, M.cyl_R[c], Rw);
             const f3 dl = mk3(-Rw[6], -Rw[7], -Rw[8]);
             const f3 centre = ld3(L.o[b]) + mulRv(Rb, ld3(M.cyl_c[c]));
-#ifdef SNK_PROFILE_FINE
-            cnt = manifold_core(M, K, H, (int)L.mfn[c], p, Rw, centre, dl, wa, prof_f);
-#else
-            cnt = manifold_core(M, K, H, (int)L.mfn[c], p, Rw, centre, dl, wa);
-#endif
+            cnt = manifold_core(M, K, H, (int)L.mfn[c], p, Rw, centre, dl, wa SNK_PROF_F_ARG);
         }
         int total;
         (void)lane_prefix3(cnt, lane, total);
@@ -1037,11 +1029,7 @@ __device__ __forceinline__ void contact_rows(float (&RJ)[kSlots], float (&RM)[kS
 // test_substep_api_servo_converges on the GPU; the failing object was an uncommitted intermediate.  The cause above is
 // therefore the best-supported reading, not a proven one: DESIGN.md 4.)
 template <class LT>
-__device__ __noinline__ void sensor_pass_v2(LT& L, const DevModel& M, const int nc, const int nlim
-#ifdef SNK_PROFILE
-                                            , unsigned long long* prof_t
-#endif
-) {
+__device__ __noinline__ void sensor_pass_v2(LT& L, const DevModel& M, const int nc, const int nlim SNK_PROF_T_PARAM) {
     constexpr int N = LT::kN;
     const int lane = lane_id();
     // lane = contact: its force and its moment about the body's joint origin (staging rows are
@@ -1121,11 +1109,7 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
 #endif
     SNK_STAMP(0)
     // (1) contacts of the current pose, (2) bias forces with gravity, joint damping torque
-#ifdef SNK_PROFILE_FINE
-    const int nc = __builtin_amdgcn_readfirstlane(find_contacts_v2(L, M, lane, ovf, prof_f));
-#else
-    const int nc = __builtin_amdgcn_readfirstlane(find_contacts_v2(L, M, lane, ovf));
-#endif
+    const int nc = __builtin_amdgcn_readfirstlane(find_contacts_v2(L, M, lane, ovf SNK_PROF_F_ARG));
     ncontacts = nc;
     if (nc < 0) return;            // does not fit this solve: nothing has been touched (substep() takes the other one)
     SNK_STAMP(1)
@@ -1138,11 +1122,7 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     body_bias<LT, true>(L, M, lane);
     lds_sync();
     SNK_FSTAMP(1)
-#ifdef SNK_PROFILE_FINE
-    aba_main<LT, true>(L, M, lane, prof_f);
-#else
-    aba_main<LT, true>(L, M, lane);
-#endif
+    aba_main<LT, true>(L, M, lane SNK_PROF_F_ARG);
     SNK_STAMP(2)
     // joint-0 force sensor, first pass [U] (parked in LDS: nothing but rows may live across the solve)
     {
@@ -1497,13 +1477,7 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     prof_t[14] = prof_t[13]; prof_t[15] = prof_t[13];
     if (sensor && lane == 0) atomicAdd(ovf + 2, 1ull);
 #endif
-    if (sensor) {
-#ifdef SNK_PROFILE
-        sensor_pass_v2(L, M, nc, nlim, prof_t);
-#else
-        sensor_pass_v2(L, M, nc, nlim);
-#endif
-    }
+    if (sensor) sensor_pass_v2(L, M, nc, nlim SNK_PROF_T_ARG);
     // (7) apply the solver's delta-v (lower half's copy), motor torques, integrate positions
     lds_sync();
     SNK_FSTAMP(5)
@@ -1519,28 +1493,7 @@ __device__ __forceinline__ void substep_v2(LT& L, const DevModel& M, int lane_in
     }
     if (lane < N) L.taum()[lane] = L.app[lane] * M.inv_dt;
     lds_sync();
-    {
-        float* bs = L.base();
-        f3 om = ld3(bs + 7), vl = ld3(bs + 10);
-        float fA = sqrtf(dot(om, om));
-        const float kThr = 0.78539816339744831f;   // [U] ANGULAR_MOTION_THRESHOLD
-        if (fA * dt > kThr) fA = kThr / dt;
-        float sc;
-        if (fA < 0.001f) sc = 0.5f * dt - (dt * dt * dt) * 0.020833333333f * fA * fA;
-        else sc = sinf(0.5f * fA * dt) / fA;
-        float dx = om.x * sc, dy = om.y * sc, dz = om.z * sc, dw = cosf(fA * dt * 0.5f);
-        float qx = bs[3], qy = bs[4], qz = bs[5], qw = bs[6];
-        float nw = dw * qw - dx * qx - dy * qy - dz * qz;
-        float nx = dw * qx + dx * qw + dy * qz - dz * qy;
-        float ny = dw * qy - dx * qz + dy * qw + dz * qx;
-        float nz = dw * qz + dx * qy - dy * qx + dz * qw;
-        float inv = 1.0f / sqrtf(nx * nx + ny * ny + nz * nz + nw * nw);
-        lds_sync();
-        if (lane == 0) {
-            bs[0] += dt * vl.x; bs[1] += dt * vl.y; bs[2] += dt * vl.z;
-            bs[3] = nx * inv; bs[4] = ny * inv; bs[5] = nz * inv; bs[6] = nw * inv;
-        }
-    }
+    step_base_pose(L.base(), dt, lane);
     lds_sync();
     SNK_FSTAMP(6)
     fk_vel(L, M, lane);

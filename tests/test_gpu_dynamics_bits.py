@@ -6,37 +6,21 @@ that reorders a sum passes it.  An edit that is meant to leave the arithmetic al
 physics step runs: the states are written with set_state.
 
 Every call gets the list IDS -- a repeat and an id outside the handle -- and is made once without a list.
-tools/dynamics_hash.py prints the same hashes for any library of the same ABI (SNK_LIB); `--pins` prints the block of
-tests/golden/dynamics_bits.json.  The pins belong to ONE toolchain and flag set and are keyed over every stamp of the
-library (libsnk.so.toolchain, .cmd, .render.cmd, .world.cmd, .dyn.cmd); under an unknown key the tests SKIP and say what to
-do.  A mismatch names the case and the part (which output array).  This test names nothing but output hashes."""
-import hashlib
-import json
-import os
-
+`tools/bits_hash.py dynamics` prints the same hashes for any library of the same ABI (SNK_LIB); `--pins` prints the block of
+tests/golden/dynamics_bits.json.  The pins belong to ONE toolchain and flag set and are keyed (tests/bit_pins.py) over every
+stamp of the library (libsnk.so.toolchain, .cmd, .render.cmd, .world.cmd, .dyn.cmd); under an unknown key the tests SKIP and
+say what to do.  A mismatch names the case and the part (which output array).  This test names nothing but output hashes."""
 import numpy as np
 import pytest
 
+import bit_pins
 import np_dynamics as nd_
 from test_gpu_dynamics import VARIANTS, stepper
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, "golden", "dynamics_bits.json")
-STAMPS = ("libsnk.so.toolchain", "libsnk.so.cmd", "libsnk.so.render.cmd", "libsnk.so.world.cmd", "libsnk.so.dyn.cmd")
-
 E = 5
 IDS = [3, 0, 3, 7, 1]                  # a repeat, and 7: outside a 5-env handle
-
-
-def toolchain_key():
-    pkgdir = os.path.join(os.path.dirname(HERE), "bullet-envs_amd")
-    try:
-        txt = "\n".join(open(os.path.join(pkgdir, s)).read() for s in STAMPS)
-    except OSError:
-        return None, "%s are missing (a library not built by bullet-envs_amd/build.py)" % " / ".join(STAMPS)
-    return hashlib.sha256(txt.encode()).hexdigest()[:12], txt
 
 
 def dynamics_case(variant):
@@ -71,23 +55,13 @@ def dynamics_case(variant):
 CASES = {"dynamics/" + v: dynamics_case(v) for v in VARIANTS}
 
 
-def dynamics_hashes(pkg, cases=None):
-    """{case: {part: sha256[:16]}} of the named cases (None: all), what the test pins and tools/dynamics_hash.py prints"""
+def hashes(pkg, case):
+    """{part: sha256[:16]} of a named case, what the test pins and `tools/bits_hash.py dynamics` prints"""
     import torch
-    return {c: {part: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16] for part, a in CASES[c](pkg, torch)}
-            for c in (CASES if cases is None else cases)}
+    return bit_pins.array_hashes(CASES[case](pkg, torch))
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_dynamics_bits_are_pinned(pkg, case):
     pytest.importorskip("torch")
-    key, txt = toolchain_key()
-    pinned = json.load(open(GOLDEN))
-    if key not in pinned:
-        pytest.skip("no pinned dynamics bits for this toolchain / flag set (key %s: %s).  Verify tests/test_gpu_dynamics.py on "
-                    "it, then run `python tools/dynamics_hash.py --pins` on the GPU box and add the block it prints to "
-                    "tests/golden/dynamics_bits.json." % (key, txt))
-    got = dynamics_hashes(pkg, [case])[case]
-    want = pinned[key]["cases"][case]
-    differ = sorted(p for p in set(got) | set(want) if got.get(p) != want.get(p))
-    assert not differ, "%s: %s differ from the pinned bits (got %s)" % (case, ", ".join(differ), got)
+    bit_pins.check("dynamics", case, lambda: hashes(pkg, case))

@@ -8,22 +8,22 @@ helper, a re-layout of a stage) must leave THESE hashes alone.  No physics step 
 with set_state / set_manifold / set_box, so these pins do not move when the step kernels' (tests/test_gpu_bits.py) do.
 
 Every id-taking call gets the list IDS -- a repeat and an id outside the handle -- and is called once without a list.
-tools/query_hash.py prints the same hashes for any library of the same ABI (SNK_LIB); `--pins` prints the block of
+`tools/bits_hash.py query` prints the same hashes for any library of the same ABI (SNK_LIB); `--pins` prints the block of
 tests/golden/query_bits.json.  The pins belong to ONE toolchain and flag set and are keyed as tests/test_gpu_bits.py keys
-its own, over every stamp that describes these units (libsnk.so.toolchain, .cmd, .render.cmd, .world.cmd); under an unknown
-key the tests SKIP and say what to do.  A mismatch names the case and the part (which output array).
+its own (tests/bit_pins.py), over every stamp that describes these units (libsnk.so.toolchain, .cmd, .render.cmd,
+.world.cmd); under an unknown key the tests SKIP and say what to do.  A mismatch names the case and the part (which output
+array).
 
 test_a_block_taking_a_second_row_... pins nothing: it is the one test of a block that takes a second row (more rows than
 the grid's 65536 blocks), where the row loop's trailing barrier is all that keeps the next row's record load from the
 lanes still reading this row's."""
 import contextlib
-import hashlib
-import json
 import os
 
 import numpy as np
 import pytest
 
+import bit_pins
 import np_closest as ncl
 import ray_sets as RY
 import render_scenes as RS
@@ -33,10 +33,6 @@ from test_gpu_contacts import synthetic_box, synthetic_cache
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, "golden", "query_bits.json")
-STAMPS = ("libsnk.so.toolchain", "libsnk.so.cmd", "libsnk.so.render.cmd", "libsnk.so.world.cmd")
-
 E = 5
 IDS = [3, 0, 3, 7, 1]                  # a repeat, and 7: outside a 5-env handle
 # variant -> (n_modules, SNK_FORCE_STREAMED): Lds<16, true>, Lds<16, false>, Lds<32, false>
@@ -45,15 +41,6 @@ VARIANTS = {"16": (16, False), "16s": (16, True), "32": (32, False)}
 # the static box on the streamed-row image
 SCENES = {"16s": ("16s", False), "16f": ("16f", False), "32": ("32", False), "16s-streamed": ("16s", True)}
 BOX, LINKS = 1, 2
-
-
-def toolchain_key():
-    pkgdir = os.path.join(os.path.dirname(HERE), "bullet-envs_amd")
-    try:
-        txt = "\n".join(open(os.path.join(pkgdir, s)).read() for s in STAMPS)
-    except OSError:
-        return None, "%s are missing (a library not built by bullet-envs_amd/build.py)" % " / ".join(STAMPS)
-    return hashlib.sha256(txt.encode()).hexdigest()[:12], txt
 
 
 @contextlib.contextmanager
@@ -247,26 +234,15 @@ for _s in SCENES:
     CASES["render/" + _s] = render_case(_s)
 
 
-def query_hashes(pkg, cases=None):
-    """{case: {part: sha256[:16]}} of the named cases (None: all), what the test pins and tools/query_hash.py prints"""
-    d = Dev()
-    return {c: {part: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16] for part, a in CASES[c](pkg, d)}
-            for c in (CASES if cases is None else cases)}
+def hashes(pkg, case):
+    """{part: sha256[:16]} of a named case, what the test pins and `tools/bits_hash.py query` prints"""
+    return bit_pins.array_hashes(CASES[case](pkg, Dev()))
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_query_bits_are_pinned(pkg, case):
     pytest.importorskip("torch")
-    key, txt = toolchain_key()
-    pinned = json.load(open(GOLDEN))
-    if key not in pinned:
-        pytest.skip("no pinned query bits for this toolchain / flag set (key %s: %s).  Verify the query kernels' accuracy tests "
-                    "on it, then run `python tools/query_hash.py --pins` on the GPU box and add the block it prints to "
-                    "tests/golden/query_bits.json." % (key, txt))
-    got = query_hashes(pkg, [case])[case]
-    want = pinned[key]["cases"][case]
-    differ = sorted(p for p in set(got) | set(want) if got.get(p) != want.get(p))
-    assert not differ, "%s: %s differ from the pinned bits (got %s)" % (case, ", ".join(differ), got)
+    bit_pins.check("query", case, lambda: hashes(pkg, case))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

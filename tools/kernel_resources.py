@@ -10,11 +10,13 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "bullet-envs_amd"))
+from build import SOURCES      # noqa: E402  (the library's translation units, the working tree's: build.py's table)
 
 
-def device_asm(root, args, out, src="csrc/snk_api.hip"):
-    """Compiles <root>/bullet-envs_amd/<src> (the step kernels' translation unit; main() also lists the renderer's,
-    csrc/snk_render.hip, the world kernels', csrc/snk_world.hip, and the dynamics queries', csrc/snk_dyn.hip) device-only to assembly with the product's own flags (that tree's
+def device_asm(root, args, out, src=SOURCES[0]):
+    """Compiles <root>/bullet-envs_amd/<src> (the step kernels' translation unit; main() lists every unit of
+    build.py's table) device-only to assembly with the product's own flags (that tree's
     `build.py --print-flags`) plus `args`; returns the command.  (tools/same_isa.py compares two trees with it.)"""
     pkg = os.path.join(root, "bullet-envs_amd")
     flags = subprocess.check_output([sys.executable, os.path.join(pkg, "build.py"), "--print-flags"], text=True).split()
@@ -25,9 +27,8 @@ def device_asm(root, args, out, src="csrc/snk_api.hip"):
 
 def main():
     print("%-46s %6s %6s %9s %5s" % ("kernel", "VGPRs", "SGPRs", "scratch B", "occ"))
-    for src in ("csrc/snk_api.hip", "csrc/snk_render.hip", "csrc/snk_world.hip", "csrc/snk_dyn.hip"):
-        if os.path.exists(os.path.join(ROOT, "bullet-envs_amd", src)):
-            one(src)
+    for src in SOURCES:
+        one(src)
 
 
 def one(src):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Is the device code of the working tree the same as that of a git revision?  Compiles each of the four translation units
-(csrc/snk_api.hip, snk_render.hip, snk_world.hip, snk_dyn.hip) device-only to assembly (tools/kernel_resources.py: build.py's flags) for
+"""Is the device code of the working tree the same as that of a git revision?  Compiles each translation unit of the
+working tree's build.py (its table of units) device-only to assembly (tools/kernel_resources.py: build.py's flags) for
 both, drops the lines that carry the `__hip_cuid_<hash>` symbol (it hashes the input) and prints one verdict per file:
 `identical`, or else the symbols whose text differs (exit status 1 if any file differs); a unit the revision does not
 have is `new in the working tree` with its kernels listed, and no difference.  The check for a
@@ -13,9 +13,7 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-from kernel_resources import ROOT, device_asm
-
-SOURCES = ("csrc/snk_api.hip", "csrc/snk_render.hip", "csrc/snk_world.hip", "csrc/snk_dyn.hip")
+from kernel_resources import ROOT, SOURCES, device_asm
 
 
 def sections(path):
