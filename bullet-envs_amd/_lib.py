@@ -127,6 +127,8 @@ SYMBOLS = {
     "snk_dynamics_host": (C.c_int, [_vp, _I32, C.c_int32, C.c_int32, _F, _F]),
     "snk_jacobians": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "snk_jacobians_host": (C.c_int, [_vp, _I32, C.c_int32, _I32, _F, C.c_int32, _F]),
+    "snk_apply_impulse": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_float, _vp, _vp]),
+    "snk_apply_impulse_host": (C.c_int, [_vp, _U8, _F, _I32, _F, C.c_int32, C.c_int32, C.c_float, _F]),
     "snk_view_matrix_ypr": (C.c_int, [_F, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _F]),
     "snk_projection_fov": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, _F]),
     "snk_last_error": (C.c_char_p, []),
@@ -148,6 +150,10 @@ RAYS_ALL = RAYS_GROUND | RAYS_SNAKE | RAYS_BOX
 BIAS_VELOCITY = 1       # SNK_BIAS_VELOCITY: the Coriolis, centrifugal and gyroscopic terms of snk_dynamics' h
 BIAS_GRAVITY = 2        # SNK_BIAS_GRAVITY: minus the generalised gravity force
 JAC_MAX_POINTS = 256    # SNK_JAC_MAX_POINTS: points of one snk_jacobians call
+WRENCH_FLOATS = 9           # SNK_WRENCH_FLOATS, a wrench of snk_apply_impulse: [force 3 | torque 3 | point 3]
+IMPULSE_LINK_FRAME = 1      # SNK_IMPULSE_LINK_FRAME: force, torque and point in the link's COM frame (else world)
+IMPULSE_DRY = 2             # SNK_IMPULSE_DRY: the delta only, nothing of the state written
+IMPULSE_MAX_POINTS = 256    # SNK_IMPULSE_MAX_POINTS: points of one snk_apply_impulse call
 
 #: the camera behind render() / getCameraImage when the caller gives no matrices [U]: the reference calls
 #: resetDebugVisualizerCamera(1.5, -30, -90, [1.28, 0, 0]) right before its getCameraImage (snake.py:322-327) -- the reading
@@ -875,6 +881,51 @@ class Stepper:
         check(self.lib.snk_jacobians_host(self.h, idp, k, rows.ctypes.data_as(_I32) if P else None,
                                           fptr(loc) if loc is not None else None, P, fptr(jac)), "snk_jacobians_host")
         return jac
+
+    # ---- the applied forces (snk_apply_impulse and its host form) ----
+    def apply_impulse_device(self, active_ptr=0, gen_force_ptr=0, link_rows_ptr=0, wrench_ptr=0, n_points=0, flags=0,
+                             seconds=0.0, delta_ptr=0, stream=0):
+        """snk_apply_impulse: u += seconds x M^-1 Q for the envs whose byte of active [n_envs] u8 is non-zero (0: all), Q =
+        gen_force [n_envs, nd] f32 + the wrenches [n_envs, n_points, 9] f32 on the links link_rows [n_points] i32; delta
+        [n_envs, nd] f32.  Every buffer a device pointer or 0.  Asynchronous on `stream`."""
+        check(self.lib.snk_apply_impulse(self.h, active_ptr or None, gen_force_ptr or None, link_rows_ptr or None,
+                                         wrench_ptr or None, int(n_points), int(flags), float(seconds), delta_ptr or None,
+                                         stream or None), "snk_apply_impulse")
+
+    def apply_impulse(self, gen_force=None, link_rows=None, wrenches=None, flags=0, seconds=None, active=None):
+        """snk_apply_impulse_host: the velocity of the active envs (active [n_envs] bool / uint8; None: all) becomes u +
+        delta, delta = seconds x M^-1 Q (flags IMPULSE_DRY: nothing is written), and delta [n_envs, nd] float32 comes back.
+        Q = gen_force [n_envs, nd] (moment about the root origin 3 | force 3 | joint torques n; None: none) + the wrenches
+        [n_envs, P, 9] = [force 3 | torque 3 | point 3] on the links link_rows [P] (rows of link_states; one list for every
+        env), in world axes at a world point, or with IMPULSE_LINK_FRAME in the link's COM frame.  seconds None: the
+        handle's dt as the kernels hold it (snk.h, "The applied forces")."""
+        nd = self.n + 6
+        gf = None
+        if gen_force is not None:
+            gf = np.ascontiguousarray(gen_force, dtype=np.float32)
+            if gf.shape != (self.n_envs, nd):
+                raise ValueError("gen_force must be [%d, %d], got %s" % (self.n_envs, nd, gf.shape))
+        rows = np.zeros(0, np.int32) if link_rows is None else np.ascontiguousarray(link_rows, dtype=np.int32).reshape(-1)
+        P = len(rows)
+        wr = None
+        if P or wrenches is not None:
+            if wrenches is None:
+                raise ValueError("link_rows without wrenches")
+            wr = np.ascontiguousarray(wrenches, dtype=np.float32)
+            if wr.shape != (self.n_envs, P, WRENCH_FLOATS):
+                raise ValueError("wrenches must be [%d, %d, %d], got %s" % (self.n_envs, P, WRENCH_FLOATS, wr.shape))
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(active).astype(np.uint8).reshape(-1)
+            if act.shape != (self.n_envs,):
+                raise ValueError("active must be [%d], got %s" % (self.n_envs, act.shape))
+        delta = np.zeros((self.n_envs, nd), np.float32)
+        check(self.lib.snk_apply_impulse_host(self.h, act.ctypes.data_as(_U8) if act is not None else None,
+                                              fptr(gf) if gf is not None else None, rows.ctypes.data_as(_I32) if P else None,
+                                              fptr(wr) if wr is not None and P else None, P, int(flags),
+                                              float(np.float32(self.params.dt)) if seconds is None else float(seconds),
+                                              fptr(delta)), "snk_apply_impulse_host")
+        return delta
 
     def timing_enable(self, capacity):
         check(self.lib.snk_timing_enable(self.h, int(capacity)), "snk_timing_enable")

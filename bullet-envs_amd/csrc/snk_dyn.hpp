@@ -284,4 +284,122 @@ __global__ __launch_bounds__(64) void jacobians_kernel(const DevModel* __restric
     }
 }
 
+// ----------------------------------------------------------------------------------
+// impulse_kernel (include/snk.h, "The applied forces": snk_apply_impulse): the one kernel of this unit that WRITES the
+// state -- the velocity floats of the record and nothing else.  One wave per env (the mask's byte per env, not an id
+// list: two rows of one env would race), in front of whatever steps next; the step kernels do not know of it.
+//   Q   lane = component d of u: gen_force[d], plus per point the lane's screw against the point's world wrench,
+//       ang . (tau + (x - P) x f) + lin . f where the component moves the link's body (dof_body(d) <= body), else nothing:
+//       the operands of jacobians_kernel's column d, so that Q = gen_force + sum_p J_p^T [f_p ; tau_p].  The points are
+//       staged kJacPointsPerPass at a time, lane = point: the link's frame (link_row_frame), the wrench turned to world
+//       axes (SNK_IMPULSE_LINK_FRAME) and the body, twelve floats, which every lane then reads as broadcasts.
+//   M^-1 Q   the articulated-body recursion the substep itself runs (aba_main<FACTOR>, snk_dynamics.hpp) on an image with
+//       no velocity in it: zeta = 0, the bodies' bias forces 0, no damping, no gravity -- the joint entries of Q as the
+//       joint torques, minus its first six as the base's bias force.  In the device code's own coordinates (world axes,
+//       each body about its joint origin, r[b] between neighbours, S_b = [axis ; 0]): inward IA_b, U_b = IA_b S_b, D_b =
+//       S_b . U_b and the force recursion, a 6 x 6 inverse at the base, outward the accelerations.  Never a factorisation
+//       of the dense M: the tip joints' 1e-4 kg m^2 sit next to whole kg m^2.
+//   delta = seconds x that, one float per lane; without SNK_IMPULSE_DRY the record's velocity float becomes u + delta by
+//       ONE float32 add (contraction off: not an fma of seconds), stored straight to the record.
+// An env whose byte is 0 is neither loaded nor stored; its delta row is zeros.
+// ----------------------------------------------------------------------------------
+constexpr int kImpulseLinkFrame = 1, kImpulseDry = 2;      // SNK_IMPULSE_LINK_FRAME, SNK_IMPULSE_DRY
+constexpr int kWrenchFloats = 9;                           // SNK_WRENCH_FLOATS: [force 3 | torque 3 | point 3]
+
+template <int N, bool V2>
+__global__ __launch_bounds__(64) void impulse_kernel(const DevModel* __restrict__ Mp, float* __restrict__ recs,
+                                                     const float* __restrict__ links, const uint8_t* __restrict__ active,
+                                                     const float* __restrict__ gen_force,
+                                                     const int32_t* __restrict__ link_rows_in,
+                                                     const float* __restrict__ wrench, int n_points, int flags, float seconds,
+                                                     float* __restrict__ delta, int n_envs) {
+    using LT = Lds<N, V2>;
+    constexpr int ND = N + 6, LR = 3 * N + 2, PP = kJacPointsPerPass;
+    __shared__ float4 smem_raw[(sizeof(LT) + 15) / 16];
+    __shared__ float pts[PP][12];      // per staged point: [x 3 | f 3 | tau 3 | body (int bits; -1: no such link) | - -]
+    LT& L = *reinterpret_cast<LT*>(smem_raw);
+    const DevModel& M = *Mp;
+    const int lane = threadIdx.x;
+    const int col = lane < ND ? lane : 0;
+    const int bd = dof_body(col);
+    for (int row = blockIdx.x; row < n_envs; row += gridDim.x) {
+        if (active && !active[row]) {      // (the same byte for every lane: the wave skips the env as one)
+            if (delta && lane < ND) delta[(size_t)row * ND + lane] = 0.f;
+            continue;
+        }
+        int env;
+        load_row_env(L, M, recs, nullptr, row, n_envs, lane, env);
+        f3 ang, lin, P;
+        dof_screw(L, col, ang, lin, P);
+        float Q = (gen_force && lane < ND) ? gen_force[(size_t)row * ND + lane] : 0.f;
+#pragma unroll 1
+        for (int p0 = 0; p0 < n_points; p0 += PP) {
+            const int cnt = n_points - p0 < PP ? n_points - p0 : PP;
+            if (lane < cnt) {
+                const int p = p0 + lane;
+                const int lr = link_rows_in[p];
+                const float* w = wrench + ((size_t)row * n_points + p) * kWrenchFloats;
+                f3 x = mk3(0.f, 0.f, 0.f), f = x, t = x;
+                int b = -1;
+                if (lr >= 0 && lr < LR) {
+                    float Rw[9];
+                    f3 ow, cw;
+                    b = link_row_frame(L, links + (size_t)lr * kLinkFloats, Rw, ow, cw);
+                    f = ld3(w); t = ld3(w + 3); x = ld3(w + 6);
+                    if (flags & kImpulseLinkFrame) {
+                        f = mulRv(Rw, f); t = mulRv(Rw, t); x = cw + mulRv(Rw, x);
+                    }
+                }
+                float* s = pts[lane];
+                st3(s, x); st3(s + 3, f); st3(s + 6, t); s[9] = __int_as_float(b);
+            }
+            lds_sync();
+#pragma unroll 1
+            for (int k = 0; k < cnt; k++) {
+                const float* s = pts[k];
+                const f3 x = ld3(s), f = ld3(s + 3), t = ld3(s + 6);
+                if (bd <= __float_as_int(s[9])) Q += dot(ang, t + cross(x - P, f)) + dot(lin, f);
+            }
+            lds_sync();      // (the stage is read by every lane above: the next pass waits for them)
+        }
+        // the image aba_main<FACTOR> reads, without velocities: lane = body its inertia about its joint origin (body_bias's
+        // layout [[Ibar, m [c]x], [-m [c]x, m 1]]), no bias force, no velocity product; lane = component its entry of Q
+        if (lane <= N) {
+            const int b = lane;
+            const float* R = L.R[b];
+            const float m = M.mass[b];
+            const f3 cw = mulRv(R, ld3(M.com[b]));
+            float Ibar[6];
+            rotSym(R, M.Ib[b], Ibar);
+            float* IA = L.IA[b];
+#pragma unroll
+            for (int i = 0; i < 6; i++) IA[i] = Ibar[i];
+            const float hx = m * cw.x, hy = m * cw.y, hz = m * cw.z;
+            IA[6] = 0.f; IA[7] = -hz; IA[8] = hy;
+            IA[9] = hz;  IA[10] = 0.f; IA[11] = -hx;
+            IA[12] = -hy; IA[13] = hx; IA[14] = 0.f;
+            IA[15] = m; IA[16] = 0.f; IA[17] = 0.f; IA[18] = m; IA[19] = 0.f; IA[20] = m;
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                L.zeta[b][i] = 0.f;
+                if (b > 0) L.p[b][i] = 0.f;
+            }
+        }
+        if (lane < 6) L.p[0][lane] = -Q;
+        else if (lane < ND) L.tauj[lane - 6] = Q;
+        lds_sync();
+        aba_main<LT, true>(L, M, lane);      // (ends in a barrier: acc0 and qdd are there for every lane)
+        if (lane < ND) {
+#pragma clang fp contract(off)
+            const float dl = seconds * (lane < 6 ? L.acc0[lane] : L.qdd[lane - 6]);
+            if (delta) delta[(size_t)row * ND + lane] = dl;
+            if (!(flags & kImpulseDry)) {
+                const int at = lane < 6 ? 7 + lane : 13 + N + (lane - 6);      // omega, v | qd: the record's order
+                recs[(size_t)env * LT::REC + at] = L.rec[at] + dl;
+            }
+        }
+        lds_sync();      // (the record and the sweeps' results are read by every lane above: the next env waits)
+    }
+}
+
 }  // namespace snk

@@ -457,6 +457,58 @@ class DeviceWorld(_TensorArgs):
         self._keep(ids, rows, loc)
         return out
 
+    def apply_forces(self, gen_force=None, link_rows=None, wrenches=None, frame="world", duration=None, active=None,
+                     dry=False, out=None):
+        """Applies forces for `duration` seconds to the state as it lies: the velocity u of every active env becomes u +
+        delta, delta = duration x M(q)^-1 Q, by one launch in front of whatever steps next (snk_apply_impulse; include/snk.h,
+        "The applied forces") -- PyBullet's applyExternalForce / applyExternalTorque and, with max_motor_impulse=0,
+        TORQUE_CONTROL.  Q = gen_force + sum over the points of J^T [force ; torque], J what jacobians() reports:
+        gen_force  [E, nd] float32 or None: moment about the root origin 3 | force 3 | joint torques n (conjugate to u)
+        link_rows  P rows of link_states (Bullet link + 1), a list or an int32 tensor, shared by every env; 0 .. 256 of them
+        wrenches   [E, P, 9] float32: [force 3 | torque 3 | point 3] per env and point
+        frame      "world": world axes and a world point (WORLD_FRAME); "link": the link's COM frame (LINK_FRAME)
+        duration   seconds the forces are held (None: the handle's dt as the kernels hold it)
+        active     uint8 / bool [E] or None (all): an env whose byte is 0 keeps every bit of its state; its delta is zeros
+        dry        nothing is written: delta alone (impulse_response)
+        Returns `out` ([E, nd] float32: delta) when given or when dry, else None."""
+        t = self.torch
+        nd = self.n + 6
+        if frame not in ("world", "link"):
+            raise ValueError("frame must be 'world' or 'link', got %r" % (frame,))
+        if gen_force is not None:
+            gen_force = self._arg(gen_force, "gen_force", (t.float32,), (self.num_envs, nd))
+        rows = None
+        P = 0
+        if link_rows is not None:
+            rows = t.as_tensor(link_rows, dtype=t.int32, device=self.device).reshape(-1).contiguous()
+            P = int(rows.numel())
+        if P > _lib.IMPULSE_MAX_POINTS:
+            raise ValueError("link_rows must name 0 .. %d points, got %d" % (_lib.IMPULSE_MAX_POINTS, P))
+        if P or wrenches is not None:
+            if wrenches is None:
+                raise ValueError("link_rows without wrenches")
+            wrenches = self._arg(wrenches, "wrenches", (t.float32,), (self.num_envs, P, _lib.WRENCH_FLOATS))
+        if gen_force is None and P == 0:
+            raise ValueError("nothing to apply: neither gen_force nor wrenches")
+        if active is not None:
+            active = self._arg(active, "active", (t.uint8, t.bool), (self.num_envs,))
+        if dry or out is not None:
+            out = self._out(out, "out", (self.num_envs, nd))
+        seconds = float(np.float32(self.params.dt)) if duration is None else float(duration)
+        flags = (_lib.IMPULSE_LINK_FRAME if frame == "link" else 0) | (_lib.IMPULSE_DRY if dry else 0)
+        self.stepper.apply_impulse_device(active.data_ptr() if active is not None else 0,
+                                          gen_force.data_ptr() if gen_force is not None else 0,
+                                          rows.data_ptr() if P else 0, wrenches.data_ptr() if P else 0, P, flags, seconds,
+                                          out.data_ptr() if out is not None else 0, self._stream())
+        self._keep(active, gen_force, rows, wrenches)
+        return out
+
+    def impulse_response(self, gen_force=None, link_rows=None, wrenches=None, frame="world", duration=None, active=None,
+                         out=None):
+        """[E, nd] float32: M(q)^-1 Q x duration of apply_forces' arguments, with nothing of the state written (its dry
+        form): what the forces WOULD do to u."""
+        return self.apply_forces(gen_force, link_rows, wrenches, frame, duration, active, dry=True, out=out)
+
     def reset(self, mask=None, out=None):
         """The soft reset (snake.py:96-99, 119-127) of the envs of `mask` (uint8 / bool [E]; None: all) onto their rows
         of the reset-pose table.  Returns the observations [E, 3n + 8]; rows of unmasked envs are left as `out` had them

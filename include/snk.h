@@ -731,6 +731,65 @@ int snk_jacobians(snk_handle* h, const int32_t* env_ids_dev, int32_t n_rows, con
 int snk_jacobians_host(snk_handle* h, const int32_t* env_ids, int32_t n_rows, const int32_t* link_rows, const float* local,
                        int32_t n_points, float* jac);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The applied forces: the contract of snk_apply_impulse (what PyBullet exposes as applyExternalForce, applyExternalTorque
+ * and TORQUE_CONTROL, which the reference never calls and a controller computing tau = h + J^T f from the dynamics
+ * queries, or a trainer pushing a link for a few substeps, does).  The kernel (bullet-envs_amd/csrc/snk_dyn.hpp:
+ * impulse_kernel) and the independent numpy model of the tests (tests/np_impulse.py) are both written from this text.
+ *
+ * What it is.  Forward dynamics is affine in the applied force: ABA(q, u, Q) = ABA(q, u, 0) + M(q)^-1 Q.  A generalised
+ * force Q held for `seconds` is therefore, to first order, the velocity impulse delta = seconds x M(q)^-1 Q, and this call
+ * adds it to the velocity the state holds NOW, by a kernel of its own, in front of whatever steps next (snk_substep,
+ * snk_step, the fused env-step): the step kernels do not know of it.  With max_motor_impulse = 0 in snk_params (motors
+ * off) it is TORQUE_CONTROL; with the default motors it is a push on a servo-held snake.
+ *
+ * Q = gen_force + sum_p J_p^T [f_p ; tau_p], in the coordinates of "The dynamics queries":
+ *   gen_force_dev [n_envs][nd] f32 or NULL: the generalised force conjugate to u = [omega | v | qd] -- the moment about the
+ *     root link's origin (world axes) 3, the force 3, the joint torques n; Q . u is power.
+ *   link_rows_dev [n_points] i32: rows of snk_link_states, ONE list shared by every env (as in snk_jacobians); n_points in
+ *     0 .. SNK_IMPULSE_MAX_POINTS, with 0 both pointers may be NULL.  A row may repeat: its wrenches add up.
+ *   wrench_dev [n_envs][n_points][SNK_WRENCH_FLOATS] f32: [force 3 | torque 3 | point 3] per env and point.  Without
+ *     SNK_IMPULSE_LINK_FRAME (PyBullet's WORLD_FRAME) force and torque are in world axes and the point is a world position
+ *     that rides on the link for this call; with it (LINK_FRAME) all three are in the link's COM frame, the frame of
+ *     snk_jacobians' local_dev: origin the link's COM, axes the link's rotation.  J_p is exactly the Jacobian
+ *     snk_jacobians reports for that link and point.  A link row outside 0 .. 3n + 1 cannot be refused on the device
+ *     path: it contributes nothing.
+ *   A call with neither gen_force_dev nor points is refused.
+ * delta = seconds x M(q)^-1 Q, M the matrix snk_dynamics reports: rigid bodies only, no damping and no h -- a caller who
+ * wants unconstrained forward dynamics passes Q - h.  It is computed by the articulated-body recursion of the substep
+ * itself, never by factoring the dense M.  seconds must be finite and >= 0.  delta_dev [n_envs][nd] f32 or NULL.
+ *
+ * What is written.  active_dev [n_envs] u8 or NULL (all envs): snk_substep's mask, not an id list -- the call writes state
+ * and repeated ids would race.  An env whose byte is 0 is neither loaded nor stored and its row of delta is zeros.  Of an
+ * active env the velocity floats of the record -- floats 7-12 and 13 + n .. 12 + 2n of snk_get_state -- become u + delta,
+ * ONE float32 add per component, and nothing else is written: pose, q, the aux floats (motor torques, joint-0 force,
+ * previous x), the contact cache, the free box, the ground friction and the reset poses keep their bits.  With
+ * SNK_IMPULSE_DRY the arithmetic is the same and nothing of the state is written: delta_dev (required then) is the
+ * impulse response M^-1 Q x seconds.  No clamp is applied: the next substep's max_coord_vel rule sees the new velocity.
+ * The free box of obstacle 2 cannot be pushed: it is a body of its own with no component in u, and is out of scope here.
+ *
+ * [U] Next to Bullet.  Bullet puts an applied force into the SAME articulated-body pass as -h(q, u) and the damping; here
+ * the step that follows evaluates those at u + delta instead of u.  The difference is dt x d(h + damping)/du x delta:
+ * second order in dt (measured: DESIGN.md 3, "Other deviations"; tests/test_np_impulse.py prints it).
+ *
+ * Asynchronous on `stream`, one launch (one wave per env), no atomics, no waits, nothing allocated: it can be captured in
+ * a graph.  It does not synchronise, copy or validate.  Refused, naming the argument: a null or poisoned handle; unknown
+ * flag bits; n_points out of range; points without link_rows_dev or without wrench_dev; nothing to apply;
+ * SNK_IMPULSE_DRY without delta_dev; seconds negative or not finite; a pointer that is not 4-byte aligned.
+ * snk_apply_impulse_host: the same with HOST buffers; it synchronises the device first, like the state accessors, and also
+ * refuses a link row outside 0 .. 3n + 1 and, in the rows of the active envs, a non-finite generalised force, wrench or
+ * point -- each with its index.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SNK_WRENCH_FLOATS 9          /* [force 3 | torque 3 | point 3] */
+#define SNK_IMPULSE_LINK_FRAME 1     /* flags: force, torque and point are in the link's COM frame (PyBullet's LINK_FRAME);
+                                        without it world axes and a world point (WORLD_FRAME) */
+#define SNK_IMPULSE_DRY 2            /* flags: compute delta only, write nothing of the state */
+#define SNK_IMPULSE_MAX_POINTS 256   /* points of one snk_apply_impulse call */
+int snk_apply_impulse(snk_handle* h, const uint8_t* active_dev, const float* gen_force_dev, const int32_t* link_rows_dev,
+                      const float* wrench_dev, int32_t n_points, int32_t flags, float seconds, float* delta_dev, void* stream);
+int snk_apply_impulse_host(snk_handle* h, const uint8_t* active, const float* gen_force, const int32_t* link_rows,
+                           const float* wrench, int32_t n_points, int32_t flags, float seconds, float* delta);
+
 /* Where this build's structural limits were met, counted on the device since snk_create (Bullet has no such limits;
  * DESIGN.md 3).  Ground contacts have none left: the streamed-row solve has a slot for every point its chain's manifolds
  * can hold (8n), and the register-resident 16-link solve hands the substeps that outgrow its 64 slots to it.
@@ -773,7 +832,7 @@ int snk_debug_set_tickets(snk_handle* h, uint32_t base);
  * after a real alarm: snk_step / snk_step_packed / snk_step_traced(_host) / snk_step_host / snk_reset(_host) / snk_substep_host and the state
  * accessors (get/set state, manifold, box, obs, mean height, link positions, joint-3 force, set_ground_friction,
  * snk_set_reset_pose, snk_get_reset_pose, snk_set_reset_pose_dev) and snk_render / snk_render_host and the tensor seam
- * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host), snk_contacts(_host), snk_closest_points(_host)) and snk_ray_test(_host) and snk_dynamics(_host) and snk_jacobians(_host) return
+ * (snk_substep, snk_observe, snk_link_states(_host), snk_copy_envs(_host), snk_contacts(_host), snk_closest_points(_host)) and snk_ray_test(_host) and snk_dynamics(_host) and snk_jacobians(_host) and snk_apply_impulse(_host) return
  * non-zero -- and snk_reset_pose_floats, snk_contact_slots, snk_link_pairs, snk_closest_slots and snk_dyn_dofs 0 -- with snk_last_error() = "env-step scheduler: a bounded wait ran out ..."; snk_destroy succeeds.  The
  * reference's failure story is SubprocVecEnv.close() draining and joining its workers
  * (ppo/multiprocessing_env.py:140-150): here too the only way on is to destroy the handle and create a new one. */
