@@ -210,6 +210,45 @@ def check(rc, what):
         raise RuntimeError("%s failed: %s" % (what, last_error()))
 
 
+def _call(name, *args):
+    """One library call that reports by return code; the name is written once, so the message names this call."""
+    check(getattr(load(), name)(*args), name)
+
+
+class _ArgError(ValueError, AssertionError):
+    """A caller's array or tensor does not fit the call.  Raised by _host here and by device_env's _arg, never by an
+    `assert` statement: the checks in front of the C calls hold under `python -O`.  (Also an AssertionError: that is
+    what the oldest of these checks raised.)"""
+
+
+_PTR = {np.dtype(np.float32): _F, np.dtype(np.uint8): _U8, np.dtype(np.int32): _I32, np.dtype(np.float64): _D}
+
+
+def _host(x, dtype, shape, what, says=None, optional=False, inplace=False, flat=False, row=False):
+    """A caller's array as a host form reads it: contiguous, of `dtype`, of `shape` (None: any), or _ArgError "`what`
+    must have shape .., got .." (`says` replaces the text in front of the comma).  optional: None stays None, an absent
+    argument; inplace: the call writes into the caller's own array, so nothing is converted: it is a contiguous ndarray
+    of `dtype` already; flat: any shape of that many elements, read as one row; row: one row shape[1:] stands for every
+    row."""
+    if x is None and optional:
+        return None
+    if inplace and not (isinstance(x, np.ndarray) and x.dtype == dtype and x.flags.c_contiguous):
+        raise _ArgError("%s must be a C-contiguous %s ndarray" % (what, np.dtype(dtype).name))
+    a = np.ascontiguousarray(x, dtype=dtype)
+    if flat:
+        a = a.reshape(-1)
+    if row and a.shape == tuple(shape[1:]):
+        a = np.ascontiguousarray(np.broadcast_to(a, shape))
+    if shape is not None and a.shape != tuple(shape):
+        raise _ArgError("%s, got %s" % (says or "%s must have shape %s" % (what, tuple(shape)), a.shape))
+    return a
+
+
+def _ptr(a):
+    """The pointer of a host array as SYMBOLS types it; None, an absent argument, is NULL."""
+    return None if a is None else a.ctypes.data_as(_PTR[a.dtype])
+
+
 def default_params(**over):
     p = SnkParams()
     load().snk_default_params(C.byref(p))
@@ -228,7 +267,7 @@ def noncontact_order(n_modules):
     """The sweep order the kernels are compiled with for snk_params::noncontact_order 1 (snk_debug_noncontact_order):
     2n entries, 0..n-1 = limit j, n..2n-1 = motor j - n, in the order of the forward sweep."""
     out = np.zeros(2 * int(n_modules), np.int32)
-    check(load().snk_debug_noncontact_order(int(n_modules), out.ctypes.data_as(_I32)), "snk_debug_noncontact_order")
+    _call("snk_debug_noncontact_order", int(n_modules), _ptr(out))
     return out
 
 
@@ -241,7 +280,7 @@ def rows_layout(n_modules):
     """The layout of the streamed-row solve's block of rows (snk_debug_rows_layout; snk_lds.hpp: Lds<N, false>) as a dict
     of ROWS_LAYOUT's names.  Host arithmetic only: no handle, no device."""
     out = np.zeros(len(ROWS_LAYOUT), np.int32)
-    check(load().snk_debug_rows_layout(int(n_modules), out.ctypes.data_as(_I32)), "snk_debug_rows_layout")
+    _call("snk_debug_rows_layout", int(n_modules), _ptr(out))
     return dict(zip(ROWS_LAYOUT, (int(x) for x in out)))
 
 
@@ -250,7 +289,7 @@ def reach_bound(params=None, **over):
     (longest joint-to-joint offset [m], |COM of the base link| [m], both rounded up by 1.001; fixed slack [m])."""
     p = params if params is not None else default_params(**over)
     out = np.zeros(3, np.float32)
-    check(load().snk_debug_reach_bound(C.byref(p), out.ctypes.data_as(_F)), "snk_debug_reach_bound")
+    _call("snk_debug_reach_bound", C.byref(p), _ptr(out))
     return float(out[0]), float(out[1]), float(out[2])
 
 
@@ -263,27 +302,27 @@ def link_inertial_offsets(n_modules=16, **params):
     localInertialFramePosition; row r = Bullet link r - 1).  Host arithmetic only: no handle, no device."""
     p = default_params(n_modules=int(n_modules), **params)
     out = np.zeros((3 * int(n_modules) + 2, 3), np.float64)
-    check(load().snk_link_inertial_offsets(C.byref(p), out.ctypes.data_as(_D)), "snk_link_inertial_offsets")
+    _call("snk_link_inertial_offsets", C.byref(p), _ptr(out))
     return out
 
 
 def contact_links(n_modules=16, **params):
     """snk_contact_links: [2n] int32, the Bullet link index of every collision cylinder's link (PyBullet's linkIndexA of a
     contact of that cylinder; row link + 1 of link_states).  Host arithmetic only: no handle, no device."""
-    p = default_params(n_modules=int(n_modules), **params)
-    out = np.zeros(2 * int(n_modules), np.int32)
-    check(load().snk_contact_links(C.byref(p), out.ctypes.data_as(_I32)), "snk_contact_links")
+    return _contact_links(default_params(n_modules=int(n_modules), **params))
+
+
+def _contact_links(p):
+    out = np.zeros(2 * p.n_modules, np.int32)
+    _call("snk_contact_links", C.byref(p), _ptr(out))
     return out
 
 
 def view_matrix_ypr(target, distance, yaw, pitch, roll=0.0, up_axis=2):
     """snk_view_matrix_ypr: PyBullet's computeViewMatrixFromYawPitchRoll [U], a column-major float32 16-vector."""
-    t = np.ascontiguousarray(target, dtype=np.float32)
-    if t.shape != (3,):
-        raise ValueError("camera target must hold 3 values, got %s" % (t.shape,))
+    t = _host(target, np.float32, (3,), "target", "camera target must hold 3 values")
     out = np.zeros(16, np.float32)
-    check(load().snk_view_matrix_ypr(fptr(t), float(distance), float(yaw), float(pitch), float(roll), int(up_axis), fptr(out)),
-          "snk_view_matrix_ypr")
+    _call("snk_view_matrix_ypr", _ptr(t), float(distance), float(yaw), float(pitch), float(roll), int(up_axis), _ptr(out))
     return out
 
 
@@ -291,7 +330,7 @@ def projection_fov(fov, aspect, near, far):
     """snk_projection_fov: PyBullet's computeProjectionMatrixFOV [U], a column-major float32 16-vector (far == near gives
     the infinite entries the formula gives; nothing raises)."""
     out = np.zeros(16, np.float32)
-    check(load().snk_projection_fov(float(fov), float(aspect), float(near), float(far), fptr(out)), "snk_projection_fov")
+    _call("snk_projection_fov", float(fov), float(aspect), float(near), float(far), _ptr(out))
     return out
 
 
@@ -372,7 +411,7 @@ class Stepper:
         self.lib = load()
         self.params = params if params is not None else default_params(**over)
         h = _vp()
-        check(self.lib.snk_create(C.byref(self.params), int(n_envs), int(device), C.byref(h)), "snk_create")
+        _call("snk_create", C.byref(self.params), int(n_envs), int(device), C.byref(h))
         self.h = h
         self.n_envs = int(n_envs)
         self.device = int(device)
@@ -392,32 +431,46 @@ class Stepper:
         except Exception:
             pass
 
+    def _call(self, name, *args):
+        """Every call on the handle that reports by return code: the name is written once."""
+        check(getattr(self.lib, name)(self.h, *args), name)
+
+    def _count(self, name, *args):
+        """The getters whose zero is a refusal: the count, or the library's reason."""
+        k = int(getattr(self.lib, name)(self.h, *args))
+        if k == 0:
+            raise RuntimeError("%s failed: %s" % (name, last_error()))
+        return k
+
+    def _zeros(self, *shape, dtype=np.float32):
+        """a fresh per-env table [n_envs, *shape]"""
+        return np.zeros((self.n_envs,) + shape, dtype=dtype)
+
+    def _read(self, name, *shape):
+        """The getters of one float32 table [n_envs, *shape]."""
+        out = self._zeros(*shape)
+        self._call(name, _ptr(out))
+        return out
+
     # ---- host-buffer calls ----
     def reset(self, mask=None):
-        obs = np.zeros((self.n_envs, self.obs_dim), dtype=np.float32)
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(mask, dtype=np.uint8)
-            assert m.shape == (self.n_envs,)
-        check(self.lib.snk_reset_host(self.h, m.ctypes.data_as(_U8) if m is not None else None, fptr(obs)),
-              "snk_reset_host")
+        obs = self._zeros(self.obs_dim)
+        self._call("snk_reset_host", _ptr(_host(mask, np.uint8, (self.n_envs,), "mask", optional=True)), _ptr(obs))
         return obs
 
     def _step(self, actions, vec_mode, traced):
         """step and step_traced, as step_host is in C: the trace is the only variation."""
-        assert actions.dtype == np.float32 and actions.flags.c_contiguous
-        assert actions.shape == (self.n_envs, self.act_dim)
+        _host(actions, np.float32, (self.n_envs, self.act_dim), "actions", inplace=True)
         obs = np.empty((self.n_envs, self.obs_dim), dtype=np.float32)
         rew = np.empty(self.n_envs, dtype=np.float32)
         done = np.empty(self.n_envs, dtype=np.uint8)
         sub = np.empty(self.n_envs, dtype=np.int32)
-        out = (fptr(actions), fptr(obs), fptr(rew), done.ctypes.data_as(_U8), sub.ctypes.data_as(_I32))
+        out = (_ptr(actions), _ptr(obs), _ptr(rew), _ptr(done), _ptr(sub))
         if not traced:
-            check(self.lib.snk_step_host(self.h, *out, 1 if vec_mode else 0), "snk_step_host")
+            self._call("snk_step_host", *out, 1 if vec_mode else 0)
             return obs, rew, done.astype(bool), sub
         trace = np.full(self.trace_shape(), np.nan, dtype=np.float32)
-        check(self.lib.snk_step_traced_host(self.h, *out, fptr(trace), trace.shape[1], 1 if vec_mode else 0),
-              "snk_step_traced_host")
+        self._call("snk_step_traced_host", *out, _ptr(trace), trace.shape[1], 1 if vec_mode else 0)
         return obs, rew, done.astype(bool), sub, trace
 
     def step(self, actions, vec_mode=True):
@@ -435,10 +488,8 @@ class Stepper:
         return self._step(actions, vec_mode, True)
 
     def substep(self, targets, k=1):
-        t = np.ascontiguousarray(targets, dtype=np.float32)
-        assert t.shape == (self.n_envs, self.n)
-        info = np.zeros((self.n_envs, 2), dtype=np.int32)
-        check(self.lib.snk_substep_host(self.h, fptr(t), int(k), info.ctypes.data_as(_I32)), "snk_substep_host")
+        info = self._zeros(2, dtype=np.int32)
+        self._call("snk_substep_host", _ptr(_host(targets, np.float32, (self.n_envs, self.n), "targets")), int(k), _ptr(info))
         return info
 
     def debug_rows_layout(self):
@@ -448,88 +499,59 @@ class Stepper:
     def debug_rows(self):
         """[n_envs, kRowFloats] float32: every env's block of streamed rows as its last substep left it (snk_debug_rows:
         streamed-row handles of at most as many envs as resident waves, right after substep())."""
-        out = np.zeros((self.n_envs, self.debug_rows_layout()["kRowFloats"]), dtype=np.float32)
+        out = self._zeros(self.debug_rows_layout()["kRowFloats"])
         for e in range(self.n_envs):
-            check(self.lib.snk_debug_rows(self.h, e, fptr(out[e])), "snk_debug_rows")
+            self._call("snk_debug_rows", e, _ptr(out[e]))
         return out
 
+    def _table(self, x, what, *shape):
+        """the pointer of a caller's float32 table [n_envs, *shape] (None, where the call allows it: NULL)"""
+        return _ptr(_host(x, np.float32, (self.n_envs,) + shape, what, optional=True))
+
     def get_state(self):
-        s = np.zeros((self.n_envs, self.state_dim), dtype=np.float32)
-        a = np.zeros((self.n_envs, self.n + 2), dtype=np.float32)
-        check(self.lib.snk_get_state(self.h, fptr(s), fptr(a)), "snk_get_state")
+        s, a = self._zeros(self.state_dim), self._zeros(self.n + 2)
+        self._call("snk_get_state", _ptr(s), _ptr(a))
         return s, a
 
     def set_state(self, state=None, aux=None):
-        s = a = None
-        if state is not None:
-            s = np.ascontiguousarray(state, dtype=np.float32)
-            assert s.shape == (self.n_envs, self.state_dim)
-        if aux is not None:
-            a = np.ascontiguousarray(aux, dtype=np.float32)
-            assert a.shape == (self.n_envs, self.n + 2)
-        check(self.lib.snk_set_state(self.h, fptr(s) if s is not None else None, fptr(a) if a is not None else None),
-              "snk_set_state")
+        self._call("snk_set_state", self._table(state, "state", self.state_dim), self._table(aux, "aux", self.n + 2))
 
     def get_reset_pose(self):
         """The reset-pose table (snk_get_reset_pose): [n_envs, 7 + n] = per env [position 3 | quaternion xyzw 4 | joint
         angles n], what the env's next soft reset -- reset() or the step kernel's own on `done` -- lands on."""
-        p = np.zeros((self.n_envs, 7 + self.n), dtype=np.float32)
-        check(self.lib.snk_get_reset_pose(self.h, fptr(p)), "snk_get_reset_pose")
-        return p
+        return self._read("snk_get_reset_pose", 7 + self.n)
 
     def set_reset_pose(self, pose, mask=None):
         """snk_set_reset_pose: rows [position 3 | quaternion xyzw 4 | joint angles n] for the envs of `mask` (None: all).
         pose is [n_envs, 7 + n], or one row [7 + n] that every (masked) env gets.  Rows of unmasked envs are ignored."""
-        p = np.asarray(pose, dtype=np.float32)
-        if p.shape == (7 + self.n,):
-            p = np.broadcast_to(p, (self.n_envs, 7 + self.n))
-        if p.shape != (self.n_envs, 7 + self.n):
-            raise ValueError("reset pose must have shape (%d, %d) or (%d,), got %s"
-                             % (self.n_envs, 7 + self.n, 7 + self.n, np.shape(pose)))
-        p = np.ascontiguousarray(p)
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-            if m.shape != (self.n_envs,):
-                raise ValueError("mask must have shape (%d,), got %s" % (self.n_envs, m.shape))
-        check(self.lib.snk_set_reset_pose(self.h, m.ctypes.data_as(_U8) if m is not None else None, fptr(p)),
-              "snk_set_reset_pose")
+        W = 7 + self.n
+        p = _host(pose, np.float32, (self.n_envs, W), "pose",
+                  "reset pose must have shape (%d, %d) or (%d,)" % (self.n_envs, W, W), row=True)
+        m = _host(None if mask is None else np.asarray(mask) != 0, np.uint8, (self.n_envs,), "mask", optional=True)
+        self._call("snk_set_reset_pose", _ptr(m), _ptr(p))
 
     def set_reset_pose_device(self, pose_ptr, mask_ptr=0, stream=0):
         """snk_set_reset_pose_dev: the same update from device buffers ([n_envs, 7 + n] f32, mask [n_envs] u8 or 0 for
         all), asynchronous on `stream`; nothing is validated."""
-        check(self.lib.snk_set_reset_pose_dev(self.h, mask_ptr or None, pose_ptr, stream or None), "snk_set_reset_pose_dev")
+        self._call("snk_set_reset_pose_dev", mask_ptr, pose_ptr, stream)
 
     def get_manifold(self):
         """contact_model 1: [n_envs, 2n, 29] contact cache (see snk.h); None for a contact_model 0 handle."""
         if self.lib.snk_manifold_floats(self.h) == 0:
             return None
-        m = np.zeros((self.n_envs, 2 * self.n, 29), dtype=np.float32)
-        check(self.lib.snk_get_manifold(self.h, fptr(m)), "snk_get_manifold")
-        return m
+        return self._read("snk_get_manifold", 2 * self.n, 29)
 
     def set_manifold(self, m):
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        assert m.shape == (self.n_envs, 2 * self.n, 29)
-        check(self.lib.snk_set_manifold(self.h, fptr(m)), "snk_set_manifold")
+        self._call("snk_set_manifold", _ptr(_host(m, np.float32, (self.n_envs, 2 * self.n, 29), "manifold")))
 
     def get_box(self):
         """obstacle 2: (state [n_envs, 13], manifold with the plane [n_envs, 29]) of the free box."""
-        s = np.zeros((self.n_envs, 13), dtype=np.float32)
-        m = np.zeros((self.n_envs, 29), dtype=np.float32)
-        check(self.lib.snk_get_box(self.h, fptr(s), fptr(m)), "snk_get_box")
+        s, m = self._zeros(13), self._zeros(29)
+        self._call("snk_get_box", _ptr(s), _ptr(m))
         return s, m
 
     def set_box(self, state=None, manifold=None):
-        s = m = None
-        if state is not None:
-            s = np.ascontiguousarray(state, dtype=np.float32)
-            assert s.shape == (self.n_envs, 13)
-        if manifold is not None:
-            m = np.ascontiguousarray(manifold, dtype=np.float32)
-            assert m.shape == (self.n_envs, 29)
-        check(self.lib.snk_set_box(self.h, fptr(s) if s is not None else None, fptr(m) if m is not None else None),
-              "snk_set_box")
+        self._call("snk_set_box", self._table(state, "state", 13), self._table(manifold, "manifold", 29))
 
     def snapshot(self, reset_pose=True):
         """The simulator state of every env as a Snapshot (the EFFECTIVE friction, read back from the device);
@@ -562,100 +584,83 @@ class Stepper:
         every point the manifolds can hold), link-link / obstacle contacts left out).  The last two at zero mean Bullet's
         'no limit' held."""
         out = (C.c_uint64 * 3)()
-        check(self.lib.snk_contact_overflow(self.h, out), "snk_contact_overflow")
+        self._call("snk_contact_overflow", out)
         return int(out[0]), int(out[1]), int(out[2])
 
     def contact_histogram_enable(self, on=True):
         """Switches the per-substep counting on or off (off after creation: one atomic per substep, 0.7 % of the rate)."""
-        check(self.lib.snk_contact_histogram_enable(self.h, 1 if on else 0), "snk_contact_histogram_enable")
+        self._call("snk_contact_histogram_enable", 1 if on else 0)
 
     def contact_histogram(self, reset=False):
         """snk_contact_histogram: out[k] = physics substeps that ran with k contact points while the counting was enabled
         (since the last call with reset=True); the last bin collects everything beyond it."""
         n = int(self.lib.snk_contact_histogram_bins())
         out = (C.c_uint64 * n)()
-        check(self.lib.snk_contact_histogram(self.h, out, 1 if reset else 0), "snk_contact_histogram")
+        self._call("snk_contact_histogram", out, 1 if reset else 0)
         return np.array(out[:], dtype=np.uint64)
 
     def get_obs(self):
-        o = np.zeros((self.n_envs, self.obs_dim), dtype=np.float32)
-        check(self.lib.snk_get_obs(self.h, fptr(o)), "snk_get_obs")
-        return o
+        return self._read("snk_get_obs", self.obs_dim)
 
     def mean_height(self):
-        o = np.zeros(self.n_envs, dtype=np.float32)
-        check(self.lib.snk_mean_height(self.h, fptr(o)), "snk_mean_height")
-        return o
+        return self._read("snk_mean_height")
 
     def link_positions(self):
         """[n_envs, 3(n+1)]: getLinkPositions of every env ([x.., y.., z..] of links 0,3,...,3n)."""
-        o = np.zeros((self.n_envs, 3 * (self.n + 1)), dtype=np.float32)
-        check(self.lib.snk_link_positions(self.h, fptr(o)), "snk_link_positions")
-        return o
+        return self._read("snk_link_positions", 3 * (self.n + 1))
 
     def joint3_reaction_fz(self):
         """Fz of the first motor joint's reaction (Bullet joint 3) after the last substep, [n_envs]."""
-        o = np.zeros(self.n_envs, dtype=np.float32)
-        check(self.lib.snk_joint3_reaction_fz(self.h, fptr(o)), "snk_joint3_reaction_fz")
-        return o
+        return self._read("snk_joint3_reaction_fz")
 
     def set_ground_friction(self, mu):
-        m = np.ascontiguousarray(mu, dtype=np.float32)
-        assert m.shape == (self.n_envs,)
-        check(self.lib.snk_set_ground_friction(self.h, fptr(m)), "snk_set_ground_friction")
+        self._call("snk_set_ground_friction", _ptr(_host(mu, np.float32, (self.n_envs,), "mu")))
 
     def get_ground_friction(self):
         """The effective per-env plane friction (ones unless set), read back from the device."""
-        m = np.zeros(self.n_envs, dtype=np.float32)
-        check(self.lib.snk_get_ground_friction(self.h, fptr(m)), "snk_get_ground_friction")
-        return m
+        return self._read("snk_get_ground_friction")
 
     def debug_set_tickets(self, base):
-        check(self.lib.snk_debug_set_tickets(self.h, int(base) & 0xFFFFFFFF), "snk_debug_set_tickets")
+        self._call("snk_debug_set_tickets", int(base) & 0xFFFFFFFF)
 
     def debug_raise_alarm(self):
         """Test hook: the scheduler's alarm raised from the host (include/snk.h); the handle is poisoned afterwards."""
-        check(self.lib.snk_debug_raise_alarm(self.h), "snk_debug_raise_alarm")
+        self._call("snk_debug_raise_alarm")
 
     def model_describe(self):
         bodies = np.zeros((self.n + 1, 10))
         origins = np.zeros((self.n + 1, 3))
-        check(self.lib.snk_model_describe(self.h, bodies.ctypes.data_as(_D), origins.ctypes.data_as(_D)),
-              "snk_model_describe")
+        self._call("snk_model_describe", _ptr(bodies), _ptr(origins))
         return bodies, origins
 
-    # ---- device-pointer calls (torch tensors own the memory) ----
+    # ---- device-pointer calls (torch tensors own the memory; a pointer 0 is NULL: ctypes converts it) ----
     def step_device(self, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr=0, vec_mode=True, stream=0):
-        check(self.lib.snk_step(self.h, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr or None,
-                                1 if vec_mode else 0, stream or None), "snk_step")
+        self._call("snk_step", actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr, 1 if vec_mode else 0, stream)
 
     def step_traced_device(self, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr, trace_ptr, trace_rows, vec_mode=True,
                            stream=0):
         """snk_step_traced: snk_step plus one trace row per physics substep, [n_envs x trace_rows x trace row floats] f32
         at trace_ptr (128-byte aligned); sub_ptr is required (it says how many rows of each env are valid)."""
-        check(self.lib.snk_step_traced(self.h, actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr or None, trace_ptr or None,
-                                       int(trace_rows), 1 if vec_mode else 0, stream or None), "snk_step_traced")
+        self._call("snk_step_traced", actions_ptr, obs_ptr, rew_ptr, done_ptr, sub_ptr, trace_ptr, int(trace_rows),
+                   1 if vec_mode else 0, stream)
 
     def step_packed_device(self, actions_ptr, packed_ptr, row_stride, sub_ptr=0, vec_mode=True, stream=0):
         """snk_step_packed: rows [obs | reward f32 | done u32] of `row_stride` floats in one device buffer."""
-        check(self.lib.snk_step_packed(self.h, actions_ptr, packed_ptr, int(row_stride), sub_ptr or None,
-                                       1 if vec_mode else 0, stream or None), "snk_step_packed")
+        self._call("snk_step_packed", actions_ptr, packed_ptr, int(row_stride), sub_ptr, 1 if vec_mode else 0, stream)
 
     def reset_device(self, mask_ptr=0, obs_ptr=0, stream=0):
-        check(self.lib.snk_reset(self.h, mask_ptr or None, obs_ptr or None, stream or None), "snk_reset")
+        self._call("snk_reset", mask_ptr, obs_ptr, stream)
 
     # ---- the tensor seam: substeps, read-outs, link states and forks on device pointers (0: none) ----
     def substep_device(self, targets_ptr, k=1, active_ptr=0, info_ptr=0, stream=0):
         """snk_substep: k physics substeps towards targets [n_envs, n] f32 for the envs whose byte of active [n_envs] u8
         is non-zero (0: all); info [n_envs, 2] i32.  Asynchronous on `stream`."""
-        check(self.lib.snk_substep(self.h, targets_ptr or None, int(k), active_ptr or None, info_ptr or None, stream or None),
-              "snk_substep")
+        self._call("snk_substep", targets_ptr, int(k), active_ptr, info_ptr, stream)
 
     def observe_device(self, obs_ptr=0, height_ptr=0, linkpos_ptr=0, stream=0):
         """snk_observe: observation [n_envs, obs_dim], mean height [n_envs], link positions [n_envs, 3(n+1)], each f32
         or 0.  Asynchronous on `stream`."""
-        check(self.lib.snk_observe(self.h, obs_ptr or None, height_ptr or None, linkpos_ptr or None, stream or None),
-              "snk_observe")
+        self._call("snk_observe", obs_ptr, height_ptr, linkpos_ptr, stream)
 
     @property
     def link_rows(self):
@@ -664,42 +669,34 @@ class Stepper:
 
     def link_states_device(self, ids_ptr, n_rows, out_ptr, stream=0):
         """snk_link_states: out [n_rows, 3n + 2, 16] f32 for the envs ids [n_rows] i32 (0: envs 0 .. n_rows - 1)."""
-        check(self.lib.snk_link_states(self.h, ids_ptr or None, int(n_rows), out_ptr or None, stream or None),
-              "snk_link_states")
+        self._call("snk_link_states", ids_ptr, int(n_rows), out_ptr, stream)
 
     def copy_envs_device(self, src_ptr, dst_ptr, n_pairs, reset_pose=False, stream=0):
         """snk_copy_envs: env dst[i] becomes env src[i] (ids [n_pairs] i32 on the device; nothing validated)."""
-        check(self.lib.snk_copy_envs(self.h, src_ptr or None, dst_ptr or None, int(n_pairs),
-                                     COPY_RESET_POSE if reset_pose else 0, stream or None), "snk_copy_envs")
+        self._call("snk_copy_envs", src_ptr, dst_ptr, int(n_pairs), COPY_RESET_POSE if reset_pose else 0, stream)
 
     def _ids(self, env_ids):
-        """(int32 array or None, how many envs it names, its pointer or None) of an `env_ids` argument (None: all envs)"""
-        if env_ids is None:
-            return None, self.n_envs, None
-        ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-        return ids, len(ids), ids.ctypes.data_as(_I32)
+        """(the pointer of an `env_ids` argument as an int32 list, NULL for None: all envs; how many envs it names)"""
+        ids = _host(env_ids, np.int32, None, "env_ids", optional=True, flat=True)
+        return _ptr(ids), self.n_envs if ids is None else len(ids)
 
     def link_states(self, env_ids=None):
         """snk_link_states_host: [k, 3n + 2, 16] float32 of the envs `env_ids` (None: all; ids may repeat, any order):
         per link [COM 3 | quaternion xyzw 4 | link-frame origin 3 | COM velocity 3 | angular velocity 3], world frame."""
-        ids, k, idp = self._ids(env_ids)
+        idp, k = self._ids(env_ids)
         out = np.zeros((max(k, 1), 3 * self.n + 2, LINK_STATE_FLOATS), np.float32)
-        check(self.lib.snk_link_states_host(self.h, idp, k, fptr(out)), "snk_link_states_host")
+        self._call("snk_link_states_host", idp, k, _ptr(out))
         return out
 
     @property
     def contact_slots(self):
         """snk_contact_slots: contact slots per env, 8n (+ 4 with the free box); raises on a contact_model 0 handle."""
-        k = int(self.lib.snk_contact_slots(self.h))
-        if k == 0:
-            raise RuntimeError("snk_contact_slots failed: %s" % last_error())
-        return k
+        return self._count("snk_contact_slots")
 
     def contacts_device(self, ids_ptr, n_rows, points_ptr=0, force_ptr=0, count_ptr=0, stream=0):
         """snk_contacts: points [n_rows, slots, 16] f32, force [n_rows, 2n + 1] f32, count [n_rows] i32 (each a device
         pointer or 0) for the envs ids [n_rows] i32 (0: envs 0 .. n_rows - 1).  Asynchronous on `stream`."""
-        check(self.lib.snk_contacts(self.h, ids_ptr or None, int(n_rows), points_ptr or None, force_ptr or None,
-                                    count_ptr or None, stream or None), "snk_contacts")
+        self._call("snk_contacts", ids_ptr, int(n_rows), points_ptr, force_ptr, count_ptr, stream)
 
     def contacts(self, env_ids=None):
         """snk_contacts_host: (points [k, slots, 16] float32, force [k, 2n + 1] float32, count [k] int32) of the envs
@@ -707,43 +704,33 @@ class Stepper:
         cached point j of cylinder c; the last four of an obstacle 2 handle: the free box) is [point on the body 3 | point
         on the ground 3 | normal 3 | distance | normal force N | impulse | c (2n: the box) | j | live | 0], sixteen zeros
         when not live; force sums a cylinder's live slots, entry 2n the box's."""
-        ids, k, idp = self._ids(env_ids)
+        idp, k = self._ids(env_ids)
         slots = self.contact_slots
         points = np.zeros((max(k, 1), slots, CONTACT_FLOATS), np.float32)
         force = np.zeros((max(k, 1), 2 * self.n + 1), np.float32)
         count = np.zeros(max(k, 1), np.int32)
-        check(self.lib.snk_contacts_host(self.h, idp, k, fptr(points), fptr(force), count.ctypes.data_as(_I32)),
-              "snk_contacts_host")
+        self._call("snk_contacts_host", idp, k, _ptr(points), _ptr(force), _ptr(count))
         return points, force, count
 
     def contact_links(self):
         """snk_contact_links of this handle's parameters (module function contact_links)."""
-        out = np.zeros(2 * self.n, np.int32)
-        check(self.lib.snk_contact_links(C.byref(self.params), out.ctypes.data_as(_I32)), "snk_contact_links")
-        return out
+        return _contact_links(self.params)
 
     @property
     def link_pairs(self):
         """snk_link_pairs: the link-link pairs of the chain, C(2n, 2) - (2n - 1) (465 / 1953)."""
-        k = int(self.lib.snk_link_pairs(self.h))
-        if k == 0:
-            raise RuntimeError("snk_link_pairs failed: %s" % last_error())
-        return k
+        return self._count("snk_link_pairs")
 
     def closest_slots(self, max_pairs):
         """snk_closest_slots: slots per env of closest_points' table, 2n + max_pairs."""
-        k = int(self.lib.snk_closest_slots(self.h, int(max_pairs)))
-        if k == 0:
-            raise RuntimeError("snk_closest_slots failed: %s" % last_error())
-        return k
+        return self._count("snk_closest_slots", int(max_pairs))
 
     def closest_points_device(self, ids_ptr, n_rows, distance, flags, max_pairs, points_ptr=0, clearance_ptr=0, count_ptr=0,
                               stream=0):
         """snk_closest_points: points [n_rows, 2n + max_pairs, 16] f32, clearance [n_rows, 2, 2n] f32, count [n_rows, 2] i32
         (each a device pointer or 0) for the envs ids [n_rows] i32 (0: envs 0 .. n_rows - 1).  Asynchronous on `stream`."""
-        check(self.lib.snk_closest_points(self.h, ids_ptr or None, int(n_rows), float(distance), int(flags), int(max_pairs),
-                                          points_ptr or None, clearance_ptr or None, count_ptr or None, stream or None),
-              "snk_closest_points")
+        self._call("snk_closest_points", ids_ptr, int(n_rows), float(distance), int(flags), int(max_pairs), points_ptr,
+                   clearance_ptr, count_ptr, stream)
 
     def closest_points(self, distance, env_ids=None, flags=PAIRS_BOX | PAIRS_LINKS, max_pairs=None):
         """snk_closest_points_host: (points [k, 2n + max_pairs, 16] float32, clearance [k, 2, 2n] float32, count [k, 2]
@@ -753,26 +740,25 @@ class Stepper:
         pair).  A record is [point on cylinder a 3 | point on B 3 | normal on B 3 | distance | tier | 0 | a | b (2n: the
         box) | live | 0]; clearance is min(found distances, distance) per cylinder for the box (row 0) and the other links
         (row 1); count = (box pairs, link-link pairs) found, the latter not clipped to max_pairs."""
-        ids, k, idp = self._ids(env_ids)
+        idp, k = self._ids(env_ids)
         mp = self.link_pairs if max_pairs is None else int(max_pairs)
         ok = 0 <= mp <= 4096                                      # (the library refuses the rest by name; no huge buffers first)
         points = np.zeros((max(k, 1), 2 * self.n + (mp if ok else 0), CONTACT_FLOATS), np.float32)
         clearance = np.zeros((max(k, 1), 2, 2 * self.n), np.float32)
         count = np.zeros((max(k, 1), 2), np.int32)
-        check(self.lib.snk_closest_points_host(self.h, idp, k, float(distance), int(flags), mp, fptr(points), fptr(clearance),
-                                               count.ctypes.data_as(_I32)), "snk_closest_points_host")
+        self._call("snk_closest_points_host", idp, k, float(distance), int(flags), mp, _ptr(points), _ptr(clearance),
+                   _ptr(count))
         return points, clearance, count
 
     def copy_envs(self, src, dst, reset_pose=False):
         """snk_copy_envs_host: env dst[i] becomes env src[i] in everything a Snapshot holds (the reset pose only with
         reset_pose=True).  Refused with the index, nothing written: an id outside the handle, a repeated dst, a dst
         that is also a src."""
-        s = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
-        d = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1)
+        s = _host(src, np.int32, None, "src", flat=True)
+        d = _host(dst, np.int32, None, "dst", flat=True)
         if len(s) != len(d):
             raise ValueError("src and dst must name as many envs each, got %d and %d" % (len(s), len(d)))
-        check(self.lib.snk_copy_envs_host(self.h, s.ctypes.data_as(_I32), d.ctypes.data_as(_I32), len(s),
-                                          COPY_RESET_POSE if reset_pose else 0), "snk_copy_envs_host")
+        self._call("snk_copy_envs_host", _ptr(s), _ptr(d), len(s), COPY_RESET_POSE if reset_pose else 0)
 
     @staticmethod
     def link_inertial_offsets(n_modules=16, **params):
@@ -784,24 +770,22 @@ class Stepper:
         """snk_render_host: images of the envs `env_ids` (None: all; ids may repeat, any order) from their current state.
         view / proj: column-major 16-vectors, one pair shared by every image or [n_images, 16] each.  Returns
         (rgba [k, height, width, 4] uint8, depth [k, height, width] float32 or None, seg int32 primitive ids or None)."""
-        ids, k, idp = self._ids(env_ids)
+        idp, k = self._ids(env_ids)
         cams, shared = camera_block(view, proj, k)
         W, H = int(width), int(height)
         ok = 1 <= W <= 4096 and 1 <= H <= 4096 and k >= 1        # (the library refuses the rest by name; no huge buffers first)
         rgba = np.zeros((k, H, W, 4) if ok else (1,), np.uint8)
         dep = np.zeros((k, H, W), np.float32) if depth and ok else None
         sg = np.zeros((k, H, W), np.int32) if seg and ok else None
-        check(self.lib.snk_render_host(self.h, idp, k, fptr(cams), 1 if shared else 0, W, H, RENDER_SHADOW if shadow else 0,
-                                       rgba.ctypes.data_as(_U8), fptr(dep) if dep is not None else None,
-                                       sg.ctypes.data_as(_I32) if sg is not None else None), "snk_render_host")
+        self._call("snk_render_host", idp, k, _ptr(cams), 1 if shared else 0, W, H, RENDER_SHADOW if shadow else 0,
+                   _ptr(rgba), _ptr(dep), _ptr(sg))
         return rgba, dep, sg
 
     def render_device(self, ids_ptr, n_images, cams_ptr, shared, width, height, flags, rgba_ptr, depth_ptr=0, seg_ptr=0,
                       stream=0):
         """snk_render: every buffer a device pointer (0: none), asynchronous on `stream`."""
-        check(self.lib.snk_render(self.h, ids_ptr or None, int(n_images), cams_ptr or None, 1 if shared else 0, int(width),
-                                  int(height), int(flags), rgba_ptr or None, depth_ptr or None, seg_ptr or None,
-                                  stream or None), "snk_render")
+        self._call("snk_render", ids_ptr, int(n_images), cams_ptr, 1 if shared else 0, int(width), int(height), int(flags),
+                   rgba_ptr, depth_ptr, seg_ptr, stream)
 
     # ---- the ray test (snk_ray_test / snk_ray_test_host) ----
     def ray_test(self, rays, env_ids=None, parent_row=-1, flags=RAYS_ALL):
@@ -811,75 +795,62 @@ class Stepper:
         link's COM; PyBullet's parentLinkIndex L is row L + 1).  flags: RAYS_GROUND | RAYS_SNAKE | RAYS_BOX, what can be
         hit.  A record is [hit fraction | position 3 | outward normal 3 | primitive id: 0 ground, 1 + c cylinder c, 1 + 2n
         the box], world frame; a miss is [1, 0, 0, 0, 0, 0, 0, -1] (snk.h, "The ray test")."""
-        ids, k, idp = self._ids(env_ids)
-        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        idp, k = self._ids(env_ids)
+        rays = _host(rays, np.float32, None, "rays")
         if rays.ndim not in (2, 3) or rays.shape[-1] != RAY_FLOATS or (rays.ndim == 3 and rays.shape[0] != k):
             raise ValueError("rays must be [%d, n_rays, 6] or [n_rays, 6], got %s" % (k, rays.shape))
         shared = rays.ndim == 2
         R = int(rays.shape[-2])
         ok = k >= 1 and 1 <= R <= 65536 and k * R <= 1 << 28      # (the library refuses the rest by name; no huge buffers first)
         hits = np.zeros((k, R, HIT_FLOATS) if ok else (1,), np.float32)
-        check(self.lib.snk_ray_test_host(self.h, idp, k, fptr(rays) if rays.size else None, R, int(parent_row),
-                                         (int(flags) & ~RAYS_SHARED) | (RAYS_SHARED if shared else 0), fptr(hits)),
-              "snk_ray_test_host")
+        self._call("snk_ray_test_host", idp, k, _ptr(rays if rays.size else None), R, int(parent_row),
+                   (int(flags) & ~RAYS_SHARED) | (RAYS_SHARED if shared else 0), _ptr(hits))
         return hits
 
     def ray_test_device(self, ids_ptr, n_rows, rays_ptr, n_rays, parent_row, flags, hits_ptr, stream=0):
         """snk_ray_test: every buffer a device pointer (ids 0: envs 0 .. n_rows - 1), asynchronous on `stream`."""
-        check(self.lib.snk_ray_test(self.h, ids_ptr or None, int(n_rows), rays_ptr or None, int(n_rays), int(parent_row),
-                                    int(flags), hits_ptr or None, stream or None), "snk_ray_test")
+        self._call("snk_ray_test", ids_ptr, int(n_rows), rays_ptr, int(n_rays), int(parent_row), int(flags), hits_ptr, stream)
 
     # ---- the dynamics queries (snk_dynamics / snk_jacobians and their host forms) ----
     @property
     def dyn_dofs(self):
         """snk_dyn_dofs: nd = 6 + n, the components of u = [omega 3 | v of the root origin 3 | qd n]."""
-        k = int(self.lib.snk_dyn_dofs(self.h))
-        if k == 0:
-            raise RuntimeError("snk_dyn_dofs failed: %s" % last_error())
-        return k
+        return self._count("snk_dyn_dofs")
 
     def dynamics_device(self, ids_ptr, n_rows, flags, mass_ptr=0, bias_ptr=0, stream=0):
         """snk_dynamics: mass [n_rows, nd, nd] f32, bias [n_rows, nd] f32 (each a device pointer or 0) for the envs ids
         [n_rows] i32 (0: envs 0 .. n_rows - 1).  Asynchronous on `stream`."""
-        check(self.lib.snk_dynamics(self.h, ids_ptr or None, int(n_rows), int(flags), mass_ptr or None, bias_ptr or None,
-                                    stream or None), "snk_dynamics")
+        self._call("snk_dynamics", ids_ptr, int(n_rows), int(flags), mass_ptr, bias_ptr, stream)
 
     def dynamics(self, env_ids=None, flags=BIAS_VELOCITY | BIAS_GRAVITY, mass=True, bias=True):
         """snk_dynamics_host: (M [k, nd, nd] float32 or None, h [k, nd] float32 or None) of the envs `env_ids` (None: all;
         ids may repeat, any order) at the state they hold: M du/dt + h = Q over u = [omega 3 | v of the root origin 3 | qd
         n].  flags: BIAS_VELOCITY | BIAS_GRAVITY, the terms of h (snk.h, "The dynamics queries")."""
-        ids, k, idp = self._ids(env_ids)
+        idp, k = self._ids(env_ids)
         nd = self.n + 6
         M = np.zeros((max(k, 1), nd, nd), np.float32) if mass else None
         h = np.zeros((max(k, 1), nd), np.float32) if bias else None
-        check(self.lib.snk_dynamics_host(self.h, idp, k, int(flags), fptr(M) if mass else None, fptr(h) if bias else None),
-              "snk_dynamics_host")
+        self._call("snk_dynamics_host", idp, k, int(flags), _ptr(M), _ptr(h))
         return M, h
 
     def jacobians_device(self, ids_ptr, n_rows, link_rows_ptr, local_ptr, n_points, jac_ptr, stream=0):
         """snk_jacobians: jac [n_rows, n_points, 6, nd] f32 for the links link_rows [n_points] i32 (rows of link_states) and
         the points local [n_points, 3] f32 in their COM frames (0: the COMs); every buffer a device pointer.  Asynchronous on
         `stream`."""
-        check(self.lib.snk_jacobians(self.h, ids_ptr or None, int(n_rows), link_rows_ptr or None, local_ptr or None,
-                                     int(n_points), jac_ptr or None, stream or None), "snk_jacobians")
+        self._call("snk_jacobians", ids_ptr, int(n_rows), link_rows_ptr, local_ptr, int(n_points), jac_ptr, stream)
 
     def jacobians(self, link_rows, local=None, env_ids=None):
         """snk_jacobians_host: [k, n_points, 6, nd] float32 of the envs `env_ids` (None: all; ids may repeat, any order):
         per point rows 0-2 the world linear velocity per unit of each component of u, rows 3-5 the link's angular velocity.
         link_rows: rows of link_states (Bullet link + 1), one list for every env; local: [n_points, 3] points in the links'
         COM frames (None: the COMs)."""
-        ids, k, idp = self._ids(env_ids)
-        rows = np.ascontiguousarray(link_rows, dtype=np.int32).reshape(-1)
+        idp, k = self._ids(env_ids)
+        rows = _host(link_rows, np.int32, None, "link_rows", flat=True)
         P = len(rows)
-        loc = None
-        if local is not None:
-            loc = np.ascontiguousarray(local, dtype=np.float32)
-            if loc.shape != (P, 3):
-                raise ValueError("local must be [%d, 3], got %s" % (P, loc.shape))
+        loc = _host(local, np.float32, (P, 3), "local", "local must be [%d, 3]" % P, optional=True)
         ok = 1 <= P <= JAC_MAX_POINTS                         # (the library refuses the rest by name; no huge buffers first)
         jac = np.zeros((max(k, 1), P, 6, self.n + 6) if ok else (1,), np.float32)
-        check(self.lib.snk_jacobians_host(self.h, idp, k, rows.ctypes.data_as(_I32) if P else None,
-                                          fptr(loc) if loc is not None else None, P, fptr(jac)), "snk_jacobians_host")
+        self._call("snk_jacobians_host", idp, k, _ptr(rows if P else None), _ptr(loc), P, _ptr(jac))
         return jac
 
     # ---- the applied forces (snk_apply_impulse and its host form) ----
@@ -888,9 +859,8 @@ class Stepper:
         """snk_apply_impulse: u += seconds x M^-1 Q for the envs whose byte of active [n_envs] u8 is non-zero (0: all), Q =
         gen_force [n_envs, nd] f32 + the wrenches [n_envs, n_points, 9] f32 on the links link_rows [n_points] i32; delta
         [n_envs, nd] f32.  Every buffer a device pointer or 0.  Asynchronous on `stream`."""
-        check(self.lib.snk_apply_impulse(self.h, active_ptr or None, gen_force_ptr or None, link_rows_ptr or None,
-                                         wrench_ptr or None, int(n_points), int(flags), float(seconds), delta_ptr or None,
-                                         stream or None), "snk_apply_impulse")
+        self._call("snk_apply_impulse", active_ptr, gen_force_ptr, link_rows_ptr, wrench_ptr, int(n_points), int(flags),
+                   float(seconds), delta_ptr, stream)
 
     def apply_impulse(self, gen_force=None, link_rows=None, wrenches=None, flags=0, seconds=None, active=None):
         """snk_apply_impulse_host: the velocity of the active envs (active [n_envs] bool / uint8; None: all) becomes u +
@@ -900,38 +870,25 @@ class Stepper:
         env), in world axes at a world point, or with IMPULSE_LINK_FRAME in the link's COM frame.  seconds None: the
         handle's dt as the kernels hold it (snk.h, "The applied forces")."""
         nd = self.n + 6
-        gf = None
-        if gen_force is not None:
-            gf = np.ascontiguousarray(gen_force, dtype=np.float32)
-            if gf.shape != (self.n_envs, nd):
-                raise ValueError("gen_force must be [%d, %d], got %s" % (self.n_envs, nd, gf.shape))
-        rows = np.zeros(0, np.int32) if link_rows is None else np.ascontiguousarray(link_rows, dtype=np.int32).reshape(-1)
+        E = self.n_envs
+        gf = _host(gen_force, np.float32, (E, nd), "gen_force", "gen_force must be [%d, %d]" % (E, nd), optional=True)
+        rows = _host([] if link_rows is None else link_rows, np.int32, None, "link_rows", flat=True)
         P = len(rows)
-        wr = None
-        if P or wrenches is not None:
-            if wrenches is None:
-                raise ValueError("link_rows without wrenches")
-            wr = np.ascontiguousarray(wrenches, dtype=np.float32)
-            if wr.shape != (self.n_envs, P, WRENCH_FLOATS):
-                raise ValueError("wrenches must be [%d, %d, %d], got %s" % (self.n_envs, P, WRENCH_FLOATS, wr.shape))
-        act = None
-        if active is not None:
-            act = np.ascontiguousarray(active).astype(np.uint8).reshape(-1)
-            if act.shape != (self.n_envs,):
-                raise ValueError("active must be [%d], got %s" % (self.n_envs, act.shape))
-        delta = np.zeros((self.n_envs, nd), np.float32)
-        check(self.lib.snk_apply_impulse_host(self.h, act.ctypes.data_as(_U8) if act is not None else None,
-                                              fptr(gf) if gf is not None else None, rows.ctypes.data_as(_I32) if P else None,
-                                              fptr(wr) if wr is not None and P else None, P, int(flags),
-                                              float(np.float32(self.params.dt)) if seconds is None else float(seconds),
-                                              fptr(delta)), "snk_apply_impulse_host")
+        if P and wrenches is None:
+            raise ValueError("link_rows without wrenches")
+        wr = _host(wrenches, np.float32, (E, P, WRENCH_FLOATS), "wrenches",
+                   "wrenches must be [%d, %d, %d]" % (E, P, WRENCH_FLOATS), optional=True)
+        act = _host(active, np.uint8, (E,), "active", "active must be [%d]" % E, optional=True, flat=True)
+        delta = self._zeros(nd)
+        self._call("snk_apply_impulse_host", _ptr(act), _ptr(gf), _ptr(rows if P else None), _ptr(wr if P else None), P,
+                   int(flags), float(np.float32(self.params.dt)) if seconds is None else float(seconds), _ptr(delta))
         return delta
 
     def timing_enable(self, capacity):
-        check(self.lib.snk_timing_enable(self.h, int(capacity)), "snk_timing_enable")
+        self._call("snk_timing_enable", int(capacity))
 
     def timing_read(self):
         ms = C.c_double()
         cnt = C.c_int32()
-        check(self.lib.snk_timing_read(self.h, C.byref(ms), C.byref(cnt)), "snk_timing_read")
+        self._call("snk_timing_read", C.byref(ms), C.byref(cnt))
         return ms.value, cnt.value

@@ -30,17 +30,30 @@ class _TensorArgs(object):
     def _stream(self):
         return self.torch.cuda.current_stream(self.device).cuda_stream
 
-    def _arg(self, x, what, dtypes, shape):
-        """a caller's tensor as the kernels read it: on this device, of one of `dtypes`, of `shape`, contiguous"""
+    def _arg(self, x, what, dtypes, shape, optional=False, more=None, flat=False):
+        """A caller's tensor as the kernels read it: on this device, of one of `dtypes`, of `shape`, contiguous -- THE
+        check between a caller's tensor and what a kernel reads and writes, raised (_lib._ArgError), never an `assert`.
+        optional: None stays None, an absent argument; more = (d, "rows"): dimension d may be larger than asked (the
+        kernel is told its size); flat: any shape of as many elements."""
         t = self.torch
+        if x is None and optional:
+            return None
         if not isinstance(x, t.Tensor) or not x.is_cuda or x.device != self.device:
-            raise ValueError("%s must be a CUDA tensor on %s" % (what, self.device))
+            raise _lib._ArgError("%s must be a CUDA tensor on %s" % (what, self.device))
         if x.dtype not in dtypes:
-            raise ValueError("%s must be %s, got %s" % (what, " or ".join(str(d) for d in dtypes), x.dtype))
-        if tuple(x.shape) != tuple(shape):
-            raise ValueError("%s must have shape %s, got %s" % (what, tuple(shape), tuple(x.shape)))
+            raise _lib._ArgError("%s must be %s, got %s" % (what, " or ".join(str(d) for d in dtypes), x.dtype))
+        got, want = tuple(x.shape), tuple(shape)
+        if got != want:
+            if flat:
+                fits = x.numel() == int(np.prod(want))
+            else:
+                d = more[0] if more else 0
+                fits = more and len(got) == len(want) and got[d] > want[d] and got[:d] + got[d + 1:] == want[:d] + want[d + 1:]
+            if not fits:
+                raise _lib._ArgError("%s must have shape %s%s, got %s" % (what, want, " (or more %s)" % more[1] if more else
+                                                                         " (or as many elements)" if flat else "", got))
         if not x.is_contiguous():
-            raise ValueError("%s must be contiguous" % what)
+            raise _lib._ArgError("%s must be contiguous" % what)
         return x
 
     def _out(self, out, what, shape, dtype=None):
@@ -49,6 +62,24 @@ class _TensorArgs(object):
         if out is None:
             return t.empty(shape, dtype=dtype, device=self.device)
         return self._arg(out, what, (dtype,), shape)
+
+    def _want(self, spec, shape, dtype=None):
+        """_out of an output a query may leave out: spec is None (not wanted) or (its name in a message, the caller's
+        tensor or None for a fresh one)"""
+        return None if spec is None else self._out(spec[1], spec[0], shape, dtype)
+
+    @staticmethod
+    def _ptr(x):
+        """a tensor's device pointer; 0, the kernels' NULL, for an absent one"""
+        return 0 if x is None else x.data_ptr()
+
+    def _reset_pose_dev(self, pose, mask):
+        """snk_set_reset_pose_dev on the current stream: pose [E, 7 + n] float32, mask uint8 / bool [E] or None"""
+        t = self.torch
+        pose = self._arg(pose, "pose", (t.float32,), (self.num_envs, 7 + self.stepper.n))
+        mask = self._arg(mask, "mask", (t.uint8, t.bool), (self.num_envs,), optional=True)   # (a bool is one byte, 0 / 1)
+        self.stepper.set_reset_pose_device(pose.data_ptr(), self._ptr(mask), self._stream())
+        self._keep(pose, mask)
 
     def _keep(self, *tensors):
         """the kernels read these when the stream gets there: they stay alive until then"""
@@ -94,9 +125,7 @@ class DeviceVecEnv(_TensorArgs):
         log, say: a rollout can then look at the counts after its last step instead of reducing them after every one)"""
         if substeps is None:
             return self.substeps.data_ptr()
-        t = self.torch
-        assert substeps.is_cuda and substeps.dtype == t.int32 and substeps.is_contiguous() and substeps.numel() == self.num_envs
-        return substeps.data_ptr()
+        return self._arg(substeps, "substeps", (self.torch.int32,), (self.num_envs,), flat=True).data_ptr()
 
     def trace_shape(self):
         """Shape of the float32 CUDA tensor step(trace=...) fills: [E, max_counter + 1, floats per row]."""
@@ -104,46 +133,31 @@ class DeviceVecEnv(_TensorArgs):
 
     def _trace_ptr(self, trace):
         """a caller-owned trace tensor (trace_shape(); more rows are allowed, the kernel leaves them alone)"""
-        t = self.torch
-        want = self.trace_shape()
-        if not isinstance(trace, t.Tensor) or not trace.is_cuda or trace.device != self.device:
-            raise ValueError("trace must be a CUDA tensor on %s" % (self.device,))
-        if trace.dtype != t.float32:
-            raise ValueError("trace must be float32, got %s" % (trace.dtype,))
-        if trace.dim() != 3 or trace.shape[0] != want[0] or trace.shape[1] < want[1] or trace.shape[2] != want[2]:
-            raise ValueError("trace must have shape %s (or more rows), got %s" % (want, tuple(trace.shape)))
-        if not trace.is_contiguous():
-            raise ValueError("trace must be contiguous")
-        return trace.data_ptr()
+        return self._arg(trace, "trace", (self.torch.float32,), self.trace_shape(), more=(1, "rows")).data_ptr()
+
+    def _actions_ptr(self, actions):
+        return self._arg(actions, "actions", (self.torch.float32,), (self.num_envs, self.act_dim)).data_ptr()
 
     def step(self, actions, vec_mode=True, substeps=None, trace=None):
         """actions: float32 CUDA tensor [E, A], contiguous; clipped in place.  Asynchronous.
         trace: a float32 CUDA tensor of trace_shape(): the step kernel then also writes row s of env e after its physics
         substep s, [obs | link positions | padding] (snk_step_traced); rows at and beyond the env's substep count (in
         self.substeps, or `substeps`) are not touched."""
-        t = self.torch
-        assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous()
-        assert tuple(actions.shape) == (self.num_envs, self.act_dim)
+        out = (self._actions_ptr(actions), self.obs.data_ptr(), self.rew.data_ptr(), self.done.data_ptr(),
+               self._sub_ptr(substeps))
         if trace is not None:
-            self.stepper.step_traced_device(actions.data_ptr(), self.obs.data_ptr(), self.rew.data_ptr(),
-                                            self.done.data_ptr(), self._sub_ptr(substeps), self._trace_ptr(trace),
-                                            trace.shape[1], vec_mode, self._stream())
-            return self.obs, self.rew, self.done
-        self.stepper.step_device(actions.data_ptr(), self.obs.data_ptr(), self.rew.data_ptr(),
-                                 self.done.data_ptr(), self._sub_ptr(substeps), vec_mode, self._stream())
+            self.stepper.step_traced_device(*out, self._trace_ptr(trace), trace.shape[1], vec_mode, self._stream())
+        else:
+            self.stepper.step_device(*out, vec_mode, self._stream())
         return self.obs, self.rew, self.done
 
     def step_packed(self, actions, packed, vec_mode=True, substeps=None):
         """The same step, written by the kernel as rows [obs | reward | done] of `packed` ([E, >= O + 2] float32 on this
         device; the done cell holds the integer 0 / 1): the block a sharded env gathers (snk_step_packed).  self.obs /
         rew / done are NOT updated by this call.  Asynchronous."""
-        t = self.torch
-        assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous()
-        assert tuple(actions.shape) == (self.num_envs, self.act_dim)
-        assert packed.is_cuda and packed.dtype == t.float32 and packed.is_contiguous()
-        assert packed.shape[0] == self.num_envs and packed.shape[1] >= self.obs_dim + 2
-        self.stepper.step_packed_device(actions.data_ptr(), packed.data_ptr(), packed.shape[1], self._sub_ptr(substeps),
-                                        vec_mode, self._stream())
+        self._arg(packed, "packed", (self.torch.float32,), (self.num_envs, self.obs_dim + 2), more=(1, "columns"))
+        self.stepper.step_packed_device(self._actions_ptr(actions), packed.data_ptr(), packed.shape[1],
+                                        self._sub_ptr(substeps), vec_mode, self._stream())
         return packed
 
     def set_ground_friction(self, mu):
@@ -173,9 +187,8 @@ class DeviceVecEnv(_TensorArgs):
         rgba = t.empty((k, H, W, 4) if ok else (4,), dtype=t.uint8, device=self.device)
         dep = t.empty((k, H, W), dtype=t.float32, device=self.device) if depth and ok else None
         sg = t.empty((k, H, W), dtype=t.int32, device=self.device) if seg and ok else None
-        self.stepper.render_device(ids.data_ptr() if ids is not None else 0, k, cams.data_ptr(), v.shape[0] == 1, W, H,
-                                   _lib.RENDER_SHADOW if shadow else 0, rgba.data_ptr(),
-                                   dep.data_ptr() if dep is not None else 0, sg.data_ptr() if sg is not None else 0,
+        self.stepper.render_device(self._ptr(ids), k, cams.data_ptr(), v.shape[0] == 1, W, H,
+                                   _lib.RENDER_SHADOW if shadow else 0, rgba.data_ptr(), self._ptr(dep), self._ptr(sg),
                                    self._stream())
         self._keep(ids, cams)
         return rgba, dep, sg
@@ -188,26 +201,9 @@ class DeviceVecEnv(_TensorArgs):
         nothing validated.  Anything else (ndarray, list, CPU tensor) goes through the host form, which synchronises and
         refuses non-finite values and non-unit quaternions."""
         t = self.torch
-        W = 7 + self.stepper.n
         if isinstance(pose, t.Tensor) and pose.is_cuda:
-            if pose.device != self.device or pose.dtype != t.float32 or tuple(pose.shape) != (self.num_envs, W):
-                raise ValueError("reset pose must be a float32 tensor of shape (%d, %d) on %s, got %s %s on %s"
-                                 % (self.num_envs, W, self.device, pose.dtype, tuple(pose.shape), pose.device))
-            pose = pose.contiguous()
-            mptr = 0
-            if mask is not None:
-                if not isinstance(mask, t.Tensor) or mask.device != self.device or tuple(mask.shape) != (self.num_envs,) \
-                        or mask.dtype not in (t.uint8, t.bool):
-                    raise ValueError("with a CUDA pose the mask must be a uint8 or bool tensor of shape (%d,) on %s"
-                                     % (self.num_envs, self.device))
-                mask = mask.contiguous()
-                mptr = mask.data_ptr()          # (a bool tensor is one byte per element, 0 / 1)
-            self.stepper.set_reset_pose_device(pose.data_ptr(), mptr, self._stream())
-            # the copy kernel reads `pose` / `mask` when the stream gets there: they stay alive until then
-            pose.record_stream(t.cuda.current_stream(self.device))
-            if mptr:
-                mask.record_stream(t.cuda.current_stream(self.device))
-            return
+            # (this form takes strided views too: the copy kernel reads their contiguous copies)
+            return self._reset_pose_dev(pose.contiguous(), mask.contiguous() if isinstance(mask, t.Tensor) else mask)
         if isinstance(pose, t.Tensor):
             pose = pose.numpy()
         if isinstance(mask, t.Tensor):
@@ -263,33 +259,31 @@ class DeviceWorld(_TensorArgs):
         rows of inactive envs are left alone."""
         t = self.torch
         targets = self._arg(targets, "targets", (t.float32,), (self.num_envs, self.n))
-        if active is not None:
-            active = self._arg(active, "active", (t.uint8, t.bool), (self.num_envs,))     # (a bool is one byte, 0 / 1)
-        if info is not None:
-            info = self._arg(info, "info", (t.int32,), (self.num_envs, 2))
+        active = self._arg(active, "active", (t.uint8, t.bool), (self.num_envs,), optional=True)   # (a bool is one byte, 0 / 1)
+        info = self._arg(info, "info", (t.int32,), (self.num_envs, 2), optional=True)
         if int(k) < 0:
             raise ValueError("k must not be negative, got %d" % int(k))
-        self.stepper.substep_device(targets.data_ptr(), int(k), active.data_ptr() if active is not None else 0,
-                                    info.data_ptr() if info is not None else 0, self._stream())
+        self.stepper.substep_device(targets.data_ptr(), int(k), self._ptr(active), self._ptr(info), self._stream())
         self._keep(targets, active)
+
+    def _observe(self, which, out):
+        """One snk_observe read-out, [E, ...] float32: `which` is observe_device's name of it."""
+        row = {"obs_ptr": (self.obs_dim,), "height_ptr": (), "linkpos_ptr": (3 * (self.n + 1),)}[which]
+        out = self._out(out, "out", (self.num_envs,) + row)
+        self.stepper.observe_device(stream=self._stream(), **{which: out.data_ptr()})
+        return out
 
     def observation(self, out=None):
         """getObservation (snake.py:209-217) of every env: [E, 3n + 8] float32."""
-        out = self._out(out, "out", (self.num_envs, self.obs_dim))
-        self.stepper.observe_device(obs_ptr=out.data_ptr(), stream=self._stream())
-        return out
+        return self._observe("obs_ptr", out)
 
     def mean_height(self, out=None):
         """checkSnakeHeight's mean z (snake.py:237-245) of every env: [E] float32."""
-        out = self._out(out, "out", (self.num_envs,))
-        self.stepper.observe_device(height_ptr=out.data_ptr(), stream=self._stream())
-        return out
+        return self._observe("height_ptr", out)
 
     def link_positions(self, out=None):
         """getLinkPositions (snake.py:138-146) of every env: [E, 3(n + 1)] float32, [x.., y.., z..] of links 0, 3, .., 3n."""
-        out = self._out(out, "out", (self.num_envs, 3 * (self.n + 1)))
-        self.stepper.observe_device(linkpos_ptr=out.data_ptr(), stream=self._stream())
-        return out
+        return self._observe("linkpos_ptr", out)
 
     def link_states(self, env_ids=None, out=None):
         """[k, 3n + 2, 16] float32: getLinkState(computeLinkVelocity=1) of every link of the envs `env_ids` (None: all;
@@ -298,7 +292,7 @@ class DeviceWorld(_TensorArgs):
         3 | angular velocity 3], world frame."""
         ids, k = self._ids(env_ids)
         out = self._out(out, "out", (k, self.link_rows, _lib.LINK_STATE_FLOATS))
-        self.stepper.link_states_device(ids.data_ptr() if ids is not None else 0, k, out.data_ptr(), self._stream())
+        self.stepper.link_states_device(self._ptr(ids), k, out.data_ptr(), self._stream())
         self._keep(ids)
         return out
 
@@ -309,23 +303,24 @@ class DeviceWorld(_TensorArgs):
         contract).  Slot 4 c + j is cached point j of cylinder c, the last four of an obstacle 2 world the free box's; a
         slot is [point on the body 3 | point on the ground 3 | normal 3 | distance | normal force N | impulse | c (2n: the
         box) | j | live | 0], zeros when not live.  out: a (points, force, count) tuple of tensors to write into."""
-        t = self.torch
-        ids, k = self._ids(env_ids)
         po, fo, co = (None, None, None) if out is None else out
-        points = self._out(po, "out[0]", (k, self.stepper.contact_slots, _lib.CONTACT_FLOATS))
-        force = self._out(fo, "out[1]", (k, 2 * self.n + 1))
-        count = self._out(co, "out[2]", (k,), t.int32)
-        self.stepper.contacts_device(ids.data_ptr() if ids is not None else 0, k, points.data_ptr(), force.data_ptr(),
-                                     count.data_ptr(), self._stream())
+        return self._contacts(env_ids, ("out[0]", po), ("out[1]", fo), ("out[2]", co))
+
+    def _contacts(self, env_ids, points=None, force=None, count=None):
+        """One snk_contacts launch for the outputs wanted (_want)."""
+        ids, k = self._ids(env_ids)
+        # (contact_slots is asked only with the records: contact_forces leaves a contact_model 0 handle to snk_contacts' refusal)
+        points = points and self._want(points, (k, self.stepper.contact_slots, _lib.CONTACT_FLOATS))
+        force = self._want(force, (k, 2 * self.n + 1))
+        count = self._want(count, (k,), self.torch.int32)
+        self.stepper.contacts_device(self._ptr(ids), k, self._ptr(points), self._ptr(force), self._ptr(count), self._stream())
         self._keep(ids)
         return points, force, count
 
     def contact_forces(self, out=None):
         """[E, 2n + 1] float32: the normal force of the ground on every cylinder of every env, in newtons (entry 2n: on
         the free box, 0 without one) -- the touch / ground-reaction term of a reward written over step_simulation."""
-        out = self._out(out, "out", (self.num_envs, 2 * self.n + 1))
-        self.stepper.contacts_device(0, self.num_envs, force_ptr=out.data_ptr(), stream=self._stream())
-        return out
+        return self._contacts(None, force=("out", out))[1]
 
     def closest_points(self, distance, env_ids=None, flags=_lib.PAIRS_BOX | _lib.PAIRS_LINKS, max_pairs=64, out=None):
         """(points [k, 2n + max_pairs, 16] float32, clearance [k, 2, 2n] float32, count [k, 2] int32): PyBullet's
@@ -336,14 +331,17 @@ class DeviceWorld(_TensorArgs):
         `max_pairs` of them.  A slot is [point on cylinder a 3 | point on B 3 | normal on B 3 | distance | tier | 0 | a |
         b (2n: the box) | live | 0], zeros when not live; count[:, 1] is not clipped to max_pairs.  out: a (points,
         clearance, count) tuple of tensors to write into."""
-        t = self.torch
-        ids, k = self._ids(env_ids)
         po, co, no = (None, None, None) if out is None else out
-        points = self._out(po, "out[0]", (k, self.stepper.closest_slots(max_pairs), _lib.CONTACT_FLOATS))
-        clearance = self._out(co, "out[1]", (k, 2, 2 * self.n))
-        count = self._out(no, "out[2]", (k, 2), t.int32)
-        self.stepper.closest_points_device(ids.data_ptr() if ids is not None else 0, k, distance, flags, max_pairs,
-                                           points.data_ptr(), clearance.data_ptr(), count.data_ptr(), self._stream())
+        return self._closest(distance, env_ids, flags, max_pairs, ("out[0]", po), ("out[1]", co), ("out[2]", no))
+
+    def _closest(self, distance, env_ids, flags, max_pairs, points=None, clearance=None, count=None):
+        """One snk_closest_points launch for the outputs wanted (_want)."""
+        ids, k = self._ids(env_ids)
+        points = points and self._want(points, (k, self.stepper.closest_slots(max_pairs), _lib.CONTACT_FLOATS))
+        clearance = self._want(clearance, (k, 2, 2 * self.n))
+        count = self._want(count, (k, 2), self.torch.int32)
+        self.stepper.closest_points_device(self._ptr(ids), k, distance, flags, max_pairs, self._ptr(points),
+                                           self._ptr(clearance), self._ptr(count), self._stream())
         self._keep(ids)
         return points, clearance, count
 
@@ -351,10 +349,7 @@ class DeviceWorld(_TensorArgs):
         """[E, 2, 2n] float32: per cylinder of every env its distance to the box (row 0) and to the nearest other link it
         forms a pair with (row 1), each min(found distances, distance) -- `distance` reads "nothing within reach".  The
         proximity term of a reward written over step_simulation; no records are written."""
-        out = self._out(out, "out", (self.num_envs, 2, 2 * self.n))
-        self.stepper.closest_points_device(0, self.num_envs, distance, flags, 0, clearance_ptr=out.data_ptr(),
-                                           stream=self._stream())
-        return out
+        return self._closest(distance, None, flags, 0, clearance=("out", out))[1]
 
     def ray_test(self, rays, env_ids=None, parent_row=-1, flags=_lib.RAYS_ALL, out=None):
         """[k, R, 8] float32: PyBullet's rayTestBatch for the envs `env_ids` (None: all; an int32 CUDA tensor or a sequence;
@@ -372,7 +367,7 @@ class DeviceWorld(_TensorArgs):
         R = int(rays.shape[-2])
         rays = self._arg(rays, "rays", (t.float32,), (R, _lib.RAY_FLOATS) if shared else (k, R, _lib.RAY_FLOATS))
         out = self._out(out, "out", (k, R, _lib.HIT_FLOATS))
-        self.stepper.ray_test_device(ids.data_ptr() if ids is not None else 0, k, rays.data_ptr(), R, parent_row,
+        self.stepper.ray_test_device(self._ptr(ids), k, rays.data_ptr(), R, parent_row,
                                      (int(flags) & ~_lib.RAYS_SHARED) | (_lib.RAYS_SHARED if shared else 0), out.data_ptr(),
                                      self._stream())
         self._keep(ids, rays)
@@ -390,13 +385,16 @@ class DeviceWorld(_TensorArgs):
         zeros) at the state they hold, by one launch (snk_dynamics; include/snk.h has the contract): M du/dt + h = Q over
         u = [omega 3 | v of the root origin 3 | qd n] -- PyBullet's calculateMassMatrix and calculateInverseDynamics(q, qd,
         0).  gravity / velocity: the terms of h.  out: an (M, h) tuple of tensors to write into."""
+        mo, ho = (None, None) if out is None else out
+        return self._dynamics(env_ids, self._bias_flags(gravity, velocity), ("out[0]", mo), ("out[1]", ho))
+
+    def _dynamics(self, env_ids, flags, M=None, h=None):
+        """One snk_dynamics launch for the outputs wanted (_want)."""
         ids, k = self._ids(env_ids)
         nd = self.n + 6
-        mo, ho = (None, None) if out is None else out
-        M = self._out(mo, "out[0]", (k, nd, nd))
-        h = self._out(ho, "out[1]", (k, nd))
-        self.stepper.dynamics_device(ids.data_ptr() if ids is not None else 0, k, self._bias_flags(gravity, velocity),
-                                     M.data_ptr(), h.data_ptr(), self._stream())
+        M = self._want(M, (k, nd, nd))
+        h = self._want(h, (k, nd))
+        self.stepper.dynamics_device(self._ptr(ids), k, flags, self._ptr(M), self._ptr(h), self._stream())
         self._keep(ids)
         return M, h
 
@@ -410,24 +408,13 @@ class DeviceWorld(_TensorArgs):
     def mass_matrix(self, env_ids=None, out=None):
         """[k, nd, nd] float32: M(q) alone (dynamics' first output), symmetric bit for bit; 1/2 u^T M u is the kinetic
         energy."""
-        ids, k = self._ids(env_ids)
-        nd = self.n + 6
-        out = self._out(out, "out", (k, nd, nd))
-        self.stepper.dynamics_device(ids.data_ptr() if ids is not None else 0, k, _lib.BIAS_VELOCITY | _lib.BIAS_GRAVITY,
-                                     mass_ptr=out.data_ptr(), stream=self._stream())
-        self._keep(ids)
-        return out
+        return self._dynamics(env_ids, _lib.BIAS_VELOCITY | _lib.BIAS_GRAVITY, M=("out", out))[0]
 
     def bias_forces(self, env_ids=None, gravity=True, velocity=True, out=None):
         """[k, nd] float32: h alone (dynamics' second output): the Coriolis, centrifugal and gyroscopic forces at the
         state's u (`velocity`) minus the generalised gravity force (`gravity`); gravity alone is what a controller adds to
         hold the pose.  Rigid bodies only: none of the integrator's damping."""
-        ids, k = self._ids(env_ids)
-        out = self._out(out, "out", (k, self.n + 6))
-        self.stepper.dynamics_device(ids.data_ptr() if ids is not None else 0, k, self._bias_flags(gravity, velocity),
-                                     bias_ptr=out.data_ptr(), stream=self._stream())
-        self._keep(ids)
-        return out
+        return self._dynamics(env_ids, self._bias_flags(gravity, velocity), h=("out", out))[1]
 
     def jacobians(self, link_rows, local=None, env_ids=None, out=None):
         """[k, P, 6, nd] float32: PyBullet's calculateJacobian for P points of the envs `env_ids` (None: all; an int32 CUDA
@@ -452,8 +439,7 @@ class DeviceWorld(_TensorArgs):
                 raise ValueError("local must have shape %s, got %s" % ((P, 3), tuple(loc.shape)))
             loc = loc.contiguous()
         out = self._out(out, "out", (k, P, 6, self.n + 6))
-        self.stepper.jacobians_device(ids.data_ptr() if ids is not None else 0, k, rows.data_ptr(),
-                                      loc.data_ptr() if loc is not None else 0, P, out.data_ptr(), self._stream())
+        self.stepper.jacobians_device(self._ptr(ids), k, rows.data_ptr(), self._ptr(loc), P, out.data_ptr(), self._stream())
         self._keep(ids, rows, loc)
         return out
 
@@ -475,8 +461,7 @@ class DeviceWorld(_TensorArgs):
         nd = self.n + 6
         if frame not in ("world", "link"):
             raise ValueError("frame must be 'world' or 'link', got %r" % (frame,))
-        if gen_force is not None:
-            gen_force = self._arg(gen_force, "gen_force", (t.float32,), (self.num_envs, nd))
+        gen_force = self._arg(gen_force, "gen_force", (t.float32,), (self.num_envs, nd), optional=True)
         rows = None
         P = 0
         if link_rows is not None:
@@ -490,16 +475,14 @@ class DeviceWorld(_TensorArgs):
             wrenches = self._arg(wrenches, "wrenches", (t.float32,), (self.num_envs, P, _lib.WRENCH_FLOATS))
         if gen_force is None and P == 0:
             raise ValueError("nothing to apply: neither gen_force nor wrenches")
-        if active is not None:
-            active = self._arg(active, "active", (t.uint8, t.bool), (self.num_envs,))
+        active = self._arg(active, "active", (t.uint8, t.bool), (self.num_envs,), optional=True)
         if dry or out is not None:
             out = self._out(out, "out", (self.num_envs, nd))
         seconds = float(np.float32(self.params.dt)) if duration is None else float(duration)
         flags = (_lib.IMPULSE_LINK_FRAME if frame == "link" else 0) | (_lib.IMPULSE_DRY if dry else 0)
-        self.stepper.apply_impulse_device(active.data_ptr() if active is not None else 0,
-                                          gen_force.data_ptr() if gen_force is not None else 0,
-                                          rows.data_ptr() if P else 0, wrenches.data_ptr() if P else 0, P, flags, seconds,
-                                          out.data_ptr() if out is not None else 0, self._stream())
+        self.stepper.apply_impulse_device(self._ptr(active), self._ptr(gen_force), self._ptr(rows if P else None),
+                                          self._ptr(wrenches if P else None), P, flags, seconds, self._ptr(out),
+                                          self._stream())
         self._keep(active, gen_force, rows, wrenches)
         return out
 
@@ -514,25 +497,19 @@ class DeviceWorld(_TensorArgs):
         of the reset-pose table.  Returns the observations [E, 3n + 8]; rows of unmasked envs are left as `out` had them
         (zeros for a fresh tensor)."""
         t = self.torch
-        if mask is not None:
-            mask = self._arg(mask, "mask", (t.uint8, t.bool), (self.num_envs,))
+        mask = self._arg(mask, "mask", (t.uint8, t.bool), (self.num_envs,), optional=True)
         if out is None:
             out = t.zeros((self.num_envs, self.obs_dim), dtype=t.float32, device=self.device)
         else:
             out = self._arg(out, "out", (t.float32,), (self.num_envs, self.obs_dim))
-        self.stepper.reset_device(mask.data_ptr() if mask is not None else 0, out.data_ptr(), self._stream())
+        self.stepper.reset_device(self._ptr(mask), out.data_ptr(), self._stream())
         self._keep(mask)
         return out
 
     def set_reset_pose(self, pose, mask=None):
         """Rows [position 3 | quaternion xyzw 4 | joint angles n] of the reset-pose table from CUDA tensors (pose [E, 7 +
         n] float32, mask uint8 / bool [E] or None): snk_set_reset_pose_dev on the current stream, nothing validated."""
-        t = self.torch
-        pose = self._arg(pose, "pose", (t.float32,), (self.num_envs, 7 + self.n))
-        if mask is not None:
-            mask = self._arg(mask, "mask", (t.uint8, t.bool), (self.num_envs,))
-        self.stepper.set_reset_pose_device(pose.data_ptr(), mask.data_ptr() if mask is not None else 0, self._stream())
-        self._keep(pose, mask)
+        self._reset_pose_dev(pose, mask)
 
     def fork(self, src, dst, reset_pose=False):
         """Env dst[i] becomes env src[i] in everything a Snapshot holds: state record, contact cache, free box, ground
@@ -674,7 +651,8 @@ class ShardedVecEnv(object):
         if self.rank == self.root:
             a = t.as_tensor(actions, dtype=t.float32)       # shares memory with a float32 ndarray / tensor
             a2 = a[:, :, 0] if (a.dim() == 3 and a.shape[2] == 1) else a
-            assert tuple(a2.shape) == (self.num_envs, self.A), a2.shape
+            if tuple(a2.shape) != (self.num_envs, self.A):
+                raise _lib._ArgError("actions must have shape %s, got %s" % ((self.num_envs, self.A), tuple(a2.shape)))
             self._act_all.copy_(a2, non_blocking=True)      # (asynchronous only from pinned host memory / the device)
             chunks = list(self._act_all.split(self.E, dim=0))
         else:

@@ -32,6 +32,80 @@ def test_library_exports_every_declared_symbol(pkg):
     assert sorted(_lib.SYMBOLS) == declared
 
 
+def _header():
+    """(include/snk.h without comments and preprocessor lines, its `#define SNK_<NAME> <integer>` lines as a dict)"""
+    txt = open(os.path.join(ROOT, "include", "snk.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", " ", txt)
+    defines = {m.group(1): int(m.group(2), 0)
+               for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+SNK_(\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", txt, flags=re.M)}
+    return re.sub(r"^[ \t]*#[^\n]*$", " ", txt, flags=re.M), defines
+
+
+_C_SCALARS = {"int": "int", "int32_t": "int", "uint32_t": "uint32", "float": "float", "double": "double", "void": "void"}
+_C_POINTEES = {"float": ctypes.c_float, "double": ctypes.c_double, "int32_t": ctypes.c_int32, "uint8_t": ctypes.c_uint8,
+               "uint64_t": ctypes.c_uint64}
+
+
+def _c_kind(decl):
+    """The kind of a C parameter or return type: (scalar kind, None) or ("pointer", the ctypes type a typed binding of a
+    one-level pointer must point to, None where any does)."""
+    words = re.findall(r"\w+", re.sub(r"\[[^\]]*\]", "", decl))
+    words = [w for w in words if w not in ("const", "struct", "unsigned", "signed")]
+    levels = decl.count("*") + decl.count("[")
+    base = words[0]                               # (a parameter's name, when it has one, is words[1])
+    if levels:
+        return "pointer", _C_POINTEES.get(base) if levels == 1 else None
+    assert base in _C_SCALARS, "include/snk.h: a type this test does not know: %r" % decl
+    return _C_SCALARS[base], None
+
+
+def _ctypes_kind(tp):
+    if tp is None:
+        return "void", None
+    if tp in (ctypes.c_void_p, ctypes.c_char_p):
+        return "pointer", None
+    if hasattr(tp, "_type_") and not isinstance(tp._type_, str):          # ctypes.POINTER(...)
+        return "pointer", tp._type_
+    return {ctypes.c_int32: "int", ctypes.c_uint32: "uint32", ctypes.c_float: "float", ctypes.c_double: "double"}[tp], None
+
+
+def test_binding_table_matches_the_header_argument_by_argument(pkg):
+    """_lib.SYMBOLS against the prototypes of include/snk.h: the return kind and every argument's kind (pointer, int32_t /
+    int, uint32_t, float, double), and the pointee of a typed pointer.  A dropped argument or a c_float where the header
+    has an int32_t passes every other CPU test and corrupts a call on the GPU."""
+    _lib = importlib.import_module("bullet-envs_amd._lib")
+    txt, _ = _header()
+    protos = {}
+    for m in re.finditer(r"(?<=[;{}])\s*([\w\s\*]+?)\b(snk_\w+)\s*\(([^()]*)\)\s*;", txt):
+        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if ret.startswith("typedef"):
+            continue
+        assert name not in protos, name
+        protos[name] = (_c_kind(ret), [] if args in ("", "void") else [_c_kind(a) for a in args.split(",")])
+    assert sorted(protos) == _declared_symbols() == sorted(_lib.SYMBOLS)
+    assert len(protos) >= 79
+    for name, (ret, args) in sorted(protos.items()):
+        res, argtypes = _lib.SYMBOLS[name]
+        assert _ctypes_kind(res)[0] == ret[0], "%s: returns %s in the header, %r in SYMBOLS" % (name, ret[0], res)
+        assert len(argtypes) == len(args), "%s: %d arguments in the header, %d in SYMBOLS" % (name, len(args), len(argtypes))
+        for i, (tp, (kind, pointee)) in enumerate(zip(argtypes, args)):
+            got, typed = _ctypes_kind(tp)
+            assert got == kind, "%s: argument %d is %s in the header, %r in SYMBOLS" % (name, i, kind, tp)
+            if typed is not None and pointee is not None:
+                assert typed is pointee, "%s: argument %d points to %r in the header, %r in SYMBOLS" % (name, i, pointee, typed)
+
+
+def test_constants_mirror_the_header(pkg):
+    """Every `#define SNK_<NAME> <integer>` that _lib mirrors as <NAME> has the header's value."""
+    _lib = importlib.import_module("bullet-envs_amd._lib")
+    _, defines = _header()
+    mirrored = sorted(n for n in defines if hasattr(_lib, n))
+    assert len(mirrored) >= 18, mirrored
+    for n in mirrored:
+        assert getattr(_lib, n) == defines[n], "SNK_%s is %d in include/snk.h, %r in _lib" % (n, defines[n], getattr(_lib, n))
+
+
 def test_debug_rows_symbols_without_a_device(pkg):
     """snk_debug_rows_layout is host arithmetic (tests/test_np_rows.py holds its numbers to snk_lds.hpp); snk_debug_rows
     refuses its null arguments before it touches anything."""

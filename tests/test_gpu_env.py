@@ -522,6 +522,49 @@ def test_ragged_sizes_and_argument_errors(pkg):
     st.close()
 
 
+def test_shape_and_dtype_checks_refuse_before_the_call(pkg):
+    """Every check of a caller's array or tensor that was once an `assert` statement, hit once: each raises an
+    AssertionError (bullet-envs_amd/_lib.py: _ArgError, raised, so it holds under python -O) before anything reaches the
+    library.  Every bad argument owns at least as many bytes as the call would touch -- a larger array, or a wider dtype
+    of the right shape -- so a missing check shows as a failed pytest.raises, never as an access out of bounds.  The
+    handle stays usable: one good step afterwards gives, bit for bit, the observation of a fresh handle stepped alike."""
+    import torch
+    E, n = 4, 16
+    env = pkg.DeviceVecEnv(E, device_index=0, n_modules=n)
+    st = env.stepper
+    O, A = st.obs_dim, st.act_dim
+    env.reset()
+    for bad_call in (lambda: st.step(np.zeros((E, A + 1), np.float32)),
+                     lambda: st.step(np.zeros((E, A), np.float64)),
+                     lambda: st.substep(np.zeros((E, n + 1), np.float32)),
+                     lambda: st.set_state(np.zeros((E, st.state_dim + 1), np.float32)),
+                     lambda: st.set_state(aux=np.zeros((E, n + 3), np.float32)),
+                     lambda: st.set_manifold(np.zeros((E, 2 * n, 30), np.float32)),
+                     lambda: st.set_ground_friction(np.ones(E + 1, np.float32))):
+        with pytest.raises(AssertionError):
+            bad_call()
+    good = torch.from_numpy(gait(range(E), 0)).cuda()
+    wide = torch.zeros((E, A), dtype=torch.float64, device="cuda")
+    spare = torch.zeros((E + 1, O + 1), dtype=torch.float32, device="cuda")     # (E + 1)(O + 1) >= E (O + 2) floats
+    assert spare.numel() >= E * (O + 2)
+    for bad_call in (lambda: env.step(wide),
+                     lambda: env.step_packed(good, spare[:E]),                  # one column short, contiguous
+                     lambda: env.step_packed(wide, torch.zeros((E, O + 2), dtype=torch.float32, device="cuda")),
+                     lambda: env.step(good, substeps=torch.zeros(E, dtype=torch.int64, device="cuda"))):
+        with pytest.raises(AssertionError):
+            bad_call()
+    torch.cuda.synchronize()
+    fresh = pkg.DeviceVecEnv(E, device_index=0, n_modules=n)
+    fresh.reset()
+    obs = env.step(good.clone())[0]
+    ref = fresh.step(good.clone())[0]
+    torch.cuda.synchronize()
+    assert torch.equal(obs.view(torch.int32), ref.view(torch.int32))
+    assert bool(torch.isfinite(obs).all()) and float(obs.abs().max()) > 0
+    env.close()
+    fresh.close()
+
+
 def test_env_logic_branches(pkg, oracle_mod):
     """The servo loop's and the reward's rare branches, constructed on purpose, GPU vs oracle:
     0-substep step (snake.py:283 never enters the loop), the 41-substep cap (:303), height
